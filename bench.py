@@ -2,10 +2,15 @@
 """Benchmark of the hot path: BASELINE.json's metric -- train tokens/sec (whole node) of the 6L enc-dec d=512
 seq128 b64 MT train step -- on synthetic random-token batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., or
      plainly: without WORLD_SIZE in the environment the script starts its own N rank processes, one per GPU, BEFORE
      anything touches the GPU, and exits with the first non-zero rank exit code.)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the headline does not need:
+the instrumented pass of the library's per-launch profiler (the `roofline` object, adam_bytes_per_step) and the CPU
+baseline leg (`cpu_baseline`, unless --no-cpu-baseline); --breakdown runs the instrumented pass too and prints its table.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 The timed loop rotates through 8 distinct synthetic batches and alternates the two language directions, so neither
 cache residency of one batch nor the optimizer's skip of never-touched embedding rows / of the idle language head
@@ -14,7 +19,7 @@ flatters the number.
 One "step" = one pass of the hot path over one batch per rank: forward, label-smoothed NLL, backward, RCCL
 gradient all-reduce (N > 1, overlapped), global grad-norm clip, Adam -- the body of ImageMTTrainer.train_epoch
 (src/train_image_mt.py:239-295).  Tokens = non-pad TARGET tokens, the reference's own count (:256,:302-306).
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON result line; its `roofline` and `cpu_baseline` objects are null without --full.
 """
 import argparse
 import ctypes
@@ -139,6 +144,47 @@ def cpu_baseline(c, seconds_budget=15.0):
                       "([%d,%d] src/tgt), fp32 torch eager, dropout 0.1 (oracle/reference_model.py)" % (n, Bs, Bs, c["S"])}
 
 
+DUMP_SAMPLE = 1 << 20  # sampled positions per parameter-sized output of --dump-outputs (4 MiB each in float32)
+
+
+def dump_outputs(out_dir, model, opt, loss, ntokens):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy (float64 scalars, float32 samples), so that
+    two builds can be compared output for output on the same seeded inputs:
+      loss, ntokens          what train_step returned (label-smoothed NLL mean, non-pad target tokens)
+      grad_norm              the global gradient norm the step clipped with
+      params_sample          the updated fp32 master weights,
+      adam_exp_avg_sample    Adam's first and
+      adam_exp_avg_sq_sample second moments, each at the same DUMP_SAMPLE positions drawn with a fixed seed over all
+                             parameters in named_parameters() order (independent of the flat store's layout)."""
+    import numpy as np
+    from imagetranslate_amd.param_store import store_of
+    st = store_of(model)
+    if not st.valid() or st.exp_avg is None:
+        raise RuntimeError("dump_outputs: the parameters and Adam moments are not in the model's flat store")
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    g = torch.Generator().manual_seed(4321)
+    idx = torch.randint(0, total, (min(DUMP_SAMPLE, total),), generator=g).sort().values.to(st.flat.device)
+
+    def sample(of):
+        return torch.cat([of(p).reshape(-1) for p in params]).index_select(0, idx).float().cpu().numpy()
+
+    def moment(buf):
+        return lambda p: buf[st.offset(p):st.offset(p) + p.numel()]
+
+    arrays = {"loss": np.array([float(loss.detach())], np.float64),
+              "ntokens": np.array([float(ntokens)], np.float64),
+              "params_sample": sample(lambda p: p.detach()),
+              "adam_exp_avg_sample": sample(moment(st.exp_avg)),
+              "adam_exp_avg_sq_sample": sample(moment(st.exp_avg_sq))}
+    if opt.last_grad_norm_sq is not None:
+        arrays["grad_norm"] = np.array([float(opt.last_grad_norm_sq.double().sum().sqrt())], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def profile_pass(step_fn, steps=2):
     """Re-run a few steps with the library's per-launch HIP-event profiler on; returns per-kind rows."""
     from imagetranslate_amd import _lib as L
@@ -260,7 +306,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also the instrumented pass (roofline object) and the CPU baseline leg; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -318,7 +370,7 @@ def main():
     first = counter[0]
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, ntok_last = step()
     fence()
     ntok_timed = sum(ntoks[(first + k) % len(batches)] for k in range(args.steps))
     ntok_step = ntok_timed / max(1, args.steps)
@@ -332,17 +384,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         ntok_all = float(t)
     loss_val = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, model, opt, loss, ntok_last)
+        print("[bench] last timed step's outputs (%s) written to %s" % (", ".join(names), args.dump_outputs), file=sys.stderr, flush=True)
 
-    # instrumented pass: EVERY rank runs the same extra steps (they contain collectives); only rank 0 records events
-    if rank == 0:
-        rows = profile_pass(step)
-    else:
-        rows = []
-        for _ in range(2):
-            step()
-        torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
+    # instrumented pass (--full, --breakdown): EVERY rank runs the same extra steps (they contain collectives); only rank 0
+    # records events
+    rows = []
+    if args.full or args.breakdown:
+        if rank == 0:
+            rows = profile_pass(step)
+        else:
+            for _ in range(2):
+                step()
+            torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
@@ -409,7 +466,7 @@ def main():
                 print("%-40s %8d %10.3f %9.1f %9.1f" % (r["kind"], r["launches"], r["ms"], r["flops"] / (r["ms"] * 1e9 + 1e-30),
                                                         r["bytes"] / (r["ms"] * 1e6 + 1e-30)), file=sys.stderr)
             print("sum of kernel time %.3f ms / step (instrumented pass)" % tot, file=sys.stderr, flush=True)
-        out["cpu_baseline"] = cpu_baseline(c) if (world == 1 and not args.no_cpu_baseline) else None
+        out["cpu_baseline"] = cpu_baseline(c) if (args.full and world == 1 and not args.no_cpu_baseline) else None
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

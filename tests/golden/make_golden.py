@@ -5,10 +5,11 @@
 * loss_kat.json : known-answer vectors from the REFERENCE's own src/loss.py (SmoothedNLLLoss), imported from
                   /root/reference/src -- inputs + expected per-row loss + d(mean loss)/dlogits through
                   F.log_softmax.  This is data (inputs/outputs), no reference source is copied.
-* toy_seq2seq.pt: whole-model vectors from THIS repo's oracle (oracle/reference_model.py) on the toy
+* toy_seq2seq/  : whole-model vectors from THIS repo's oracle (oracle/reference_model.py) on the toy
                   configuration of SURVEY.md section 8(c) (d=128, h=4, ff=512, 2+2 layers, V=1000, B=8, S=T=32,
                   dropout off, seed fixed): inputs, state_dict, encoder states, log-probs, loss, selected grads,
-                  three optimizer steps.  The reference's own tests pin nothing numeric for the model
+                  three optimizer steps, in shards of under 1 MiB (tests/util.py save_sharded / load_toy).  The reference's
+                  own tests pin nothing numeric for the model
                   (parity unpinned) -- this fixture guards the oracle against drift.
 * beam_kat.json : known-answer vectors from the REFERENCE's own src/seq_gen.py get_outputs_until_eos (imported
                   from /root/reference/src): token matrices + eos / size_limit / remove_first_token -> cut rows.
@@ -17,7 +18,7 @@
                   <mask>=3, </s>=4, language tags next; framing of a "<lang> ... </s>" line), both imported from
                   /root/reference/src.
 * toy_beam.pt   : beam-search token ids from THIS repo's oracle (oracle/seq_gen.py) on the toy model derived from
-                  toy_seq2seq.pt by tests/util.py:beam_state_dict (matrices x2, EOS bias) so that hypotheses finish
+                  toy_seq2seq/ by tests/util.py:beam_state_dict (matrices x2, EOS bias) so that hypotheses finish
                   at different steps; text (beam 1 / 4, with and without unpadding) and image-only captioning.
                   The reference has no test or fixture for beam search (parity unpinned).
 * beam_step1_kat.pt: the REFERENCE's own src/seq_gen.py BeamDecoder.forward run un-modified (imported from /root/reference/src)
@@ -26,6 +27,9 @@
                   handling, decoder call, log_softmax, EOS zeroing, length penalty, top-k over V, the cat of the chosen word
                   (src/seq_gen.py:94-131,133-203,225-233).  Recorded: the arguments / results of its ``torch.topk`` call and
                   the token rows it returns, for beam 1 / 4 / 5 on the text path and beam 3 on the ``images=`` path.
+* loss_live_kat.pt, beam_live_kat.json: the REFERENCE's own src/loss.py SmoothedNLLLoss and src/seq_gen.py
+                  BeamDecoder.forward(max_len=2) on the inputs of the two reference pins of tests/test_oracle_pinning.py
+                  (make_live_kat; the reference's src/ directory in REFERENCE_SRC).
 * marshal_kat/  : the REFERENCE's own src/create_mt_batches.py ``write()`` (imported) on a 50-line parallel corpus and on
                   the monolingual source side, with a tokenizer its own src/textprocessor.py trains and re-loads:
                   corpus, tokenizer files (vocab.json / merges.txt / langs) and the two marshal files it wrote.
@@ -44,6 +48,8 @@ import torch.nn.functional as F
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from util import load_sharded, save_sharded  # noqa: E402
 
 
 def make_loss_kat():
@@ -101,11 +107,11 @@ def make_toy():
     m.zero_grad()
     opt = R.AdamInverseSqrtWithWarmup(m.parameters(), lr=1e-3, betas=(0.9, 0.98), warmup_updates=2)
     losses = [R.train_step(m, opt, crit, batch)[0] for _ in range(3)]
-    torch.save({"batch": batch, "state_dict": sd0, "encoder_states": enc.detach(), "log_probs": lp.detach(),
-                "argmax": lp.argmax(-1), "loss": float(loss), "grads": grads, "step_losses": losses,
-                "updated_query_weight": named["encoder.encoder.layer.0.attention.self.query.weight"].detach().clone(),
-                "config": dict(vocab=1000, enc=2, dec=2, d=128, ff=512, heads=4, lr=1e-3, warmup=2)},
-               os.path.join(HERE, "toy_seq2seq.pt"))
+    save_sharded({"batch": batch, "state_dict": sd0, "encoder_states": enc.detach(), "log_probs": lp.detach(),
+                  "argmax": lp.argmax(-1), "loss": float(loss), "grads": grads, "step_losses": losses,
+                  "updated_query_weight": named["encoder.encoder.layer.0.attention.self.query.weight"].detach().clone(),
+                  "config": dict(vocab=1000, enc=2, dec=2, d=128, ff=512, heads=4, lr=1e-3, warmup=2)},
+                 os.path.join(HERE, "toy_seq2seq"))
 
 
 def make_beam_kat():
@@ -132,7 +138,7 @@ def make_beam():
     from oracle.seq_gen import BeamDecoder
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from util import beam_inputs, beam_state_dict, caption_beam_inputs
-    fx = torch.load(os.path.join(HERE, "toy_seq2seq.pt"), weights_only=True)
+    fx = load_sharded(os.path.join(HERE, "toy_seq2seq"))
     tp = R.SyntheticTextProcessor(1000)
     m = R.Seq2Seq(tp, lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=128, intermediate_dim=512, num_attention_heads=4)
     m.load_state_dict(beam_state_dict(fx["state_dict"]))
@@ -224,7 +230,7 @@ def make_beam_step1_kat():
     from oracle import reference_model as R
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from util import beam_inputs, beam_state_dict, caption_beam_inputs
-    fx = torch.load(os.path.join(HERE, "toy_seq2seq.pt"), weights_only=True)
+    fx = load_sharded(os.path.join(HERE, "toy_seq2seq"))
     gold_beam = torch.load(os.path.join(HERE, "toy_beam.pt"), weights_only=True)
     tp = R.SyntheticTextProcessor(1000)
     kw = dict(lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=128, intermediate_dim=512, num_attention_heads=4)
@@ -247,6 +253,39 @@ def make_beam_step1_kat():
     for k, v in res.items():
         if isinstance(v, dict):
             print(k, [t.tolist() for t in v["tokens"]][:3])
+
+
+def make_live_kat():
+    """loss_live_kat.pt / beam_live_kat.json: what the REFERENCE's own src/loss.py SmoothedNLLLoss and src/seq_gen.py
+    BeamDecoder.forward(max_len=2) return on the inputs of tests/test_oracle_pinning.py's two reference pins (other inputs
+    than loss_kat.json / beam_step1_kat.pt), recorded so that the pins need no reference checkout.  The reference's src/
+    directory is given in REFERENCE_SRC."""
+    sys.path.insert(0, os.environ["REFERENCE_SRC"])
+    import loss as ref_loss  # the reference's own files
+    import seq_gen as ref_gen
+    from oracle import reference_model as R
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from util import beam_inputs, beam_state_dict
+    g = torch.Generator().manual_seed(5)
+    lp = F.log_softmax(torch.randn(33, 50, generator=g), -1)
+    t = torch.randint(0, 50, (33,), generator=g)
+    torch.save({"log_probs": lp, "target": t, "ignore_index": 0, "loss": ref_loss.SmoothedNLLLoss(ignore_index=0)(lp, t)},
+               os.path.join(HERE, "loss_live_kat.pt"))
+    fx = load_sharded(os.path.join(HERE, "toy_seq2seq"))
+    m = R.Seq2Seq(R.SyntheticTextProcessor(1000), lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=128, intermediate_dim=512,
+                  num_attention_heads=4)
+    m.load_state_dict(beam_state_dict(fx["state_dict"]))
+    m.eval()
+    inp = beam_inputs()
+    for k in ("src_inputs", "src_mask", "src_sizes"):  # the batch in reverse order
+        inp[k] = inp[k].flip(0)
+    with torch.no_grad():
+        toks = ref_gen.BeamDecoder(m, beam_width=3)(pad_idx=0, max_len=2, **inp)
+    out = {"source": "rasoolims/ImageTranslate src/seq_gen.py BeamDecoder(beam_width=3).forward(pad_idx=0, max_len=2) on "
+                     "oracle/reference_model.py, tests/util.py beam_inputs() with src_inputs / src_mask / src_sizes flipped",
+           "tokens": [x.tolist() for x in toks]}
+    json.dump(out, open(os.path.join(HERE, "beam_live_kat.json"), "w"), indent=1)
+    print("live kat: loss rows %d, beam tokens %s" % (lp.shape[0], out["tokens"]))
 
 
 def make_marshal_kat():
@@ -337,6 +376,7 @@ if __name__ == "__main__":
     make_beam_kat()
     make_beam()
     make_beam_step1_kat()
+    make_live_kat()
     make_marshal_kat()
     make_options_kat()
     make_sample_excerpt()

@@ -10,7 +10,7 @@ import torch
 from oracle import reference_model as R
 from oracle import seq_gen as OG
 from imagetranslate_amd import seq_gen as PG
-from util import beam_inputs, beam_state_dict, caption_beam_inputs
+from util import beam_inputs, beam_state_dict, caption_beam_inputs, load_toy
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -25,7 +25,7 @@ def test_get_outputs_until_eos_matches_reference_vectors(impl):
 
 
 def _toy_model():
-    fx = torch.load(os.path.join(GOLD, "toy_seq2seq.pt"), weights_only=True)
+    fx = load_toy()
     tp = R.SyntheticTextProcessor(1000)
     m = R.Seq2Seq(tp, lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=128, intermediate_dim=512, num_attention_heads=4)
     return m, fx["state_dict"]

@@ -226,8 +226,8 @@ def test_back_translation_step_against_oracle(cuda):
     from oracle import reference_model as R
     from oracle.seq_gen import BeamDecoder as OracleBeam
     from torch.nn.utils.rnn import pad_sequence
-    from tests.util import beam_state_dict
-    fx = torch.load(os.path.join(os.path.dirname(__file__), "golden", "toy_seq2seq.pt"), weights_only=True)
+    from tests.util import beam_state_dict, load_toy
+    fx = load_toy()
     kw = dict(lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=128, intermediate_dim=512, num_attention_heads=4)
     ref = R.Seq2Seq(R.SyntheticTextProcessor(1000), **kw)
     ref.load_state_dict(beam_state_dict(fx["state_dict"]))

@@ -9,7 +9,7 @@ import torch
 
 from oracle import reference_model as R
 from oracle import seq_gen as OG
-from tests.util import assert_close, beam_inputs, beam_state_dict, caption_beam_inputs
+from tests.util import assert_close, beam_inputs, beam_state_dict, caption_beam_inputs, load_toy
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -228,7 +228,7 @@ def _pair(cls="Seq2Seq", state=None, **kw):
 
 
 def _fixture_state(*a):
-    fx = torch.load(os.path.join(GOLD, "toy_seq2seq.pt"), weights_only=True)
+    fx = load_toy()
     return beam_state_dict(fx["state_dict"], *a)
 
 

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import reference_model as R
-from tests.util import assert_close
+from tests.util import assert_close, load_toy
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -103,7 +103,7 @@ def test_seq2seq_fp32_forward_backward_parity(cuda, depths):
 
 def test_fused_loss_equals_api_path_and_train_steps(cuda):
     from imagetranslate_amd.utils import AdamInverseSqrtWithWarmup
-    fx = torch.load(os.path.join(GOLD, "toy_seq2seq.pt"), weights_only=True)
+    fx = load_toy()
     c = fx["config"]
     import imagetranslate_amd.seq2seq as S
     tp = R.SyntheticTextProcessor(c["vocab"])

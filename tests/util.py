@@ -1,4 +1,54 @@
+import os
+
 import torch
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SHARD_BYTES = 900 * 1024  # tensor bytes per shard of a sharded fixture (every committed file stays under 1 MiB)
+
+
+def save_sharded(obj: dict, out_dir: str, shard_bytes: int = SHARD_BYTES):
+    """torch.save of a nested dict as out_dir/NN.pt shards of at most `shard_bytes` tensor bytes each (a single larger
+    tensor gets a shard of its own); load_sharded puts it back together."""
+    items = []
+
+    def walk(d, path):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                walk(v, path + (k,))
+            else:
+                items.append((path + (k,), v.clone() if torch.is_tensor(v) else v))
+    walk(obj, ())
+    shards, cur, size = [], [], 0
+    for path, v in items:
+        n = v.numel() * v.element_size() if torch.is_tensor(v) else 0
+        if cur and size + n > shard_bytes:
+            shards.append(cur)
+            cur, size = [], 0
+        cur.append((path, v))
+        size += n
+    shards.append(cur)
+    os.makedirs(out_dir, exist_ok=True)
+    for i, sh in enumerate(shards):
+        torch.save({"paths": [list(p) for p, _ in sh], "values": [v for _, v in sh]}, os.path.join(out_dir, "%02d.pt" % i))
+
+
+def load_sharded(out_dir: str) -> dict:
+    obj = {}
+    for f in sorted(os.listdir(out_dir)):
+        if not f.endswith(".pt"):
+            continue
+        sh = torch.load(os.path.join(out_dir, f), weights_only=True)
+        for path, v in zip(sh["paths"], sh["values"]):
+            d = obj
+            for k in path[:-1]:
+                d = d.setdefault(k, {})
+            d[path[-1]] = v
+    return obj
+
+
+def load_toy():
+    """The whole-model fixture of the toy configuration (tests/golden/make_golden.py make_toy), stored in shards."""
+    return load_sharded(os.path.join(GOLD, "toy_seq2seq"))
 
 
 def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:

@@ -2,11 +2,12 @@
 # Kernel trace of the bench step (with IMT_DW_SIDE_STREAM=0: one stream, so "gap" = time with NO kernel running) and the
 # idle-time summary of tools/trace_gaps.py: how much of a step sits between dependent launches.
 set -e
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/gaps
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export IMT_DW_SIDE_STREAM=0 IMT_ADAM_OVERLAP=0
-rocprofv3 --kernel-trace --output-format csv -d $OUT/rp -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2> $OUT/rp.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/rp -- python3 $REPO/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2> $OUT/rp.err
 F=$(ls $OUT/rp/*/*kernel_trace.csv | head -1)
 python3 - "$F" <<'PY'
 import csv, sys, collections
