@@ -192,6 +192,12 @@ SIGNATURES = {
     "imt_cast_f32_to_bf16": (c_int, [_P, _P, c_int64, _P]),
     "imt_gated_mix": (c_int, [c_int, _P, _P, _P, _P, c_int64, c_int, _P]),
     "imt_add_rows_dropout": (c_int, [c_int, _P, c_int, _P, _P, c_int64, c_int, c_int, c_float, c_uint64, _P]),
+    "imt_obj_rows": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P, _P]),
+    "imt_relu_dropout": (c_int, [c_int, _P, c_int64, c_int, c_float, c_uint64, _P]),
+    "imt_relu_dropout_bwd": (c_int, [c_int, _P, _P, _P, c_int64, c_int, c_float, c_uint64, _P]),
+    "imt_obj_fold_w": (c_int, [_P, _P, c_int, c_int, _P]),
+    "imt_obj_embed_grad": (c_int, [c_int, _P, _P, c_int64, _P, c_int64, c_int, _P]),
+    "imt_gated_mix_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
     "imt_comm_unique_id_bytes": (c_int, []),
     "imt_comm_get_unique_id": (c_int, [_P]),
     "imt_comm_init": (c_int, [_P, c_int, c_int, POINTER(c_void_p)]),

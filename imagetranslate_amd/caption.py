@@ -1,6 +1,7 @@
 """Caption a directory of images with beam search -- counterpart of src/caption.py (``build_model`` ``:62-73``,
 ``build_data_loader`` ``:49-59``, ``caption_batch`` ``:32-46``; same flags).  The image directory holds pre-extracted
-region features (``features.pt``, dataset.RegionFeatures) in place of pixels: the CNN trunk is outside the hot path."""
+region features (``features.pt``, dataset.RegionFeatures) in place of pixels: the CNN trunk is outside the hot path.
+With ``--obj`` the detector output stored beside them (``obj_feats`` / ``obj_boxes`` / ``obj_labels``) feeds the object stream."""
 import datetime
 from optparse import OptionParser
 
@@ -29,7 +30,7 @@ def get_lm_option_parser():
 @torch.no_grad()
 def caption_batch(batch, generator, text_processor, max_len: int = 256):
     outputs = generator(first_tokens=batch["first_tokens"], images=batch["images"], tgt_langs=batch["tgt_langs"],
-                        pad_idx=text_processor.pad_token_id(), max_len=max_len)
+                        pad_idx=text_processor.pad_token_id(), max_len=max_len, objects=batch.get("objects"))
     return [text_processor.decode(h[1:].tolist()) for h in outputs], batch["paths"]
 
 

@@ -142,6 +142,11 @@ class MassDataset(Dataset):
 # pre-extracted region features.  A feature directory holds ``features.pt`` = torch.save({"paths": [str, ...],
 # "feats": Tensor[n_images, regions, C]}) (read with ``weights_only=True``).  The caption file is the reference's own:
 # marshal of (unique_images: {image id: path}, captions: [(image id, caption ids), ...]) (src/dataset.py:301-306).
+# Optionally, the frozen Faster-RCNN's output (src/image_model.py:44-82) enters the same way: "obj_feats" [n_images, M, 1024]
+# (box features), "obj_boxes" [n_images, M, 4] (x1, y1, x2, y2 in pixels of the detector's 800-pixel frame) and "obj_labels"
+# [n_images, M] int64 in [0, 91), real detections first, label 0 = padding.  Batches then carry batch["objects"] =
+# {"feats", "boxes", "labels"} trimmed to the batch's largest real count (the reference pads to the batch maximum, :53-57);
+# a batch without a single detection carries no "objects" (no object stream, :53).
 class RegionFeatures:
     def __init__(self, root_img_dir: str):
         import os
@@ -150,6 +155,32 @@ class RegionFeatures:
         self.feats = blob["feats"]
         assert self.feats.dim() == 3 and self.feats.size(0) == len(self.paths), "features.pt: feats must be [n_images, regions, C]"
         self.index = {p: i for i, p in enumerate(self.paths)}
+        self.obj_feats, self.obj_boxes, self.obj_labels = blob.get("obj_feats"), blob.get("obj_boxes"), blob.get("obj_labels")
+        if self.obj_labels is not None:
+            M = self.obj_labels.size(1)
+            assert self.obj_labels.dim() == 2 and self.obj_labels.size(0) == len(self.paths), "features.pt: obj_labels must be [n_images, M]"
+            assert tuple(self.obj_feats.shape) == (len(self.paths), M, 1024), "features.pt: obj_feats must be [n_images, M, 1024]"
+            assert tuple(self.obj_boxes.shape) == (len(self.paths), M, 4), "features.pt: obj_boxes must be [n_images, M, 4]"
+            self.obj_labels = self.obj_labels.long()
+            assert M == 0 or (int(self.obj_labels.min()) >= 0 and int(self.obj_labels.max()) < 91), "features.pt: obj_labels outside [0, 91)"
+
+    def get_objects(self, paths):
+        """batch["objects"] for these images, trimmed to their largest real detection count, or None (no object keys in
+        features.pt, or no detection in any of these images)."""
+        if self.obj_labels is None:
+            return None
+        rows = [self.index.get(p, -1) for p in paths]
+        labels = self.obj_labels[[max(r, 0) for r in rows]].clone()
+        for k, r in enumerate(rows):
+            if r < 0:
+                labels[k].zero_()
+        real = labels != 0
+        n = int((real.long() * torch.arange(1, labels.size(1) + 1)).max()) if labels.numel() else 0  # last real column + 1
+        if n == 0:
+            return None
+        idx = [max(r, 0) for r in rows]
+        return {"feats": self.obj_feats[idx, :n].float().clone(), "boxes": self.obj_boxes[idx, :n].float().clone(),
+                "labels": labels[:, :n].contiguous()}
 
     def get(self, paths) -> torch.Tensor:
         """[len(paths), regions, C]; an image without features gets zeros (the reference substitutes a black image, :367)."""
@@ -159,6 +190,13 @@ class RegionFeatures:
             if r < 0:
                 out[k].zero_()
         return out
+
+
+def _with_objects(batch, features, paths):
+    objects = features.get_objects(paths) if hasattr(features, "get_objects") else None
+    if objects is not None:
+        batch["objects"] = objects
+    return batch
 
 
 class ImageCaptionDataset(Dataset):
@@ -205,9 +243,10 @@ class ImageCaptionDataset(Dataset):
 
     def __getitem__(self, item):
         texts, mask, pad_indices = self.batches[item]
-        feats = self.features.get([self.unique_images[i] for i in self.image_batches[item]])
-        return {"images": feats, "captions": texts, "pad_idx": pad_indices, "langs": torch.LongTensor([self.lang] * texts.size(0)),
-                "caption_mask": mask, "proposal": None}
+        paths = [self.unique_images[i] for i in self.image_batches[item]]
+        out = {"images": self.features.get(paths), "captions": texts, "pad_idx": pad_indices,
+               "langs": torch.LongTensor([self.lang] * texts.size(0)), "caption_mask": mask, "proposal": None}
+        return _with_objects(out, self.features, paths)
 
 
 class ImageCaptionTestDataset(ImageCaptionDataset):
@@ -224,9 +263,10 @@ class ImageCaptionTestDataset(ImageCaptionDataset):
             refs[image_id].append(cap)
         max_len = int(texts.size(1))
         first_tokens = torch.LongTensor([int(refs[i][0][0]) for i in order])
-        feats = self.features.get([self.unique_images[i] for i in order])
-        return {"images": feats, "img_ids": order, "captions": refs, "first_tokens": first_tokens,
-                "langs": torch.LongTensor([self.lang] * len(order)), "max_len": max_len + 10, "proposal": None}
+        paths = [self.unique_images[i] for i in order]
+        out = {"images": self.features.get(paths), "img_ids": order, "captions": refs, "first_tokens": first_tokens,
+               "langs": torch.LongTensor([self.lang] * len(order)), "max_len": max_len + 10, "proposal": None}
+        return _with_objects(out, self.features, paths)
 
 
 class ImageDataset(Dataset):
@@ -244,5 +284,6 @@ class ImageDataset(Dataset):
 
     def __getitem__(self, item):
         paths = self.image_batches[item]
-        return {"images": self.features.get(paths), "tgt_langs": torch.LongTensor([self.target_lang] * len(paths)),
-                "first_tokens": torch.LongTensor([self.first_token] * len(paths)), "paths": paths}
+        out = {"images": self.features.get(paths), "tgt_langs": torch.LongTensor([self.target_lang] * len(paths)),
+               "first_tokens": torch.LongTensor([self.first_token] * len(paths)), "paths": paths}
+        return _with_objects(out, self.features, paths)

@@ -411,6 +411,79 @@ def gated_mix(a, b, gate):
     return out
 
 
+OBJ_FEAT_DIM, OBJ_LABELS, GATED_MIX_BWD_PARTS = 1024, 91, 64  # include/imt_hip.h: IMT_OBJ_FEAT_DIM, IMT_OBJ_LABELS, IMT_GATED_MIX_BWD_PARTS
+
+
+def obj_padded_k(d):
+    """Kp of the object head's padded operands: d + 1031 rounded up to 64."""
+    return (d + OBJ_FEAT_DIM + 7 + 63) // 64 * 64
+
+
+def obj_rows(labels, feats, boxes, emb, w, d, dtype, want_w=True, status=None):
+    """(X [R, Kp], W_pad [d, Kp] or None) of the object head (imt_obj_rows); labels [R] int64, feats [R, 1024] fp32 / bf16,
+    boxes [R, 4] fp32, emb = flat [91 * d] slice, w = flat [d * (d + 1031)] slice, both in `dtype`."""
+    _req_cuda(labels, feats, boxes, emb, w, status)
+    assert labels.dtype == torch.int64 and boxes.dtype == torch.float32 and feats.shape[-1] == OBJ_FEAT_DIM
+    assert labels.is_contiguous() and feats.is_contiguous() and boxes.is_contiguous() and emb.is_contiguous() and w.is_contiguous()
+    assert emb.dtype == dtype and w.dtype == dtype and emb.numel() == OBJ_LABELS * d and w.numel() == d * (d + OBJ_FEAT_DIM + 7)
+    assert feats.numel() == labels.numel() * OBJ_FEAT_DIM and boxes.numel() == labels.numel() * 4
+    assert status is None or (status.dtype == torch.int32 and status.numel() >= 1)
+    R = labels.numel()
+    Kp = obj_padded_k(d)
+    x = torch.empty((R, Kp), device=emb.device, dtype=dtype)
+    w_pad = torch.empty((d, Kp), device=emb.device, dtype=dtype) if want_w else None
+    L.check(L.load().imt_obj_rows(dt(feats), IMT_F32 if dtype == torch.float32 else IMT_BF16, _p(labels), _p(feats), _p(boxes),
+                                  _p(emb), _p(w), _p(x), _p(w_pad), R, d, Kp, _p(status), _stream()), "imt_obj_rows")
+    return x, w_pad
+
+
+def relu_dropout_(y, dropout_p=0.0, dropout_seed=0):
+    _req_cuda(y)
+    assert y.dim() == 2 and y.is_contiguous()
+    L.check(L.load().imt_relu_dropout(dt(y), _p(y), y.shape[0], y.shape[1], float(dropout_p), int(dropout_seed), _stream()),
+            "imt_relu_dropout")
+    return y
+
+
+def relu_dropout_bwd(dy, y, dropout_p=0.0, dropout_seed=0):
+    _req_cuda(dy, y)
+    assert dy.shape == y.shape and dy.dtype == y.dtype and dy.is_contiguous() and y.is_contiguous()
+    dz = torch.empty_like(y)
+    L.check(L.load().imt_relu_dropout_bwd(dt(y), _p(dy), _p(y), _p(dz), y.shape[0], y.shape[1], float(dropout_p),
+                                          int(dropout_seed), _stream()), "imt_relu_dropout_bwd")
+    return dz
+
+
+def obj_fold_w(dw_pad, grad, d):
+    _req_cuda(dw_pad, grad)
+    assert dw_pad.dtype == torch.float32 and dw_pad.is_contiguous() and dw_pad.shape[0] == d
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == d * (d + OBJ_FEAT_DIM + 7)
+    L.check(L.load().imt_obj_fold_w(_p(dw_pad), _p(grad), d, dw_pad.shape[1], _stream()), "imt_obj_fold_w")
+
+
+def obj_embed_grad(labels, dx, grad):
+    _req_cuda(labels, dx, grad)
+    R, d = dx.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == R
+    assert dx.dim() == 2 and dx.stride(1) == 1
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == OBJ_LABELS * d
+    L.check(L.load().imt_obj_embed_grad(dt(dx), _p(labels), _p(dx), _rowmajor(dx), _p(grad), R, d, _stream()), "imt_obj_embed_grad")
+
+
+def gated_mix_bwd(dy, a, b, gate, dgate):
+    """(da, db); dgate (fp32 [d]) += the gate's gradient (imt_gated_mix_bwd, deterministic)."""
+    _req_cuda(dy, a, b, gate, dgate)
+    rows, d = a.shape
+    assert dy.shape == a.shape == b.shape and dy.dtype == a.dtype == b.dtype == gate.dtype
+    assert dy.is_contiguous() and a.is_contiguous() and b.is_contiguous() and gate.is_contiguous() and gate.numel() == d
+    assert dgate.dtype == torch.float32 and dgate.is_contiguous() and dgate.numel() == d
+    da, db = torch.empty_like(a), torch.empty_like(b)
+    ws = torch.empty((GATED_MIX_BWD_PARTS, d), device=a.device, dtype=torch.float32)
+    L.check(L.load().imt_gated_mix_bwd(dt(a), _p(dy), _p(a), _p(b), _p(gate), _p(da), _p(db), _p(dgate), _p(ws), rows, d, _stream()),
+            "imt_gated_mix_bwd")
+    return da, db
+
+
 def add_rows_dropout(x, add=None, out_dtype=None, dropout_p=0.0, dropout_seed=0):
     """out[r, :] = dropout(x[r, :] + add[r % add.shape[0], :]) for a 2-D x (imt_add_rows_dropout); add may be None."""
     _req_cuda(x, add)

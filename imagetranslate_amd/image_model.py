@@ -4,12 +4,14 @@
 The CNN trunk (torchvision ResNet / Faster-RCNN, ``:14-124``) is OUT of scope (frozen
 feature extractor whose pretrained weights need a network fetch); region features ``[B, 49, C]`` enter at the
 ``fc`` layer: ``ImageHead`` = dropout -> fc (no bias) -> + location_embedding -> dropout (``:35-41,77-78``).
+The detector's output (box features, boxes, labels) enters pre-extracted as ``batch["objects"]``: ``ImageCaptioning``
+then runs its object stream (object rows ``:58-78``, ``obj_decoder`` and ``multistream_attention_gate`` ``:357-366``).
 """
 import torch
 import torch.nn as nn
 
 from . import hip_ops as O
-from .bert_seq2seq import BertDecoderModel
+from .bert_seq2seq import BertDecoderModel, _Pretrained
 from .mass_seq2seq import MassSeq2Seq
 from .seq2seq import future_mask  # noqa: F401
 
@@ -58,6 +60,92 @@ class _ImageHeadFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+def _objects_present(objects):
+    """batch["objects"] = {"feats": [B,N,1024], "boxes": [B,N,4], "labels": [B,N] int64 (0 = padding)}; None, a missing key
+    or N == 0 means the batch has no object stream (the reference's max_feature_nums == 0, src/image_model.py:53), and so
+    does a batch whose labels are all 0 (padding only: no detection).  That last test is made for labels on the host only
+    (the loader already leaves "objects" out of a batch without detections): device labels would cost a synchronisation."""
+    if objects is None or objects.get("labels") is None:
+        return False
+    labels = objects["labels"]
+    if labels.dim() != 2 or labels.size(1) == 0:
+        return False
+    return labels.is_cuda or bool((labels != 0).any())
+
+
+class _ObjectHeadFn(torch.autograd.Function):
+    """Object rows of src/image_model.py:58-78 on the HIP kernels: ``imt_obj_rows`` stages [object_embedding[label] |
+    feature | locs] rows (label-0 rows zeroed whole) and the weight, both padded to Kp columns; ``imt_gemm`` NT is
+    object_feat_fc (no bias); ``imt_relu_dropout`` the ReLU and the dropout (training only).  Backward: the mask is
+    regenerated from the seed, dW is one TN GEMM into an fp32 [d, Kp] scratch folded into the flat gradient
+    (``imt_obj_fold_w``), the embedding rows' gradient dz W_pad[:, :d] is scattered by label in a fixed order
+    (``imt_obj_embed_grad``).  No gradient flows to the detector output (it runs under no_grad, :50-53)."""
+
+    @staticmethod
+    def forward(ctx, anchor, feats, boxes, labels, head, dtype, p, seed, status):
+        from .param_store import store_of
+        store = store_of(head).ensure()
+        flat = store.params_for(dtype)
+        w_p, e_p = head.object_feat_fc.weight, head.object_embedding.weight
+        d, K = w_p.shape
+        wo, eo = store.offset(w_p), store.offset(e_p)
+        B, N = labels.shape
+        x, w_pad = O.obj_rows(labels.reshape(-1).contiguous(), feats.reshape(B * N, -1).contiguous(),
+                              boxes.reshape(B * N, 4).contiguous(), flat[eo:eo + e_p.numel()], flat[wo:wo + d * K], d, dtype,
+                              status=status)
+        y = O.relu_dropout_(O.gemm(x, w_pad, O.IMT_NT, splitk_ws=O.splitk_workspace(x.device)), p, seed)
+        ctx.store, ctx.wo, ctx.eo, ctx.dims, ctx.p, ctx.seed = store, wo, eo, (B, N, d, K), p, seed
+        ctx.save_for_backward(x, w_pad, y, labels)
+        return y.view(B, N, d)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w_pad, y, labels = ctx.saved_tensors
+        store = ctx.store
+        B, N, d, K = ctx.dims
+        dz = O.relu_dropout_bwd(dout.to(y.dtype).reshape(B * N, d).contiguous(), y, ctx.p, ctx.seed)
+        dw = torch.empty(w_pad.shape, device=x.device, dtype=torch.float32)
+        O.gemm(dz, x, O.IMT_TN, out=dw)                                                   # dz^T X  [d, Kp]
+        O.obj_fold_w(dw, store.grad[ctx.wo:ctx.wo + d * K], d)                             # d(object_feat_fc.weight) +=
+        dxe = O.gemm(dz, w_pad[:, :d], O.IMT_NN, splitk_ws=O.splitk_workspace(x.device))  # d(embedding rows) [R, d]
+        O.obj_embed_grad(labels.reshape(-1).contiguous(), dxe, store.grad[ctx.eo:ctx.eo + O.OBJ_LABELS * d])
+        store.attach_grad_views()
+        return None, None, None, None, None, None, None, None, None
+
+
+class _GatedMixFn(torch.autograd.Function):
+    """sigmoid(gate + 1e-7) * a + (1 - sigmoid(gate + 1e-7)) * b (src/image_model.py:362-366): ``imt_gated_mix`` forward,
+    ``imt_gated_mix_bwd`` backward (the gate's gradient goes straight into the flat fp32 gradient)."""
+
+    @staticmethod
+    def forward(ctx, anchor, a, b, model, gate_param):
+        from .param_store import store_of
+        store = store_of(model).ensure()
+        d = a.shape[-1]
+        go = store.offset(gate_param)
+        gate = store.params_for(a.dtype)[go:go + d]
+        a2, b2 = a.reshape(-1, d).contiguous(), b.to(a.dtype).reshape(-1, d).contiguous()
+        ctx.store, ctx.go, ctx.shape = store, go, a.shape
+        ctx.save_for_backward(a2, b2, gate)
+        return O.gated_mix(a2, b2, gate).view(a.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        a2, b2, gate = ctx.saved_tensors
+        d = a2.shape[1]
+        da, db = O.gated_mix_bwd(dout.to(a2.dtype).reshape(-1, d).contiguous(), a2, b2, gate,
+                                 ctx.store.grad[ctx.go:ctx.go + d])
+        ctx.store.attach_grad_views()
+        return None, da.view(ctx.shape), db.view(ctx.shape), None, None
+
+
+def gated_mix(model, gate_param, a, b):
+    """Autograd-aware sigmoid-gated mix of two [..., d] streams with a gate parameter of ``model``'s flat store."""
+    from .param_store import store_of
+    anchor = store_of(model).ensure().anchor() if torch.is_grad_enabled() else None
+    return _GatedMixFn.apply(anchor, a, b, model, gate_param)
+
+
 class ImageHead(nn.Module):
     """Stands in for ModifiedResnet's head; ``feat_dim`` = channels of the frozen trunk (2048 for depth >= 3)."""
 
@@ -78,6 +166,66 @@ class ImageHead(nn.Module):
         seed = (int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if p > 0 else 0
         anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
         return _ImageHeadFn.apply(anchor, x, self, compute_dtype, p, seed), None
+
+    def add_object_head(self, embed_dim: int):
+        """object_feat_fc (Linear(d + 1031 -> d), no bias) and object_embedding (91 labels), src/image_model.py:110-116.
+        Built under a forked RNG: every other parameter of the model initialises exactly as without them."""
+        with torch.random.fork_rng(devices=[]):
+            self.object_feat_fc = nn.Linear(in_features=O.OBJ_FEAT_DIM + 7 + embed_dim, out_features=embed_dim, bias=False)
+            self.object_embedding = nn.Embedding(O.OBJ_LABELS, embed_dim)
+
+    def objects_forward(self, objects, compute_dtype=torch.float32):
+        """object_fc [B, N, d] (src/image_model.py:53-82) from pre-extracted detector output, or None when the batch has no
+        detections.  Labels must lie in [0, 91).  Host labels are checked here; for device labels imt_obj_rows zeroes an
+        out-of-range row and raises a status word that is read back without waiting (``check_object_labels``): the error
+        surfaces at the next call once that step has run, or at once with ``wait=True``."""
+        from .param_store import store_of
+        if not _objects_present(objects) or getattr(self, "object_feat_fc", None) is None:
+            return None
+        dev = self.object_feat_fc.weight.device
+        labels = objects["labels"]
+        status = None
+        if not labels.is_cuda:
+            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= O.OBJ_LABELS):
+                raise ValueError("objects: labels must lie in [0, %d)" % O.OBJ_LABELS)
+        else:
+            self.check_object_labels()
+            status = self.__dict__.get("_imt_label_status_dev")
+            if status is None or status.device != labels.device:
+                status = torch.zeros(1, dtype=torch.int32, device=labels.device)
+                self.__dict__["_imt_label_status_dev"] = status
+        labels = labels.to(device=dev, dtype=torch.int64)
+        feats = objects["feats"].to(dev)
+        if feats.dtype not in (torch.float32, torch.bfloat16):
+            feats = feats.float()
+        boxes = objects["boxes"].to(device=dev, dtype=torch.float32)
+        p = float(self.dropout) if self.training else 0.0
+        fixed = getattr(self, "_imt_dropout_seed", None)
+        seed = (int(fixed) + 2 if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if p > 0 else 0
+        anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
+        out = _ObjectHeadFn.apply(anchor, feats, boxes, labels, self, compute_dtype, p, seed, status)
+        if status is not None:  # cumulative device word -> pinned host copy, read once its event has completed
+            host = self.__dict__.get("_imt_label_status_host")
+            if host is None:
+                host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+                self.__dict__["_imt_label_status_host"] = host
+            host.copy_(status, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.__dict__["_imt_label_status_event"] = ev
+        return out
+
+    def check_object_labels(self, wait: bool = False):
+        """Raise if a device-resident label outside [0, 91) has reached the object head (its row was zeroed).  Without
+        ``wait`` only a read-back that has already completed is looked at (no synchronisation)."""
+        ev = self.__dict__.get("_imt_label_status_event")
+        if ev is None or (not wait and not ev.query()):
+            return
+        ev.synchronize()
+        self.__dict__["_imt_label_status_event"] = None
+        if int(self.__dict__["_imt_label_status_host"][0]) != 0:
+            self.__dict__["_imt_label_status_dev"].zero_()
+            raise ValueError("objects: a label outside [0, %d) reached the object head (its row was zeroed)" % O.OBJ_LABELS)
 
 
 class ImageMassSeq2Seq(MassSeq2Seq):
@@ -148,30 +296,73 @@ class ImageCaptioning(ImageMassSeq2Seq):
                                               freeze_image=freeze_image, resnet_depth=resnet_depth,
                                               num_attention_heads=num_attention_heads, image_feat_dim=image_feat_dim)
         if use_obj:
-            # object stream (Faster-RCNN features, :286-296): parameters are created for checkpoint compatibility,
-            # but no object features exist without the detector, so the stream stays inactive (object_fc is None).
+            # object stream (detector features, :279-296): the object head's parameters live in image_model, the second
+            # decoder is built from self.config (enc_layer layers, :281,287), not from dec_config
+            self.image_model.add_object_head(self.config.hidden_size)
+            tie = _Pretrained._tie_or_clone_weights
             if not lang_dec:
                 self.obj_decoder = BertDecoderModel(self.config)
+                if tie_embed:  # :284-285: only re-registers output_layer.weight (already the decoder's word table)
+                    tie(self.output_layer, self.decoder.embeddings.word_embeddings)
             else:
                 import copy
                 dec = BertDecoderModel(self.config)
                 self.obj_decoder = nn.ModuleList([copy.deepcopy(dec) for _ in text_processor.languages])
+                for i, dec in enumerate(self.obj_decoder):  # :288-294, in the reference's order and argument order
+                    if tie_embed:
+                        dec.embeddings.position_embeddings = self.encoder.embeddings.position_embeddings
+                    tie(self.output_layer[i], dec.embeddings.word_embeddings)
+                    tie(self.encoder.embeddings.token_type_embeddings, dec.embeddings.token_type_embeddings)
             self.multistream_attention_gate = nn.Parameter(torch.zeros(1, self.config.hidden_size).fill_(0.1),
                                                            requires_grad=True)
             self._link_stacks()
 
-    def encode(self, src_inputs=None, src_mask=None, src_langs=None, images=None):
+    def flat_param_order(self):
+        """The object stream's parameters go last in the flat store: every other parameter keeps the offset it has in a
+        model without them (and so does every gradient a batch without objects makes nonzero).  The object decoders are
+        laid out like the decoders (q|k|v and the cross key|value projections contiguous, as the stack runtime needs)."""
+        ps = super().flat_param_order()
+        obj = self._modules.get("obj_decoder")
+        if obj is None:
+            return ps
+        img = self.image_model
+        objs = list(obj) if isinstance(obj, nn.ModuleList) else [obj]
+        head = [img.object_feat_fc.weight, img.object_embedding.weight]
+        late = {id(p) for od in objs for p in od.parameters()} | {id(self.multistream_attention_gate)} | {id(p) for p in head}
+        seen = {id(p) for p in ps}
+        for p in self.parameters():
+            if id(p) not in seen and id(p) not in late:
+                seen.add(id(p))
+                ps.append(p)
+        for od in objs:
+            ps += self._decoder_param_order(od)
+        return ps + [p for od in objs for p in od.parameters()] + [self.multistream_attention_gate] + head
+
+    def encode(self, src_inputs=None, src_mask=None, src_langs=None, images=None, objects=None):
+        """Images: (image_embeddings, object_fc or None) (src/image_model.py:298-308).  ``objects`` (build extension):
+        pre-extracted detector output in place of the frozen Faster-RCNN (see ``_objects_present``)."""
         if images is not None:
             if isinstance(images, list):
                 images = images[0]
-            return self.image_model(images, self._imt_compute_dtype)
+            image_embeddings, _ = self.image_model(images, self._imt_compute_dtype)
+            object_fc = None
+            if "obj_decoder" in self._modules:
+                object_fc = self.image_model.objects_forward(self._un(objects), self._imt_compute_dtype)
+            return image_embeddings, object_fc
         return MassSeq2Seq.encode(self, src_inputs, src_mask, src_langs)
+
+    def _mix_object_stream(self, decoder_output, object_fc, batch_lang, **dec_kw):
+        """Second decoder pass over object_fc (no key mask: padded object rows take part, src/image_model.py:357-361) and
+        the sigmoid-gated mix with the image decoder's output (:362-366)."""
+        obj_decoder = self.obj_decoder if not self.lang_dec else self.obj_decoder[batch_lang]
+        object_output = obj_decoder(encoder_states=object_fc, **dec_kw)
+        return gated_mix(self, self.multistream_attention_gate, decoder_output, object_output)
 
     def _caption_rows(self, batch, src_pads, tgt_inputs, tgt_langs, tgt_mask, pad_idx, tgt_positions, proposals):
         u = self._un
         tgt_positions, tgt_inputs, tgt_mask, tgt_langs = u(tgt_positions), u(tgt_inputs), u(tgt_mask), u(tgt_langs)
         device = self.encoder.embeddings.word_embeddings.weight.device
-        image_embeddings, object_fc = self.encode(images=batch["images"])
+        image_embeddings, object_fc = self.encode(images=batch["images"], objects=batch.get("objects"))
         assert tgt_inputs is not None
         tgt_inputs = tgt_inputs.to(device)
         tgt_mask = tgt_mask.to(device)
@@ -179,7 +370,7 @@ class ImageCaptioning(ImageMassSeq2Seq):
         tgt_langs_t = self._lang_grid(tgt_langs, tgt_inputs.size(-1), device)
         pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
         rows = self._decode(image_embeddings, u(src_pads), tgt_inputs, tgt_mask, tgt_langs_t, batch_lang,
-                            position_ids=pos, proposals=proposals, pad_idx=pad_idx)
+                            position_ids=pos, proposals=proposals, pad_idx=pad_idx, obj_states=object_fc)
         return rows, tgt_inputs, tgt_mask, batch_lang
 
     def forward(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, tgt_mask=None,

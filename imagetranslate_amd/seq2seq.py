@@ -216,22 +216,28 @@ class Seq2Seq(nn.Module):
         decs = list(self.decoder) if isinstance(self.decoder, nn.ModuleList) else [self.decoder]
         shared = {id(l.attention) for l in self.encoder.encoder.layer}
         for dec in decs:
-            layers = list(dec.decoder.layer)
-            for lyr in reversed(layers):
-                ps += lyr.ordered_params(with_self_attention=id(lyr.attention) not in shared, with_cross_key_value=False)
-            # the cross-attention key|value projections of ALL layers, contiguous in layer order ([L*2d, d] then [L*2d]):
-            # the runtime projects the encoder states for every layer with one GEMM (and one each for d(encoder states)
-            # and dW in backward); their gradients are final when the decoder's backward reaches layer 0
-            for lyr in layers:
-                ps += [lyr.crossattention.self.key.weight, lyr.crossattention.self.value.weight]
-            for lyr in layers:
-                ps += [lyr.crossattention.self.key.bias, lyr.crossattention.self.value.bias]
-            ps += [dec.embeddings.LayerNorm.weight, dec.embeddings.LayerNorm.bias]
+            ps += self._decoder_param_order(dec, shared)
         for lyr in reversed(list(self.encoder.encoder.layer)):
             ps += lyr.ordered_params()
         e = self.encoder.embeddings
         ps += [e.LayerNorm.weight, e.LayerNorm.bias, e.position_embeddings.weight, e.token_type_embeddings.weight,
                e.word_embeddings.weight]
+        return ps
+
+    @staticmethod
+    def _decoder_param_order(dec, shared=()):
+        ps = []
+        layers = list(dec.decoder.layer)
+        for lyr in reversed(layers):
+            ps += lyr.ordered_params(with_self_attention=id(lyr.attention) not in shared, with_cross_key_value=False)
+        # the cross-attention key|value projections of ALL layers, contiguous in layer order ([L*2d, d] then [L*2d]):
+        # the runtime projects the encoder states for every layer with one GEMM (and one each for d(encoder states)
+        # and dW in backward); their gradients are final when the decoder's backward reaches layer 0
+        for lyr in layers:
+            ps += [lyr.crossattention.self.key.weight, lyr.crossattention.self.value.weight]
+        for lyr in layers:
+            ps += [lyr.crossattention.self.key.bias, lyr.crossattention.self.value.bias]
+        ps += [dec.embeddings.LayerNorm.weight, dec.embeddings.LayerNorm.bias]
         return ps
 
     def _apply(self, fn, *a, **kw):
@@ -345,16 +351,18 @@ class Seq2Seq(nn.Module):
         return idx.to(torch.int32), tgt_inputs[:, 1:].reshape(-1)[idx]
 
     def _decode(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=None,
-                proposals=None, pad_idx=0, sel_idx=None):
+                proposals=None, pad_idx=0, sel_idx=None, obj_states=None):
         decoder = self.decoder if not self.lang_dec else self.decoder[batch_lang]
         info = self.__dict__.get("_imt_grid_info", {}).get(id(tgt_langs_t))
         if info is not None:  # a cached uniform grid: use the (T-1)-wide one instead of a non-contiguous slice
             types = self._uniform_grid(info[0], tgt_langs_t.size(1) - 1, info[1], tgt_langs_t.device)
         else:
             types = tgt_langs_t[:, :-1]
-        decoder_output = decoder(encoder_states=encoder_states, input_ids=tgt_inputs[:, :-1],
-                                 encoder_attention_mask=enc_mask, tgt_query_mask=tgt_mask[:, :-1],
-                                 position_ids=position_ids, token_type_ids=types)
+        dec_kw = dict(input_ids=tgt_inputs[:, :-1], encoder_attention_mask=enc_mask, tgt_query_mask=tgt_mask[:, :-1],
+                      position_ids=position_ids, token_type_ids=types)
+        decoder_output = decoder(encoder_states=encoder_states, **dec_kw)
+        if obj_states is not None:  # ImageCaptioning's object stream, mixed in before attend_proposal (src/image_model.py:357-369)
+            decoder_output = self._mix_object_stream(decoder_output, obj_states, batch_lang, **dec_kw)
         if self.use_proposals:
             decoder_output = self.attend_proposal(decoder_output, proposals, pad_idx)
         flat = decoder_output.reshape(-1, decoder_output.size(-1))

@@ -12,6 +12,11 @@ What differs is HOW a step is computed:
     "every hypothesis has EOS" stop condition (``:134-136``) every ``sync_every`` steps.
   * ``kv_cache=False`` keeps the reference's literal per-step recomputation (on the HIP decoder) -- used by the
     tests to show both modes produce the same tokens.
+  * ``objects=`` (build extension, ImageCaptioning with ``use_obj``): pre-extracted detector output in place of the
+    frozen Faster-RCNN (``{"feats", "boxes", "labels"}``, see image_model).  A second incremental decoder runs
+    ``obj_decoder`` over the object rows (its own cross K/V with Tk = N, workspace and self cache; the slot table is
+    shared) and its state is mixed into the image decoder's through the sigmoid gate before the projection
+    (``:164-180``; no key mask, the object rows of a sentence serve all its beams like the image states).
 Ties between equal scores (``torch.topk`` leaves them unspecified, and ``:194-196`` creates them on purpose) are
 broken towards the lowest flat index.  ``:216`` is taken as floor division (torch 1.4 semantics).
 """
@@ -88,10 +93,10 @@ class BeamDecoder(nn.Module):
     @torch.no_grad()
     def forward(self, src_inputs=None, src_sizes=None, first_tokens=None, src_mask=None, src_langs=None, tgt_langs=None,
                 pad_idx=None, max_len: int = None, unpad_output: bool = True, beam_width: int = None, images=None,
-                proposals=None, image_embed=None):
+                proposals=None, image_embed=None, objects=None):
         tgt_langs, first_tokens, src_langs, src_mask = _un(tgt_langs), _un(first_tokens), _un(src_langs), _un(src_mask)
         src_sizes, src_inputs, images, image_embed = _un(src_sizes), _un(src_inputs), _un(images), _un(image_embed)
-        proposals = _un(proposals)
+        proposals, objects = _un(proposals), _un(objects)
         model = self.seq2seq_model.module if hasattr(self.seq2seq_model, "module") else self.seq2seq_model
         if beam_width is None:
             beam_width = self.beam_width
@@ -114,6 +119,7 @@ class BeamDecoder(nn.Module):
 
         # ---- encoder side (once per search, :94-107)
         enc_mask = None
+        obj_fc = None
         if src_inputs is not None and images is None:
             src_mask = src_mask.to(device)
             src_langs_t = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1))
@@ -121,17 +127,19 @@ class BeamDecoder(nn.Module):
             enc_mask = src_mask.to(torch.uint8).contiguous()
         elif src_inputs is None:
             if image_embed is None:
-                encoder_states, obj_feat = model.encode(images=images.to(device))
-                if obj_feat is not None:
-                    raise NotImplementedError("object-stream decoding needs detector features (SURVEY 8(f) row 4)")
+                encoder_states, obj_fc = model.encode(images=images.to(device), **({"objects": objects} if objects is not None else {}))
             else:
                 encoder_states = image_embed.to(device)
+                if objects is not None and "obj_decoder" in model._modules:
+                    obj_fc = model.image_model.objects_forward(objects, model._imt_compute_dtype)
         else:
             raise NotImplementedError(
                 "image+text beam search: the reference's multimodal encode cannot run (SURVEY a16)")
         dtype = model._imt_compute_dtype
         encoder_states = encoder_states.to(dtype).contiguous()
         Tk = encoder_states.size(1)
+        if obj_fc is not None:
+            obj_fc = obj_fc.to(dtype).contiguous()
 
         eos = model.text_processor.sep_token_id()
         V = model.config.vocab_size
@@ -165,14 +173,22 @@ class BeamDecoder(nn.Module):
         wo, bo = store.offset(w_out), store.offset(b_out)
         W = flat[wo:wo + w_out.numel()].view(w_out.shape)
         bias = flat[bo:bo + b_out.numel()]
+        obj_decoder = gate = None
+        if obj_fc is not None:
+            obj_decoder = model.obj_decoder if not model.lang_dec else model.obj_decoder[batch_lang]
+            go = store.offset(model.multistream_attention_gate)
+            gate = flat[go:go + model.config.hidden_size]
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         lib = L.load()
 
-        inc = None
+        inc = inc_obj = None
         if self.kv_cache:
             inc = _Incremental(lib, decoder, store, dtype, flat, encoder_states, enc_mask, B, beam, t_max, stream)
+            if obj_fc is not None:
+                inc_obj = _Incremental(lib, obj_decoder, store, dtype, flat, obj_fc, None, B, beam, t_max, stream)
         logits = O.alloc_rows(B * beam, V, torch.float32, device)  # leading dimension padded to 8 for odd vocabularies
         hidden = torch.empty((B * beam, model.config.hidden_size), dtype=dtype, device=device)
+        hidden_obj = torch.empty_like(hidden) if inc_obj is not None else None
 
         n_cols = 1
         done_at = None
@@ -188,6 +204,9 @@ class BeamDecoder(nn.Module):
                 ids = first_tokens if i == 1 else st.tokens
                 inc.step(i - 1, rows, rep, ids, type_rows[0 if rep == 1 else 1], st.slots[cur], hidden)
                 states = hidden[:rows]
+                if inc_obj is not None:
+                    inc_obj.step(i - 1, rows, rep, ids, type_rows[0 if rep == 1 else 1], st.slots[cur], hidden_obj)
+                    states = O.gated_mix(states, hidden_obj[:rows], gate)
             else:
                 enc = encoder_states if rep == 1 else torch.repeat_interleave(encoder_states, rep, 0)
                 emask = None
@@ -197,6 +216,11 @@ class BeamDecoder(nn.Module):
                 types = type_rows[0 if rep == 1 else 1].unsqueeze(-1).expand(-1, i)
                 states = decoder(encoder_states=enc, input_ids=prefix, encoder_attention_mask=emask,
                                  tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
+                if obj_fc is not None:
+                    objs = obj_fc if rep == 1 else torch.repeat_interleave(obj_fc, rep, 0)
+                    obj_states = obj_decoder(encoder_states=objs, input_ids=prefix, encoder_attention_mask=None,
+                                             tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
+                    states = O.gated_mix(states.contiguous(), obj_states.contiguous(), gate)
             if model.use_proposals:
                 states = model.attend_proposal(states, proposals, pad_idx)
             O.gemm(states.contiguous(), W, O.IMT_NT, bias=bias, out=logits[:rows])
@@ -223,8 +247,12 @@ class BeamDecoder(nn.Module):
                     done_at = int(full[0, 0]) + 1
         if done_at is not None and done_at >= 1:
             n_cols = min(n_cols, done_at + 1)
+        if inc_obj is not None:
+            inc_obj.check()
         if inc is not None:
-            inc.check()   # raises if a one-launch decoder step was abandoned (bounded waits); one sync, the outputs are read next anyway
+            inc.check()
+        if obj_fc is not None:
+            model.image_model.check_object_labels(wait=True)  # device labels: the search synchronises here anyway   # raises if a one-launch decoder step was abandoned (bounded waits); one sync, the outputs are read next anyway
         outputs = st.hist[st.cur].view(B, beam, t_max)[:, 0, :n_cols]
         if unpad_output:
             return get_outputs_until_eos(eos, outputs, size_limit=max_lens_host)

@@ -2,7 +2,8 @@
 ``train`` ``:194-286``): image batches (region features -> ``fc`` + location embedding -> decoder) and, optionally,
 MT batches as a second task whose loss is weighted by ``--mtlw`` (``:83``); gradients of both tasks accumulate, the clip
 runs after every backward and the optimizer steps every ``--acc`` micro-steps (``:91-97``).  The model step is the HIP
-path (``ImageCaptioning.loss_fused``).  BLEU evaluation needs sacrebleu (absent): the dev set is scored by its loss and,
+path (``ImageCaptioning.loss_fused``); when features.pt carries detector output (``obj_*`` keys, dataset.RegionFeatures)
+and the model has its object stream (no ``--no-obj``), the batches' ``objects`` train it.  BLEU evaluation needs sacrebleu (absent): the dev set is scored by its loss and,
 with ``eval_captions``, decoded with beam search."""
 import datetime
 import os
@@ -73,7 +74,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
         for i in range(len(img_test_data) if max_batches is None else min(max_batches, len(img_test_data))):
             b = img_test_data[i]
             hyps = self.generator(images=b["images"], first_tokens=b["first_tokens"], tgt_langs=b["langs"],
-                                  pad_idx=tp.pad_token_id(), max_len=b["max_len"])
+                                  pad_idx=tp.pad_token_id(), max_len=b["max_len"], objects=b.get("objects"))
             for image_id, h in zip(b["img_ids"], hyps):
                 out[image_id] = tp.decode(h[1:].tolist()) if hasattr(tp, "decode") else h[1:].tolist()
         model.train()

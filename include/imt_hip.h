@@ -335,6 +335,38 @@ int imt_gated_mix(int dtype, const void* a, const void* b, const void* gate, voi
 int imt_add_rows_dropout(int in_dtype, const void* x, int out_dtype, void* out, const void* add, int64_t rows, int d,
                          int period, float dropout_p, uint64_t dropout_seed, void* stream);
 
+/* ------------------------------------------------------------------ object stream of ImageCaptioning
+ * Pre-extracted detector output (box features [R, 1024], boxes [R, 4] = x1 y1 x2 y2, labels [R] int64, 0 = padding) enters the
+ * object head of src/image_model.py:58-78: row = [object_embedding[label] (d) | feature (1024) | locs (7)], locs = x1/800,
+ * x2/800, y1/800, y2/800, w, h, w*h (w = x2/800 - x1/800, h likewise); a label-0 row is zeroed whole; then
+ * relu(object_feat_fc(row)) (no bias) and dropout.  K = d + 1031 is odd, so the product runs on K-padded operands:
+ * imt_obj_rows   : X [R, Kp] in `dtype` (Kp >= d + 1031, Kp % 8 == 0, pad columns zero) from labels / feats (`feat_dtype`) /
+ *                  boxes (fp32) / emb ([91, d], `dtype`); with w_out != NULL the same launch writes W_pad [d, Kp] from the
+ *                  [d, d + 1031] weight w.  Labels must lie in [0, 91) (caller's contract); an out-of-range label gives a zero
+ *                  row and, when status != NULL, sets *status |= 1 on the device.
+ * imt_relu_dropout     : y <- dropout(relu(y)) in place, [rows, d] contiguous, element index r * d + c (the other dropout sites' hash).
+ * imt_relu_dropout_bwd : dz = dy * (y > 0) * keep(seed, r * d + c) / (1 - p); y is the forward's output.
+ * imt_obj_fold_w       : grad[n, k] += dw_pad[n, k] for k < d + 1031 (dw_pad = fp32 [d, Kp] TN product dz^T X).
+ * imt_obj_embed_grad   : grad[l, :] += sum over rows with labels[r] == l of dx[r, :], l = 1 .. 90, in row order (deterministic,
+ *                        no atomics); dx = [R, >= d] with leading dimension ldx (dz W_pad[:, :d]); label 0 gets nothing.
+ * imt_gated_mix_bwd    : backward of imt_gated_mix (s = sigmoid(gate + 1e-7), out = s a + (1 - s) b; src/image_model.py:362-366,
+ *                        src/seq_gen.py:177-180): da = s dy, db = (1 - s) dy, dgate[c] += sum_r dy (a - b) s (1 - s) into fp32.
+ *                        Two stages in a fixed order: IMT_GATED_MIX_BWD_PARTS row ranges -> partial_ws [PARTS, d] fp32, then
+ *                        one fold; two identical calls give bit-identical dgate. */
+#define IMT_OBJ_FEAT_DIM 1024
+#define IMT_OBJ_LABELS 91
+#define IMT_GATED_MIX_BWD_PARTS 64
+int imt_obj_rows(int feat_dtype, int dtype, const int64_t* labels, const void* feats, const float* boxes, const void* emb,
+                 const void* w, void* x_out, void* w_out, int64_t R, int d, int Kp, int* status, void* stream);
+int imt_relu_dropout(int dtype, void* y, int64_t rows, int d, float dropout_p, uint64_t dropout_seed, void* stream);
+int imt_relu_dropout_bwd(int dtype, const void* dy, const void* y, void* dz, int64_t rows, int d, float dropout_p,
+                         uint64_t dropout_seed, void* stream);
+int imt_obj_fold_w(const float* dw_pad, float* grad, int d, int Kp, void* stream);
+int imt_obj_embed_grad(int dtype, const int64_t* labels, const void* dx, int64_t ldx, float* grad, int64_t R, int d,
+                       void* stream);
+int imt_gated_mix_bwd(int dtype, const void* dy, const void* a, const void* b, const void* gate, void* da, void* db,
+                      float* dgate, float* partial_ws, int64_t rows, int d, void* stream);
+
 
 /* ------------------------------------------------------------------ whole encoder / decoder stacks
  * The host-side runtime that chains the kernels above for BertEncoderModel.forward (src/bert_seq2seq.py:103-144)

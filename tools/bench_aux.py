@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """The two secondary workloads of SURVEY section 8(d) on one MI355X (the headline C1 stays in bench.py):
   C3 captioning: region features [32,49,2048] -> fc -> 6-layer decoder d=512 -> captions [32,32]   (0.265 TFLOP/step)
+  C3obj        : C3 plus the object stream: detector features [32,100,1024] with a seeded random number of real detections
+                 per image -> object head -> second 6-layer decoder (obj_decoder) -> sigmoid-gated mix; also the object head's
+                 own forward + backward time
   C4 MASS      : monolingual src [64,256], span of int(255/2) tokens masked on the device, 6L/6L d=512 (4.27 TFLOP/step)
 Prints one JSON line per workload: ms/step, target tokens/s, TFLOP/s against the algorithmic FLOP counts of the survey."""
 import json, os, random, sys, time
@@ -53,6 +56,45 @@ def c3():
             "tokens_per_s": round(n / sec, 1), "algorithmic_tflop_per_step": 0.265, "tflops": round(0.265 / sec, 1)}
 
 
+def c3obj():
+    torch.manual_seed(1234)
+    m = ImageCaptioning(tp, lang_dec=False, enc_layer=6, dec_layer=6, embed_dim=d, intermediate_dim=ff, use_obj=True,
+                        num_attention_heads=heads, image_feat_dim=2048)
+    m.set_compute_dtype(torch.bfloat16)
+    m = m.to(dev).train()
+    opt = AdamInverseSqrtWithWarmup(m.parameters(), lr=1e-4, betas=(0.9, 0.98), warmup_updates=4000)
+    g = torch.Generator().manual_seed(1234)
+    feats = torch.randn(32, 49, 2048, generator=g).to(dev)
+    cap = torch.randint(6, V, (32, 32), generator=g); cap[:, 0] = 6; cap[:, -1] = 4
+    cap = cap.to(dev)
+    langs = torch.ones(32, dtype=torch.long)
+    labels = torch.zeros(32, 100, dtype=torch.long)
+    for b, c in enumerate(torch.randint(1, 101, (32,), generator=g).tolist()):
+        labels[b, :c] = torch.randint(1, 91, (c,), generator=g)
+    labels = labels[:, :int((labels != 0).sum(1).max())]  # the loader trims to the batch's largest count
+    n_obj = labels.size(1)
+    xy = torch.rand(32, n_obj, 2, generator=g) * 600
+    objects = {"feats": torch.randn(32, n_obj, 1024, generator=g).to(dev), "boxes": torch.cat([xy, xy + 100], -1).to(dev),
+               "labels": labels.to(dev)}
+    batch = {"images": feats, "objects": objects}
+
+    def step():
+        loss, n = m.loss_fused(batch=batch, tgt_inputs=cap, tgt_langs=langs, tgt_mask=cap != 0, pad_idx=0)
+        loss.backward()
+        opt.step(max_grad_norm=1.0, zero_grad=True)
+        return n
+    sec, n = timed(step)
+
+    def head_step():
+        out = m.image_model.objects_forward(objects, torch.bfloat16)
+        out.backward(torch.ones_like(out))
+        return 0
+    head_sec, _ = timed(head_step)
+    return {"workload": "C3obj captioning + object stream: C3 + objects [32,%d,1024] -> 6L obj_decoder d=512" % n_obj,
+            "ms_per_step": round(1e3 * sec, 3), "tokens_per_s": round(n / sec, 1),
+            "object_head_fwd_bwd_ms": round(1e3 * head_sec, 3), "object_head_share": round(head_sec / sec, 4)}
+
+
 def c4():
     torch.manual_seed(1234)
     m = ImageMassSeq2Seq(tp, lang_dec=False, enc_layer=6, dec_layer=6, embed_dim=d, intermediate_dim=ff, num_attention_heads=heads)
@@ -79,5 +121,8 @@ def c4():
 
 if __name__ == "__main__":
     random.seed(0)
-    for fn in (c3, c4):
+    want = [a for a in sys.argv[1:] if not a.startswith("--")]
+    for fn in (c3, c3obj, c4):
+        if want and fn.__name__ not in want:
+            continue
         print(json.dumps(fn()), flush=True)
