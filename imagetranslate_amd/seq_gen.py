@@ -253,7 +253,10 @@ class BeamDecoder(nn.Module):
             inc.check()
         if obj_fc is not None:
             model.image_model.check_object_labels(wait=True)  # device labels: the search synchronises here anyway   # raises if a one-launch decoder step was abandoned (bounded waits); one sync, the outputs are read next anyway
-        outputs = st.hist[st.cur].view(B, beam, t_max)[:, 0, :n_cols]
+        if n_cols == 1:   # no step ran (max_len <= 1, or beam 1 with every first token EOS): one row per sentence
+            outputs = st.hist[st.cur][:B, :1]
+        else:
+            outputs = st.hist[st.cur].view(B, beam, t_max)[:, 0, :n_cols]
         if unpad_output:
             return get_outputs_until_eos(eos, outputs, size_limit=max_lens_host)
         outputs = outputs.cpu()
@@ -274,7 +277,8 @@ class _Incremental:
         self.B, self.r_max, self.t_max, self.Tk = B, B * beam, t_max, encoder_states.size(1)
         nbytes = lambda n, what: self._positive(n, what)
         self.ws_bytes = nbytes(lib.imt_decode_workspace_bytes(ctypes.byref(desc), self.r_max), "imt_decode_workspace_bytes")
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        # zeros: the sticky status word of the one-launch step (read by check()) is clean even if the search issues no step
+        self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.cache = torch.empty(nbytes(lib.imt_decode_self_cache_bytes(ctypes.byref(desc), self.r_max, t_max),
                                         "imt_decode_self_cache_bytes"), dtype=torch.uint8, device=dev)
         self.cross = torch.empty(nbytes(lib.imt_decode_cross_bytes(ctypes.byref(desc), B, self.Tk), "imt_decode_cross_bytes"),
