@@ -152,6 +152,19 @@ class MassArgs(Structure):
     ]
 
 
+class ScoreArgs(Structure):
+    _fields_ = [
+        ("dtype", c_int32), ("N", c_int32), ("V", c_int32), ("K", c_int32),
+        ("x", c_void_p), ("ldx", c_int64),
+        ("w", c_void_p), ("ldw", c_int64),
+        ("bias", c_void_p), ("target", c_void_p),
+        ("logprob", c_void_p), ("lse", c_void_p),
+        ("seg_offsets", c_void_p), ("n_seg", c_int32), ("normalize", c_int32),
+        ("seg_score", c_void_p),
+        ("ws", c_void_p), ("ws_bytes", c_int64),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/imt_hip.h declares (tests/test_cabi.py checks)
 _P = c_void_p
 SIGNATURES = {
@@ -183,6 +196,9 @@ SIGNATURES = {
     "imt_smoothed_nll_fwd": (c_int, [_P, c_int64, _P, _P, c_int, c_int, c_float, c_int64, _P]),
     "imt_smoothed_nll_bwd": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_float, c_int64, _P]),
     "imt_xent_fused_fwd_bwd": (c_int, [c_int, _P, c_int64, _P, _P, c_int, c_int, c_float, c_int64, c_float, _P]),
+    "imt_score_ws_bytes": (c_int64, [c_int, c_int]),
+    "imt_score_supported": (c_int, [c_int, c_int, c_int]),
+    "imt_score_rows": (c_int, [POINTER(ScoreArgs), _P]),
     "imt_scaled_sum": (c_int, [_P, c_int, c_float, _P, _P]),
     "imt_sumsq": (c_int, [_P, c_int64, _P, _P, _P]),
     "imt_ln_partial_reduce": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
@@ -235,7 +251,7 @@ class ImtError(RuntimeError):
 ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_row": ProfRow, "imt_attn_block": AttnBlock,
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
-               "imt_mass_args": MassArgs}
+               "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs}
 
 
 def load():

@@ -23,6 +23,7 @@
 //                            cross-check variant for the tests).
 #include <stdlib.h>
 #include "mma.hpp"
+#include "gemm_xl.hpp"
 
 // ---- build-time tuning switches (tools/build_variant.sh builds a second library with other values for A/B runs)
 #ifndef IMT_WS_NST
@@ -58,15 +59,8 @@
 namespace {
 
 constexpr int BM = 128, BN = 128, NTHREADS = 256;
-constexpr int TILE_BYTES = 16384;            // one operand tile
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // A + B
 
-template <typename T, bool KCONTIG> struct TileGeom {
-  static constexpr int EPC = 16 / sizeof(T);                  // elements per 16-B chunk
-  static constexpr int BK = 128 / sizeof(T);                  // K elements per tile
-  static constexpr int RB = KCONTIG ? 128 : 128 * sizeof(T);  // LDS row bytes
-  static constexpr int CPR = RB / 16;                         // chunks per row
-};
 
 // ------------------------------------------------------------------------------------------------ register staging
 template <typename T, bool KCONTIG> struct Stage : TileGeom<T, KCONTIG> {
@@ -974,46 +968,6 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
 // (A rows 0-127 / 128-255, B columns 0-127 / 128-255) in the usual swizzled geometry, two 64-KiB stages: waves 0-3
 // DMA the A sub-tiles, waves 4-7 the B sub-tiles of K tile t+1 while everyone multiplies tile t; one barrier per K tile.
 // The epilogue walks the four 128 x 128 quadrants with all 512 threads (the two owning waves restage, everyone stores).
-constexpr int XL_THREADS = 512;
-constexpr int XL_STAGE = 4 * TILE_BYTES;
-constexpr int XL_LDS = 2 * XL_STAGE;
-
-// One wave's share of TWO neighbouring 16-KiB sub-tiles (operand rows / columns +128): the second sub-tile's source
-// offsets are the first's plus a constant, so a wave keeps 4 offset registers whichever operand it streams.
-template <typename T> struct DmaPair {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int voff[4], kadv, delta, wv;
-  template <bool KCONTIG> IMT_DEVICE void init(const T* base, int64_t ld, int64_t valid_bytes, int row0, int wave) {
-    typedef TileGeom<T, KCONTIG> G;
-    rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)valid_bytes, 0x00020000);
-    const int lane = threadIdx.x & 63;
-    wv = wave;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = 64 * (4 * i + wave) + lane;
-      const int tr = q / G::CPR, pc = q % G::CPR;
-      const int c = pc ^ swz<G::RB>(tr);
-      if (KCONTIG) voff[i] = (int)((((int64_t)(row0 + tr)) * ld + c * G::EPC) * (int64_t)sizeof(T));
-      else         voff[i] = (int)((((int64_t)tr) * ld + row0 + c * G::EPC) * (int64_t)sizeof(T));
-    }
-    kadv = KCONTIG ? 128 : (int)(G::BK * ld * (int64_t)sizeof(T));
-    delta = KCONTIG ? (int)(128 * ld * (int64_t)sizeof(T)) : (int)(128 * sizeof(T));
-  }
-  // The K advance and the +128-row delta are wave-uniform, but they go into the VECTOR offset: the descriptor's range
-  // check (num_records = valid_bytes, which is what turns the rows past M of a ragged last tile into zeros instead of reads
-  // past the operand) covers vgpr offset + instruction offset only -- the SGPR `soffset` operand is added AFTER the check
-  // (tools/probe_soffset.hip; the round-1 fault of tools/probe_fill.hip was exactly an soffset beyond num_records).
-  IMT_DEVICE void issue(char* tiles, int t) const {
-    const int wave = __builtin_amdgcn_readfirstlane(wv);
-    const int adv = __builtin_amdgcn_readfirstlane(t * kadv), d = __builtin_amdgcn_readfirstlane(delta);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(tiles + h * TILE_BYTES + (4 * i + wave) * 1024),
-                                                 16, voff[i] + (adv + h * d), 0, 0, 0);
-  }
-};
 
 // Epilogue of a FULL 256 x 256 tile straight from the accumulators: lane (lr, lg) owns 4 consecutive n of row 16i + lr in
 // each of its wave's 8 x 4 MFMA tiles, so bias / aux / C accesses are 8-byte (bf16) vectors, 32 B contiguous per row and
@@ -1067,37 +1021,6 @@ IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], int mw, int nw, int
   }
 }
 
-template <typename T, int LAYOUT, int HALF = -1>
-IMT_DEVICE void compute_tile_xl(f32x4 (&acc)[8][4], const char* ta, const char* tb, int wn) {
-  constexpr bool A_KC = (LAYOUT != IMT_TN), B_KC = (LAYOUT == IMT_NT);
-  typedef TileGeom<T, A_KC> GA;
-  typedef TileGeom<T, B_KC> GB;
-  typedef typename Frag<T>::type frag_t;
-  constexpr int KSTEP = Frag<T>::KSTEP;
-  constexpr int NSTEP = GA::BK / KSTEP;  // HALF = 0 / 1: the first / second half of the tile's K steps only
-  constexpr int S0 = HALF == 1 ? NSTEP / 2 : 0, S1 = HALF == 0 ? NSTEP / 2 : NSTEP;
-#pragma unroll
-  for (int s = S0; s < S1; ++s) {
-    frag_t fa[8], fb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (B_KC) fb[j] = lds_frag_kcontig<T, GB::RB>(tb, wn + 16 * j, 4 * s);
-      else      fb[j] = KStrided<T, GB::RB>::load(tb, s * KSTEP, wn + 16 * j);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (A_KC) fa[i] = lds_frag_kcontig<T, GA::RB>(ta, 16 * i, 4 * s);
-      else      fa[i] = KStrided<T, GA::RB>::load(ta, s * KSTEP, 16 * i);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mma16(acc[i][j], fb[j], fa[i]);
-    // keep the next K step's 12 fragment reads below this step's MFMAs: hoisted, they push the 128 accumulator
-    // registers + 2 x 48 fragment registers past the 256 a wave gets at two waves per SIMD (spills in the loop)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
 template <typename T, int LAYOUT>
 __global__ __launch_bounds__(XL_THREADS) void gemm_xl_kernel(const T* __restrict__ A, int64_t lda, int64_t a_bytes,

@@ -330,6 +330,82 @@ def log_softmax_fwd(logits):
     return lp, lse
 
 
+_SCORE_WS = {}
+SCORE_CHUNK_ROWS = 2048  # rows per [rows, V] fp32 block where the fused scorer does not take the shape
+
+
+def score_workspace(device, nbytes):
+    """One scratch per device for imt_score_rows, grown on demand (stream-ordered use: one call at a time)."""
+    key = (device.type, device.index)
+    ws = _SCORE_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+        _SCORE_WS[key] = ws
+    return ws
+
+
+def score_rows(x, weight, bias, targets, seg_offsets=None, normalize=True):
+    """Log-probability of ``targets[r]`` under softmax(x[r] W^T + b) for every row, without the [N, V] logits
+    (include/imt_hip.h: imt_score_rows; src/score_pairs.py:116-127).  x [N, K], weight [V, K], bias [V] or None in one
+    dtype (fp32 / bf16); targets int64 [N], a target outside [0, V) marks the row as ignored (log-prob 0, not counted).
+    seg_offsets int64 [n_seg + 1]: rows [off[s], off[s + 1]) are sentence s.  Returns (logprob [N], lse [N], seg_score
+    [n_seg] or None), all fp32.  Where ``imt_score_supported`` says no, the same numbers come from the existing kernels
+    (fp32 logits, log-softmax, gather) in blocks of at most SCORE_CHUNK_ROWS rows, so memory stays bounded there too."""
+    _req_cuda(x, weight, bias, targets, seg_offsets)
+    N, K = x.shape
+    V = weight.shape[0]
+    assert weight.shape[1] == K and weight.dtype == x.dtype and (bias is None or bias.dtype == x.dtype)
+    assert targets.dtype == torch.int64 and targets.numel() == N
+    dev = x.device
+    n_seg = 0 if seg_offsets is None else seg_offsets.numel() - 1
+    logprob = torch.empty(N, device=dev, dtype=torch.float32)
+    lse = torch.empty(N, device=dev, dtype=torch.float32)
+    seg = torch.zeros(max(n_seg, 0), device=dev, dtype=torch.float32) if seg_offsets is not None else None
+    if N == 0:
+        return logprob, lse, seg
+    x, weight, targets = rows16(x), rows16(weight), targets.contiguous()
+    if bias is not None and (bias.data_ptr() % 16 or bias.stride(0) != 1):
+        bias = bias.clone()
+    lib = L.load()
+    if lib.imt_score_supported(dt(x), V, K):
+        if seg_offsets is not None:
+            assert seg_offsets.dtype == torch.int64 and n_seg >= 1
+            seg_offsets = seg_offsets.contiguous()
+        nbytes = int(lib.imt_score_ws_bytes(N, V))
+        ws = score_workspace(dev, nbytes)
+        a = L.ScoreArgs()
+        a.dtype, a.N, a.V, a.K = dt(x), N, V, K
+        a.x, a.ldx = x.data_ptr(), _rowmajor(x) if N > 1 else max(K, x.stride(0))
+        a.w, a.ldw = weight.data_ptr(), _rowmajor(weight) if V > 1 else max(K, weight.stride(0))
+        a.bias = bias.data_ptr() if bias is not None else None
+        a.target, a.logprob, a.lse = targets.data_ptr(), logprob.data_ptr(), lse.data_ptr()
+        if seg_offsets is not None:
+            a.seg_offsets, a.n_seg, a.seg_score = seg_offsets.data_ptr(), n_seg, seg.data_ptr()
+        a.normalize = int(bool(normalize))
+        a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+        L.check(lib.imt_score_rows(ctypes.byref(a), _stream()), "imt_score_rows")
+        return logprob, lse, seg
+    valid = (targets >= 0) & (targets < V)
+    safe = torch.where(valid, targets, torch.zeros_like(targets))
+    for r0 in range(0, N, SCORE_CHUNK_ROWS):
+        r1 = min(N, r0 + SCORE_CHUNK_ROWS)
+        logits = gemm(x[r0:r1], weight, IMT_NT, bias=bias, out_dtype=torch.float32)
+        lp, l = log_softmax_fwd(logits)
+        logprob[r0:r1] = lp.gather(1, safe[r0:r1].unsqueeze(1)).squeeze(1)
+        lse[r0:r1] = l
+    logprob.masked_fill_(~valid, 0.0)
+    if seg_offsets is not None:
+        off = seg_offsets.clamp(0, N)
+        csum = torch.cat([logprob.new_zeros(1, dtype=torch.float64), logprob.double().cumsum(0)])
+        ccnt = torch.cat([off.new_zeros(1), valid.long().cumsum(0)])
+        tot = (csum[off[1:]] - csum[off[:-1]])
+        cnt = (ccnt[off[1:]] - ccnt[off[:-1]])
+        if normalize:
+            tot = torch.where(cnt > 0, tot / cnt.clamp(min=1).double(), tot)
+        seg = tot.float()
+    return logprob, lse, seg
+
+
 def log_softmax_bwd(dlp, lp, out_dtype):
     _req_cuda(dlp, lp)
     N, V = lp.shape

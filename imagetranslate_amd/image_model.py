@@ -397,3 +397,7 @@ class ImageCaptioning(ImageMassSeq2Seq):
         rows, tgt_inputs, tgt_mask, batch_lang = self._caption_rows(batch, src_pads, tgt_inputs, tgt_langs, tgt_mask,
                                                                     pad_idx, tgt_positions, proposals)
         return self._loss_from_rows(rows, tgt_inputs, tgt_mask, batch_lang, epsilon)
+
+    def score(self, *args, **kwargs):
+        raise NotImplementedError("ImageCaptioning.score: image-conditioned scoring is not implemented (score text pairs "
+                                  "with Seq2Seq / ImageMassSeq2Seq)")

@@ -423,6 +423,52 @@ class Seq2Seq(nn.Module):
                                   int(self.text_processor.pad_token_id()))
         return loss, int(targets.numel())
 
+    @torch.no_grad()
+    def score(self, src_inputs, tgt_inputs, src_mask, tgt_mask, src_langs, tgt_langs, normalize: bool = True,
+              encoder_states=None, src_index=None, return_token_logprobs: bool = False):
+        """Log-likelihood of given targets (src/score_pairs.py:116-127): per target sentence the sum over its non-pad
+        positions 1..T-1 of log p(tgt[t] | tgt[<t], src), divided by their count when ``normalize``; fp32 ``[B]`` on the
+        device.  A sentence with no such position scores 0.  The teacher-forced decoder runs on the non-pad rows only and
+        the vocabulary projection, log-softmax and gather are one fused kernel (``hip_ops.score_rows``): no ``[rows, V]``
+        matrix exists.  ``encoder_states`` (from ``encode``; ``src_inputs`` / ``src_langs`` are then unused and ``src_mask``
+        is the mask of those states) and ``src_index`` (``[B]`` long: the encoded source each target belongs to) let a
+        caller encode every source once and score many candidates against it.  ``return_token_logprobs``: also the
+        ``[rows]`` log-probs of the non-pad positions in (sentence, position) order and the ``[B + 1]`` row offsets."""
+        if self.use_proposals:
+            raise NotImplementedError("score() does not support lexical proposals")
+        device = self.encoder.embeddings.word_embeddings.weight.device
+        batch_lang = int(tgt_langs[0])
+        tgt_langs_t = self._lang_grid(tgt_langs, tgt_inputs.size(-1), device)
+        tgt_inputs, tgt_mask, src_mask = tgt_inputs.to(device), tgt_mask.to(device), src_mask.to(device)
+        sel_idx, targets = self._selection(tgt_inputs, tgt_mask)
+        if encoder_states is None:
+            src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
+            encoder_states = self.encode(src_inputs.to(device), src_mask, src_langs_t)[0]
+        if src_index is not None:
+            src_index = src_index.to(device)
+            encoder_states = encoder_states.index_select(0, src_index)
+            src_mask = src_mask.index_select(0, src_index)
+        if encoder_states.size(0) != tgt_inputs.size(0):
+            raise ValueError("score: %d encoded sources for %d targets (pass src_index)" % (encoder_states.size(0), tgt_inputs.size(0)))
+        counts = tgt_mask[:, 1:].sum(1, dtype=torch.int64)
+        offsets = torch.zeros(tgt_inputs.size(0) + 1, dtype=torch.int64, device=device)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        if targets.numel() == 0:
+            scores = torch.zeros(tgt_inputs.size(0), dtype=torch.float32, device=device)
+            return (scores, scores.new_zeros(0), offsets) if return_token_logprobs else scores
+        rows = self._decode(encoder_states, src_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang,
+                            pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
+        # the projection operands in the compute dtype, straight from the flat store (as _LinearFn takes them)
+        output_layer = self.output_layer if (not self.lang_dec) and self.tie_embed else self.output_layer[batch_lang]
+        weight, bias = output_layer.layer.weight, output_layer.layer.bias
+        store = store_of(output_layer).ensure()
+        flat = store.params_for(rows.dtype)
+        V, K = weight.shape
+        wo, bo = store.offset(weight), store.offset(bias)
+        logprob, _, scores = O.score_rows(rows.contiguous(), flat[wo:wo + V * K].view(V, K), flat[bo:bo + V], targets.contiguous(),
+                                          seg_offsets=offsets, normalize=normalize)
+        return (scores, logprob, offsets) if return_token_logprobs else scores
+
     def state_dict(self, *args, **kwargs):
         st = self.__dict__.get("_imt_flat_store")
         if st is not None:

@@ -47,7 +47,7 @@ const char* imt_last_error(void);
  * launches (2*M*N*K per GEMM; minimal operand traffic for the HBM-bound kernels).  Off by default. */
 /* sizeof() of the argument structures below as THIS library was compiled, by name ("imt_gemm_args", "imt_attn_args",
  * "imt_prof_row", "imt_attn_block", "imt_layer_desc", "imt_stack_desc", "imt_stack_io", "imt_attn_decode_args",
- * "imt_decode_io", "imt_beam_args", "imt_mass_args"); -1 for an unknown name.  A binding checks its own layout against it
+ * "imt_decode_io", "imt_beam_args", "imt_mass_args", "imt_score_args"); -1 for an unknown name.  A binding checks its own layout against it
  * once at load time (imagetranslate_amd/_lib.py does): a stale binding then fails loudly instead of passing shifted fields. */
 int imt_abi_sizeof(const char* struct_name);
 
@@ -283,6 +283,42 @@ int imt_smoothed_nll_bwd(const float* dloss, const int64_t* target, float* dlp, 
                          float epsilon, int64_t ignore_index, void* stream);
 int imt_xent_fused_fwd_bwd(int dtype, void* logits, int64_t ld, const int64_t* target, float* loss_rows, int N,
                            int V, float epsilon, int64_t ignore_index, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------ scoring of given targets (src/score_pairs.py:116-127)
+ * The reference scores a translation candidate with the teacher-forced decoder: output layer (BertOutputLayer.layer,
+ * src/bert_seq2seq.py:6-12), F.log_softmax, gather of the target ids, per-sentence sum / mean.  imt_score_rows does the
+ * tail of that in two launches and never stores the [N, V] logits:
+ *   logit[r, v] = sum_k x[r, k] w[v, k] + bias[v]          (fp32 accumulate; never rounded to T)
+ *   lse[r]      = log sum_v exp(logit[r, v])
+ *   logprob[r]  = logit[r, target[r]] - lse[r]             (0 where target[r] is outside [0, V): the row is ignored)
+ *   seg_score[s] = sum of logprob over rows [seg_offsets[s], seg_offsets[s+1]), divided by the number of non-ignored rows of
+ *                  the segment when normalize != 0 (a segment with none scores 0).
+ * Launch 1 (profiling kind score_xl_bf16 / score_xl_f32) is imt_gemm's 256 x 256-tile NT main loop with an epilogue that
+ * reduces each tile to one (max, sum exp) pair per row and picks out the target's logit; launch 2 (score_combine) merges
+ * the column tiles of a row in tile order and sums the rows of a segment in a fixed order.  No atomics: two calls on the
+ * same input give the same bits.  ws: caller-owned scratch of imt_score_ws_bytes(N, V) bytes = the [N] target logits
+ * (rounded up to 256 bytes) + ceil(V / 256) x N float2 partials; contents are undefined afterwards.
+ * imt_score_supported: 1 where the fused kernel takes (dtype, V, K): K a whole number of 128-byte K tiles (64 bf16 / 32
+ * fp32 elements) and a weight below 2 GiB.  imt_score_rows returns IMT_ERR_BAD_ARG before any launch otherwise, and on a bad
+ * dtype, null x / w / target / logprob, N, V, K <= 0 or a workspace that is too small.  ldx / ldw in elements, rows 16-byte
+ * aligned. */
+typedef struct imt_score_args {
+  int32_t dtype;                 /* IMT_F32 / IMT_BF16: type of x, w, bias */
+  int32_t N, V, K;               /* rows, vocabulary, hidden size */
+  const void* x; int64_t ldx;    /* [N, K] decoder output rows */
+  const void* w; int64_t ldw;    /* [V, K] BertOutputLayer.layer.weight */
+  const void* bias;              /* [V], nullable */
+  const int64_t* target;         /* [N]; a target outside [0, V) marks the row as ignored */
+  float* logprob;                /* [N] out: logit[target] - lse; 0 for ignored rows */
+  float* lse;                    /* [N] out, nullable */
+  const int64_t* seg_offsets;    /* [n_seg + 1] device, nullable: rows [off[s], off[s+1]) form sentence s */
+  int32_t n_seg, normalize;      /* normalize != 0: divide by the number of non-ignored rows of the segment */
+  float* seg_score;              /* [n_seg] out (with seg_offsets) */
+  void* ws; int64_t ws_bytes;    /* caller-owned workspace, >= imt_score_ws_bytes(N, V) */
+} imt_score_args;
+int64_t imt_score_ws_bytes(int N, int V);
+int imt_score_supported(int dtype, int V, int K);
+int imt_score_rows(const imt_score_args* a, void* stream);
 /* out[0] = scale * sum(x[0..n)), fixed summation order: the `.mean()` of the per-row losses (train_image_mt.py:282). */
 int imt_scaled_sum(const float* x, int n, float scale, float* out, void* stream);
 
