@@ -8,19 +8,24 @@
 // (mfma(Bfrag, Afrag)) so each lane owns 4 consecutive n of one m: bias / residual / aux accesses and the C
 // store are 8- or 16-byte vectors.
 //
-// Five main loops share the tile product (compute_tile) and the LDS-restaged epilogue; imt_gemm picks one per shape
-// from measurements (profiles/r01_v5_gemm_shapes.txt, profiles/r01_gemm_epilogue_study.txt):
+// Six main loops share the tile product (compute_tile) and the LDS-restaged epilogue.  imt_gemm (host side, at the end of the
+// file) validates, then picks a strategy -- ragged-K tail + whole-tile body, split-K slabs on the persistent kernel (splitk_ws) or
+// on the 256-tile kernel (IMT_AUX_SPLITK_WS), else one launch whose loop choose_variant picks from measurements
+// (profiles/r01_v5_gemm_shapes.txt, profiles/r01_gemm_epilogue_study.txt, profiles/r01_gemm_xl_study.txt):
 //   gemm_ws_kernel         : persistent, wave-specialised -- 4 MFMA waves + 4 LDS-DMA producer waves (buffer_load ... lds,
 //                            16 B/lane, swizzle on the SOURCE address, 3-stage ring, one raw s_barrier per K tile, counted
 //                            vmcnt on the producers); on a workgroup's last tile the idle producers share the epilogue.
-//                            K a whole number of tiles and (<= one tile per CU or K >= 1024).
-//   gemm_grouped_tn_kernel : the same split for ALL weight-gradient products of a layer in one launch (full K per tile,
-//                            fp32 accumulate, fused bias gradients).
+//                            At least two whole K tiles (TN: any K) and (<= one tile per CU or K >= 1024 or TN).
+//   gemm_xl_kernel         : 256 x 256 tiles, 8 waves that all multiply and share the LDS-DMA of the next K tile: K < 1024 with
+//                            >= 512 such tiles (>= 224 with a GELU / GELU' / residual epilogue), the TN product with 224..256
+//                            tiles and K >= 2048, and the IMT_AUX_SPLITK_WS slabs.
+//   gemm_grouped_tn_kernel : the wave-specialised split for ALL weight-gradient products of a layer in one launch (full K per
+//                            tile, fp32 accumulate, fused bias gradients): imt_gemm_grouped_tn.
 //   gemm_sb_kernel         : one 32-KiB LDS buffer + register prefetch, three workgroups per CU overlap each other's
-//                            barriers and epilogues: many short-K tiles.
-//   gemm_kernel            : register-staged double buffer with predicated (zero-filling) loads: ragged / tiny K, split-K.
-//   gemm_pipe_kernel       : LDS-DMA ring issued by the MFMA waves themselves (superseded by gemm_ws_kernel; kept as a
-//                            cross-check variant for the tests).
+//                            barriers and epilogues: many short-K tiles, and whatever the LDS-DMA loops cannot run (NT / NN).
+//   gemm_kernel            : register-staged double buffer with predicated (zero-filling) loads: what gemm_sb_kernel takes, for TN.
+//   gemm_pipe_kernel       : LDS-DMA ring (3 or 4 stages) issued by the MFMA waves themselves (superseded by gemm_ws_kernel;
+//                            only by force_general, as a cross-check variant for the tests).
 #include <stdlib.h>
 #include "mma.hpp"
 #include "gemm_xl.hpp"
@@ -1319,86 +1324,92 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
 
 // ------------------------------------------------------------------------------------------------ host side
 int64_t view_bytes(int rows, int64_t ld, int inner, int es) { return rows > 0 ? ((int64_t)(rows - 1) * ld + inner) * es : 0; }
+template <typename K> bool allow_lds(K kernel, int bytes) {  // opt in to that much dynamic LDS; `static const bool once = allow_lds(...)`
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return true;
+}
+
+// The six main loops, numbered as in imt_gemm_args.force_general (include/imt_hip.h): V_DBUF gemm_kernel, V_DMA3 / V_DMA4 gemm_pipe_kernel
+// with a 3- / 4-stage ring, V_SBUF gemm_sb_kernel, V_WS gemm_ws_kernel, V_XL gemm_xl_kernel
+enum Variant { V_DBUF = 1, V_DMA3 = 2, V_SBUF = 3, V_DMA4 = 4, V_WS = 5, V_XL = 6 };
+// profiler kind == one kernel symbol: gemm_<variant>_<dtype>_<layout>, so that rocprofv3's per-symbol averages can be compared
+// one to one (both rings of gemm_pipe_kernel report as "dma").  Indexed [variant - 1][bf16][layout].
+const char* const VARIANT_KINDS[6][2][3] = {
+    {{"gemm_dbuf_f32_nt", "gemm_dbuf_f32_nn", "gemm_dbuf_f32_tn"}, {"gemm_dbuf_bf16_nt", "gemm_dbuf_bf16_nn", "gemm_dbuf_bf16_tn"}},
+    {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
+    {{"gemm_sbuf_f32_nt", "gemm_sbuf_f32_nn", "gemm_sbuf_f32_tn"}, {"gemm_sbuf_bf16_nt", "gemm_sbuf_bf16_nn", "gemm_sbuf_bf16_tn"}},
+    {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
+    {{"gemm_ws_f32_nt", "gemm_ws_f32_nn", "gemm_ws_f32_tn"}, {"gemm_ws_bf16_nt", "gemm_ws_bf16_nn", "gemm_ws_bf16_tn"}},
+    {{"gemm_xl_f32_nt", "gemm_xl_f32_nn", "gemm_xl_f32_tn"}, {"gemm_xl_bf16_nt", "gemm_xl_bf16_nn", "gemm_xl_bf16_tn"}}};
+
+// What the policy and launch<> need to know about one product, computed once per imt_gemm_args.
+struct GemmFacts {
+  int es, bk, al;            // bytes per element; K elements per tile (128 bytes); elements per 16-byte chunk
+  bool pipe_ok;              // the LDS-DMA kernels (V_DMA3 / V_DMA4 / V_WS / V_XL) can run it
+  int64_t tiles, tiles256;   // output tiles of 128 x 128 and of 256 x 256
+  int64_t a_bytes, b_bytes;  // extent of the A and B views (the range of their buffer descriptors)
+};
+GemmFacts gemm_facts(const imt_gemm_args* a) {
+  const bool bf16 = a->dtype == IMT_BF16, tn = a->layout == IMT_TN, nt = a->layout == IMT_NT;
+  const int a_rows = tn ? a->K : a->M, b_rows = nt ? a->N : a->K;
+  GemmFacts f;
+  f.es = bf16 ? 2 : 4; f.bk = bf16 ? 64 : 32; f.al = bf16 ? 8 : 4;
+  // LDS-DMA pipeline: whole K tiles only (no zero-fill needed anywhere), at least two of them, 32-bit buffer offsets
+  // (TN: K-strided operands, a ragged last K tile is zero-filled by the descriptors' range check -- any K)
+  f.pipe_ok = (a->K % f.bk == 0 || tn) && (a->K / f.bk >= 2) && ((int64_t)a_rows * a->lda * f.es < (1ll << 31)) &&
+              ((int64_t)b_rows * a->ldb * f.es < (1ll << 31));
+  f.tiles = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN); f.tiles256 = (int64_t)imt_cdiv(a->M, 256) * imt_cdiv(a->N, 256);
+  f.a_bytes = view_bytes(a_rows, a->lda, tn ? a->M : a->K, f.es); f.b_bytes = view_bytes(b_rows, a->ldb, nt ? a->K : a->N, f.es);
+  return f;
+}
 
 template <typename T, int LAYOUT>
-int launch(const imt_gemm_args* a, const EpiParams& ep, int splits, int k_per_split, int variant, hipStream_t st) {
-  const int nbx = imt_cdiv(a->N, BN), nby = imt_cdiv(a->M, BM);
-  dim3 grid(nbx * nby, splits);
-  static bool attr_set = false;
+int launch(const imt_gemm_args* a, const GemmFacts& f, EpiParams ep, int splits, int kps, Variant variant, hipStream_t st) {
+  dim3 grid((unsigned)f.tiles, splits);
   auto kern = gemm_kernel<T, LAYOUT>;
-  auto kpipe = gemm_pipe_kernel<T, LAYOUT, 3>;
-  auto kpipe4 = gemm_pipe_kernel<T, LAYOUT, 4>;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kpipe), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kpipe4), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAGE_BYTES);
-    attr_set = true;
-  }
-  // profiler kind == one kernel symbol: gemm_<variant>_<dtype>_<layout> (variant: dbuf = gemm_kernel, dma = gemm_pipe_kernel,
-  // sbuf = gemm_sb_kernel, ws = gemm_ws_kernel) so that rocprofv3's per-symbol averages can be compared one to one
-  static const char* const kinds[7][2][3] = {
-      {{"", "", ""}, {"", "", ""}},
-      {{"gemm_dbuf_f32_nt", "gemm_dbuf_f32_nn", "gemm_dbuf_f32_tn"}, {"gemm_dbuf_bf16_nt", "gemm_dbuf_bf16_nn", "gemm_dbuf_bf16_tn"}},
-      {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
-      {{"gemm_sbuf_f32_nt", "gemm_sbuf_f32_nn", "gemm_sbuf_f32_tn"}, {"gemm_sbuf_bf16_nt", "gemm_sbuf_bf16_nn", "gemm_sbuf_bf16_tn"}},
-      {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
-      {{"gemm_ws_f32_nt", "gemm_ws_f32_nn", "gemm_ws_f32_tn"}, {"gemm_ws_bf16_nt", "gemm_ws_bf16_nn", "gemm_ws_bf16_tn"}},
-      {{"gemm_xl_f32_nt", "gemm_xl_f32_nn", "gemm_xl_f32_tn"}, {"gemm_xl_bf16_nt", "gemm_xl_bf16_nn", "gemm_xl_bf16_tn"}}};
+  auto kpipe = gemm_pipe_kernel<T, LAYOUT, 3>, kpipe4 = gemm_pipe_kernel<T, LAYOUT, 4>;
+  static const bool once = allow_lds(kern, 2 * STAGE_BYTES) && allow_lds(kpipe, 3 * STAGE_BYTES) && allow_lds(kpipe4, 4 * STAGE_BYTES);
   const double es = sizeof(T), esc = ep.c_f32 ? 4.0 : es;
-  const char* kind = kinds[variant >= 1 && variant <= 6 ? variant : 1][sizeof(T) == 2][LAYOUT];
+  const char* kind = VARIANT_KINDS[variant - 1][sizeof(T) == 2][LAYOUT];
   if (imt_prof_enabled() && getenv("IMT_PROF_SHAPES")) kind = imt_prof_intern(kind, a->M, a->N, a->K);
-  ImtProfScope prof(kind, 2.0 * a->M * a->N * a->K,
-                    ((double)a->M * a->K + (double)a->N * a->K) * es + (double)a->M * a->N * esc, st);
-  const T* A = reinterpret_cast<const T*>(a->A);
-  const T* B = reinterpret_cast<const T*>(a->B);
-  if (variant == 6) {
-    static bool xl_attr = false;
-    auto kxl = gemm_xl_kernel<T, LAYOUT>;
-    if (!xl_attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kxl), hipFuncAttributeMaxDynamicSharedMemorySize, XL_LDS); xl_attr = true; }
-    const int64_t a_bytes = (LAYOUT == IMT_TN) ? view_bytes(a->K, a->lda, a->M, sizeof(T)) : view_bytes(a->M, a->lda, a->K, sizeof(T));
-    const int64_t b_bytes = (LAYOUT == IMT_NT) ? view_bytes(a->N, a->ldb, a->K, sizeof(T)) : view_bytes(a->K, a->ldb, a->N, sizeof(T));
-    const int nwg = imt_cdiv(a->M, 256) * imt_cdiv(a->N, 256);
-    ImtTrace tr("gemm_xl", splits == 1 ? nwg : 0, st);  // IMT_TRACE=gemm_xl: phases = first K tile landed | K loop | epilogue
-    EpiParams ept = ep;
-    ept.trace = tr.dev;
-    hipLaunchKernelGGL(kxl, dim3(nwg, splits), dim3(XL_THREADS), XL_LDS, st, A, a->lda, a_bytes, B, a->ldb, b_bytes, a->M, a->N, a->K, ept);
-    if (tr.dev) fprintf(stderr, "[gemm_xl %s %dx%dx%d]\n", kind, a->M, a->N, a->K);
-  } else if (variant == 5) {
-    static bool ws_attr = false;
-    auto kws = gemm_ws_kernel<T, LAYOUT>;
-    if (!ws_attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kws), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS); ws_attr = true; }
-    const int64_t a_bytes = (LAYOUT == IMT_TN) ? view_bytes(a->K, a->lda, a->M, sizeof(T)) : view_bytes(a->M, a->lda, a->K, sizeof(T));
-    const int64_t b_bytes = (LAYOUT == IMT_NT) ? view_bytes(a->N, a->ldb, a->K, sizeof(T)) : view_bytes(a->K, a->ldb, a->N, sizeof(T));
-    const int tiles = nbx * nby * (ep.splits > 1 ? ep.splits : 1);
-    ImtTrace tr("gemm_ws", tiles < 256 ? tiles : 256, st);
-    EpiParams ept = ep;
-    ept.trace = tr.dev;
-    hipLaunchKernelGGL(kws, dim3(tiles < 256 ? tiles : 256), dim3(WS_THREADS), WS_LDS, st, A, a->lda, a_bytes, B, a->ldb, b_bytes, a->M, a->N, a->K, ept);
-    if (tr.dev) fprintf(stderr, "[gemm_ws %s %dx%dx%d bias %d resid %d drop %d aux %d acc %d]\n", kind, a->M, a->N, a->K, ep.bias != nullptr, ep.resid != nullptr, ep.drop_thresh != 0, ep.aux_mode, ep.accumulate);
-  } else if (variant == 3) {
-    hipLaunchKernelGGL((gemm_sb_kernel<T, LAYOUT>), grid, dim3(NTHREADS), STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, k_per_split, ep);
-  } else if (variant == 2 || variant == 4) {
-    const int64_t a_bytes = (LAYOUT == IMT_TN) ? view_bytes(a->K, a->lda, a->M, sizeof(T)) : view_bytes(a->M, a->lda, a->K, sizeof(T));
-    const int64_t b_bytes = (LAYOUT == IMT_NT) ? view_bytes(a->N, a->ldb, a->K, sizeof(T)) : view_bytes(a->K, a->ldb, a->N, sizeof(T));
-    if (variant == 4)
-      hipLaunchKernelGGL(kpipe4, grid, dim3(NTHREADS), 4 * STAGE_BYTES, st, A, a->lda, a_bytes, B, a->ldb, b_bytes, a->M, a->N, a->K, k_per_split, ep);
-    else
-      hipLaunchKernelGGL(kpipe, grid, dim3(NTHREADS), 3 * STAGE_BYTES, st, A, a->lda, a_bytes, B, a->ldb, b_bytes, a->M, a->N, a->K, k_per_split, ep);
-  } else {
-    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, k_per_split, ep);
+  ImtProfScope prof(kind, 2.0 * a->M * a->N * a->K, ((double)a->M * a->K + (double)a->N * a->K) * es + (double)a->M * a->N * esc, st);
+  const T *A = reinterpret_cast<const T*>(a->A), *B = reinterpret_cast<const T*>(a->B);
+  switch (variant) {
+    case V_XL: {
+      auto kxl = gemm_xl_kernel<T, LAYOUT>;
+      static const bool xl_once = allow_lds(kxl, XL_LDS);
+      const int nwg = (int)f.tiles256;
+      ImtTrace tr("gemm_xl", splits == 1 ? nwg : 0, st);  // IMT_TRACE=gemm_xl: phases = first K tile landed | K loop | epilogue
+      ep.trace = tr.dev;
+      hipLaunchKernelGGL(kxl, dim3(nwg, splits), dim3(XL_THREADS), XL_LDS, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, ep);
+      if (tr.dev) fprintf(stderr, "[gemm_xl %s %dx%dx%d]\n", kind, a->M, a->N, a->K);
+      break;
+    }
+    case V_WS: {
+      auto kws = gemm_ws_kernel<T, LAYOUT>;
+      static const bool ws_once = allow_lds(kws, WS_LDS);
+      const int tiles = (int)f.tiles * (ep.splits > 1 ? ep.splits : 1);
+      ImtTrace tr("gemm_ws", tiles < 256 ? tiles : 256, st);
+      ep.trace = tr.dev;
+      hipLaunchKernelGGL(kws, dim3(tiles < 256 ? tiles : 256), dim3(WS_THREADS), WS_LDS, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, ep);
+      if (tr.dev) fprintf(stderr, "[gemm_ws %s %dx%dx%d bias %d resid %d drop %d aux %d acc %d]\n", kind, a->M, a->N, a->K, ep.bias != nullptr, ep.resid != nullptr, ep.drop_thresh != 0, ep.aux_mode, ep.accumulate);
+      break;
+    }
+    case V_SBUF: hipLaunchKernelGGL((gemm_sb_kernel<T, LAYOUT>), grid, dim3(NTHREADS), STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
+    case V_DMA3: hipLaunchKernelGGL(kpipe, grid, dim3(NTHREADS), 3 * STAGE_BYTES, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, kps, ep); break;
+    case V_DMA4: hipLaunchKernelGGL(kpipe4, grid, dim3(NTHREADS), 4 * STAGE_BYTES, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, kps, ep); break;
+    case V_DBUF: hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
   }
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }
 
-template <typename T> int dispatch(const imt_gemm_args* a, const EpiParams& ep, int splits, int kps, int variant, hipStream_t st) {
-  switch (a->layout) {
-    case IMT_NT: return launch<T, IMT_NT>(a, ep, splits, kps, variant, st);
-    case IMT_NN: return launch<T, IMT_NN>(a, ep, splits, kps, variant, st);
-    case IMT_TN: return launch<T, IMT_TN>(a, ep, splits, kps, variant, st);
-  }
-  imt_set_error("imt_gemm: bad layout %d", a->layout);
-  return IMT_ERR_BAD_ARG;
+// one launch of `variant` as it is: the caller has made sure that the variant can run the product
+int dispatch(const imt_gemm_args* a, const GemmFacts& f, const EpiParams& ep, int splits, int kps, Variant variant, hipStream_t st) {
+  static constexpr decltype(&launch<float, IMT_NT>) by_type[2][3] = {{launch<float, IMT_NT>, launch<float, IMT_NN>, launch<float, IMT_TN>},
+                                                                    {launch<bf16_t, IMT_NT>, launch<bf16_t, IMT_NN>, launch<bf16_t, IMT_TN>}};
+  IMT_CHECK_ARG(a->layout >= IMT_NT && a->layout <= IMT_TN, "imt_gemm: bad layout %d", a->layout);
+  return by_type[a->dtype == IMT_BF16][a->layout](a, f, ep, splits, kps, variant, st);
 }
 
 // C[m][n] = (accumulate ? C[m][n] : 0) + sum_s slab[s][m][n]      (split-K slab mode of the 256-tile kernel)
@@ -1535,14 +1546,75 @@ int launch_splitk_epilogue_ln(const float* slabs, int64_t slab_elems, int S, int
   return IMT_OK;
 }
 
+// Every environment switch this file reads, parsed once on first use (IMT_PROF_SHAPES alone is read per launch, in launch<>).
+// All but IMT_GEMM_SHARE_CUS are tuning / test aids; the defaults are the measured choices.
+struct GemmSwitches {
+  int dbg;                   // IMT_GEMM_DBG=<bits> (atoi): or-ed into EpiParams.dbg of every single launch
+  bool no_xl;                // IMT_GEMM_NO_XL (presence): never choose the 256-tile kernel
+  bool no_xl_gelu;           // IMT_GEMM_NO_XL_GELU (presence): a GELU-forward epilogue alone does not choose it
+  bool no_xl_tn;             // IMT_GEMM_NO_XL_TN (presence): weight gradients do not choose it
+  bool no_ln_ticket;         // IMT_GEMM_LN_TICKET=0 (atoi): an IMT_LN_TICKET build takes the LayerNorm launch all the same
+  bool no_small_splitk;      // IMT_GEMM_NO_SMALL_SPLITK (presence): imt_gemm_args.splitk_ws is never used
+  int splitk_ln_min_nt;      // IMT_GEMM_SPLITK_LN_MIN_NT=<K tiles> (atoi, default 8): shortest K split when the epilogue launch normalises
+  int share_cus;             // IMT_GEMM_SHARE_CUS (atoi, an empty string means 1): overrides imt_set_gemm_share_cus; -1 when unset
+  bool grouped_plain_order;  // IMT_GROUPED_PLAIN_ORDER (presence): grouped weight gradients in plain workgroup order
+};
+const GemmSwitches& gemm_switches() {
+  static const auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+  static const auto has = [](const char* name) { return getenv(name) != nullptr; };
+  static const auto share = [] { const char* v = getenv("IMT_GEMM_SHARE_CUS"); return !v ? -1 : (atoi(v) != 0 || v[0] == '\0') ? 1 : 0; };
+  static const GemmSwitches sw = {num("IMT_GEMM_DBG", 0), has("IMT_GEMM_NO_XL"), has("IMT_GEMM_NO_XL_GELU"), has("IMT_GEMM_NO_XL_TN"),
+                                  num("IMT_GEMM_LN_TICKET", 1) == 0, has("IMT_GEMM_NO_SMALL_SPLITK"), num("IMT_GEMM_SPLITK_LN_MIN_NT", 8),
+                                  share(), has("IMT_GROUPED_PLAIN_ORDER")};  // (in the order of the fields)
+  return sw;
+}
+
+int g_share_cus = 0;  // imt_set_gemm_share_cus
+// The epilogue that `a` asks for, as the kernels take it; every field not named here is zero.  Launches that differ
+// (atomic split-K, dbg, LayerNorm in the launch) override those fields.
+EpiParams epi_params(const imt_gemm_args* a) {
+  EpiParams ep{};
+  ep.C = a->C; ep.ldc = a->ldc; ep.c_f32 = (a->c_dtype == IMT_F32); ep.accumulate = a->accumulate;
+  ep.bias = a->bias; ep.resid = a->resid; ep.ldr = a->ldr; ep.aux = a->aux; ep.ldaux = a->ldaux; ep.aux_mode = a->aux_mode;
+  ep.alpha = a->alpha; ep.alpha_dev = a->alpha_dev; ep.a_colsum = a->a_colsum;
+  ep.drop_thresh = dropout_thresh(a->dropout_p); ep.inv_keep = a->dropout_p > 0.f ? 1.0f / (1.0f - a->dropout_p) : 1.0f; ep.seed = a->dropout_seed;
+  return ep;
+}
+// The main loop of a split-K slab launch: the raw partial products of K range s into fp32 slab s of `slabs` ([M][N], ld N),
+// no epilogue (that is the reduce / epilogue launch's).
+EpiParams slab_params(void* slabs, const imt_gemm_args* a) {
+  EpiParams ep{};
+  ep.C = slabs; ep.ldc = a->N; ep.c_f32 = 1; ep.alpha = 1.0f; ep.inv_keep = 1.0f; ep.slab_elems = (int64_t)a->M * a->N;
+  return ep;
+}
+void epi_set_ln(EpiParams& ep, const imt_gemm_args* a, int* tickets) {
+  ep.ln_gamma = a->ln_gamma; ep.ln_beta = a->ln_beta; ep.ln_out = a->ln_out; ep.ld_ln = a->ld_ln;
+  ep.ln_mean = a->ln_mean; ep.ln_rstd = a->ln_rstd; ep.ln_tickets = tickets; ep.ln_eps = a->ln_eps;
+}
+
+// ln_out's preconditions, checked by each strategy before its first launch (the wording differs by strategy; callers match on
+// it).  need_contiguous: the LayerNorm is a launch of its own, which reads C and writes ln_out as contiguous rows.
+enum LnSite { LN_RAGGED_K, LN_SPLITK_WS, LN_SINGLE };
+int check_ln_out(const imt_gemm_args* a, LnSite site, int splits, bool need_contiguous) {
+  static const char* const needs[3] = {"needs C of the compute type, no accumulate", "needs contiguous C of the compute type",
+                                       "needs C of the compute type, no split-K, no accumulate"};
+  if (!a->ln_out) return IMT_OK;
+  IMT_CHECK_ARG(a->ln_gamma && a->ln_beta, "imt_gemm: ln_out needs ln_gamma and ln_beta");
+  IMT_CHECK_ARG(a->c_dtype == a->dtype && splits == 1 && !a->accumulate, "imt_gemm: ln_out %s", needs[site]);
+  IMT_CHECK_ARG(!need_contiguous || (a->ldc == a->N && a->ld_ln == a->N), "imt_gemm: ln_out %s",
+                site == LN_SPLITK_WS ? needs[site] : "behind a GEMM that cannot normalise in-launch needs contiguous C and ln_out");
+  return IMT_OK;
+}
+int layernorm_behind(const imt_gemm_args* a, void* stream) {
+  return imt_layernorm_fwd(a->dtype, a->C, a->ln_gamma, a->ln_beta, a->ln_out, a->ln_mean, a->ln_rstd, a->M, a->N, a->ln_eps, 0.f, 0, stream);
+}
+
 // how many K ranges for a product with `tiles` output tiles of 128 x 128 and `nt` K tiles; 1 = do not split
-int splitk_choice(int64_t tiles, int nt, bool ln_fused) {
-  static const int off = getenv("IMT_GEMM_NO_SMALL_SPLITK") ? 1 : 0;  // tuning / tests
+int splitk_choice(int64_t tiles, int nt, bool ln_fused, const GemmSwitches& sw) {
   // with the LayerNorm in the epilogue launch the split costs no extra launch (it replaces the LayerNorm's), so a
   // shorter K pays already when the product has only a handful of tiles (decoding: 320 rows)
-  static const int ln_min_nt = getenv("IMT_GEMM_SPLITK_LN_MIN_NT") ? atoi(getenv("IMT_GEMM_SPLITK_LN_MIN_NT")) : 8;
-  const bool short_ok = ln_fused && tiles <= 32 && nt >= ln_min_nt;
-  if (off || tiles > 128 || (nt < 16 && !short_ok)) return 1;
+  const bool short_ok = ln_fused && tiles <= 32 && nt >= sw.splitk_ln_min_nt;
+  if (sw.no_small_splitk || tiles > 128 || (nt < 16 && !short_ok)) return 1;
   int s = (int)(256 / tiles);
   if (s > 8) s = 8;
   const int per_min = (nt < 16) ? 2 : 4;  // K tiles per range: below that the ramp of a range costs more than it saves
@@ -1552,44 +1624,51 @@ int splitk_choice(int64_t tiles, int nt, bool ln_fused) {
   return (nt + per - 1) / per;  // every range non-empty
 }
 
-}  // namespace
+// ---- strategy: ragged K.  Long K that is not a whole number of tiles (the vocabulary dimension: dX = dlogits[.,30000] W): the LDS-DMA
+// kernels need whole K tiles, so the ragged tail goes first as its own small product and the whole-tile body is accumulated on top by the
+// persistent kernel (477 -> ~700 TFLOP/s on 8128x512x30000).  Only for epilogues that are linear in the product (bias / residual ride on the tail call).
+imt_gemm_args ragged_k_tail(imt_gemm_args t, const GemmFacts& f) {  // NT / NN (A is [M][K]): the product over the K elements behind the last whole tile
+  const int kb = (t.K / f.bk) * f.bk;
+  t.A = reinterpret_cast<const char*>(t.A) + (int64_t)kb * f.es;
+  t.B = reinterpret_cast<const char*>(t.B) + (t.layout == IMT_NT ? (int64_t)kb : (int64_t)kb * t.ldb) * f.es;
+  t.K -= kb;
+  return t;
+}
+int run_ragged_k(const imt_gemm_args* a, const GemmFacts& f, void* stream) {
+  imt_gemm_args tail = ragged_k_tail(*a, f), body = *a;
+  body.K = a->K - tail.K; body.accumulate = 1; body.bias = nullptr; body.resid = nullptr;
+  tail.ln_out = nullptr; body.ln_out = nullptr;  // the LayerNorm (if any) follows the complete product
+  int rc = check_ln_out(a, LN_RAGGED_K, 1, true);
+  if (rc == IMT_OK) rc = imt_gemm(&tail, stream);
+  if (rc == IMT_OK) rc = imt_gemm(&body, stream);
+  return (rc == IMT_OK && a->ln_out) ? layernorm_behind(a, stream) : rc;
+}
 
-extern "C" int64_t imt_gemm_splitk_ws_bytes(void) { return (int64_t)256 * BM * BN * 4 + 4096; }
-
-// aux_mode IMT_AUX_SPLITK_WS: a product with few output tiles and a very long K (dX through the vocabulary: 8128 x 512 x
-// 30000 has 64 tiles of 256 x 256) runs as split_k K-ranges of 256-tile workgroups, each into its own fp32 slab of the
-// caller's workspace `aux` (split_k * M * N floats), followed by one reduce launch -- no atomics, fixed summation order.
-static int gemm_splitk_slabs(const imt_gemm_args* a, void* stream) {
-  const int bk = (a->dtype == IMT_BF16) ? 64 : 32, es = (a->dtype == IMT_BF16) ? 2 : 4;
+// ---- strategy: split-K slabs on the 256-tile kernel (aux_mode IMT_AUX_SPLITK_WS).  A product with few output tiles and a very long K (dX
+// through the vocabulary: 8128 x 512 x 30000 has 64 tiles of 256 x 256) runs as split_k K-ranges of 256-tile workgroups, each into its own fp32
+// slab of the caller's workspace `aux` (split_k * M * N floats), followed by one reduce launch -- no atomics, fixed summation order.
+int run_slabs(const imt_gemm_args* a, const GemmFacts& f, void* stream) {
   IMT_CHECK_ARG(a->layout != IMT_TN && a->aux && a->split_k >= 2 && a->split_k <= 16, "imt_gemm: split-K slab mode needs NT/NN, a workspace and 2..16 splits");
-  IMT_CHECK_ARG(!a->bias && !a->resid && a->dropout_p == 0.f && !a->a_colsum && a->N % 4 == 0 && a->K >= 2 * bk * a->split_k,
+  IMT_CHECK_ARG(!a->bias && !a->resid && a->dropout_p == 0.f && !a->a_colsum && a->N % 4 == 0 && a->K >= 2 * f.bk * a->split_k,
                 "imt_gemm: split-K slab mode: plain epilogue, N %% 4 == 0, at least two K tiles per split");
-  IMT_CHECK_ARG(a->c_dtype == a->dtype || a->c_dtype == IMT_F32, "imt_gemm: c_dtype must be f32 or dtype");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  imt_gemm_args body = *a;
-  body.aux = nullptr; body.aux_mode = IMT_AUX_NONE;
-  int accumulate = a->accumulate;
-  if (a->K % bk != 0) {  // ragged tail first, as its own small product straight into C
-    const int kb = (a->K / bk) * bk;
-    imt_gemm_args tail = body;
-    tail.split_k = 1; tail.K = a->K - kb;
-    tail.A = reinterpret_cast<const char*>(a->A) + (int64_t)kb * es;                                   // NT / NN: A is [M][K]
-    tail.B = reinterpret_cast<const char*>(a->B) + (a->layout == IMT_NT ? (int64_t)kb : (int64_t)kb * a->ldb) * es;
-    const int rc = imt_gemm(&tail, stream);
-    if (rc != IMT_OK) return rc;
-    body.K = kb; accumulate = 1;
+  imt_gemm_args body = *a; body.aux = nullptr; body.aux_mode = IMT_AUX_NONE;
+  int accumulate = a->accumulate, rc = IMT_OK;
+  if (a->K % f.bk != 0) {  // ragged tail first, as its own small product straight into C
+    imt_gemm_args tail = ragged_k_tail(body, f);
+    tail.split_k = 1;
+    if ((rc = imt_gemm(&tail, stream)) != IMT_OK) return rc;
+    body.K = a->K - tail.K; accumulate = 1;
   }
-  const int64_t a_rows = body.M, b_rows = (body.layout == IMT_NT) ? body.N : body.K;
-  IMT_CHECK_ARG(a_rows * body.lda * es < (1ll << 31) && b_rows * body.ldb * es < (1ll << 31), "imt_gemm: split-K slab mode: operand too large for 32-bit offsets");
-  EpiParams ep;
-  memset(&ep, 0, sizeof(ep));
-  ep.C = a->aux; ep.ldc = body.N; ep.c_f32 = 1; ep.accumulate = 0;
-  ep.alpha = body.alpha; ep.alpha_dev = body.alpha_dev; ep.inv_keep = 1.0f;
-  ep.slab_elems = (int64_t)body.M * body.N;
-  int rc = (body.dtype == IMT_F32) ? dispatch<float>(&body, ep, body.split_k, body.K, 6, st) : dispatch<bf16_t>(&body, ep, body.split_k, body.K, 6, st);
-  if (rc != IMT_OK) return rc;
+  const GemmFacts bf = gemm_facts(&body);
+  // (K is whole tiles now, at least two per split: only the 32-bit offsets are left of pipe_ok)
+  IMT_CHECK_ARG(bf.pipe_ok, "imt_gemm: split-K slab mode: operand too large for 32-bit offsets");
+  EpiParams ep = slab_params(a->aux, &body);
+  ep.alpha = body.alpha; ep.alpha_dev = body.alpha_dev;  // the reduce launch only sums
+  ep.splits = 0;                                         // (the persistent kernel's field; the 256-tile kernel takes its K range from gridDim.y)
+  if ((rc = dispatch(&body, bf, ep, body.split_k, body.K, V_XL, st)) != IMT_OK) return rc;
   const int64_t groups = (int64_t)body.M * (body.N / 4);
-  ImtProfScope prof("gemm_splitk_reduce", 0.0, (double)body.M * body.N * (4.0 * body.split_k + 2.0 * es), st);
+  ImtProfScope prof("gemm_splitk_reduce", 0.0, (double)body.M * body.N * (4.0 * body.split_k + 2.0 * f.es), st);
   const float* slabs = reinterpret_cast<const float*>(a->aux);
   if (a->c_dtype == IMT_F32)
     hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(imt_cdiv(groups, 256)), dim3(256), 0, st, slabs, ep.slab_elems, body.split_k,
@@ -1601,34 +1680,110 @@ static int gemm_splitk_slabs(const imt_gemm_args* a, void* stream) {
   return IMT_OK;
 }
 
-// one-tile-per-CU GEMMs on the three-workgroups-per-CU kernel (data-parallel runs): imt_set_gemm_share_cus, overridden by the
-// environment variable IMT_GEMM_SHARE_CUS=0|1
-static int g_share_cus = 0;
-static bool share_cus_policy() {
-  static const char* env = getenv("IMT_GEMM_SHARE_CUS");
-  if (env) return atoi(env) != 0 || env[0] == '\0';
-  return g_share_cus != 0;
+// ---- strategy: split-K slabs on the persistent kernel (imt_gemm_args.splitk_ws).  Few output tiles, long K, a workspace for partial sums:
+// K ranges on the persistent kernel + one epilogue launch that sums the slabs and, for dense + bias + dropout + residual + LayerNorm with N <= 1024,
+// normalises its rows itself
+bool splitk_ws_ln_fused(const imt_gemm_args* a) { return a->ln_out && a->aux_mode == IMT_AUX_NONE && a->N <= 1024 && a->c_dtype != IMT_F32; }
+// the number of K ranges; 1 = the strategy does not apply
+int splitk_ws_splits(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits) {
+  if (a->force_general != 0 || !a->splitk_ws || splits != 1 || a->layout == IMT_TN || !f.pipe_ok || a->N % 4 != 0 || a->a_colsum) return 1;
+  const int S = splitk_choice(f.tiles, a->K / f.bk, splitk_ws_ln_fused(a), sw);
+  // (edge tiles store only rows < M, slabs are addressed [m][n] with ld N)
+  return ((int64_t)S * a->M * a->N * 4 <= a->splitk_ws_bytes && ((uintptr_t)a->splitk_ws & 15) == 0) ? S : 1;
 }
+int run_splitk_ws(const imt_gemm_args* a, const GemmFacts& f, int S, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int rc = check_ln_out(a, LN_SPLITK_WS, 1, true);
+  EpiParams slab = slab_params(a->splitk_ws, a); slab.splits = S;
+  if (rc == IMT_OK) rc = dispatch(a, f, slab, 1, a->K, V_WS, st);
+  if (rc != IMT_OK) return rc;
+  EpiParams ep = epi_params(a);
+  const float* slabs = reinterpret_cast<const float*>(a->splitk_ws);
+  if (splitk_ws_ln_fused(a)) {
+    epi_set_ln(ep, a, nullptr);
+    ImtProfScope prof("gemm_splitk_epilogue_ln", 0.0, (double)a->M * a->N * (4.0 * S + 3.0 * f.es), st);
+    return (a->dtype == IMT_F32) ? launch_splitk_epilogue_ln<float>(slabs, slab.slab_elems, S, a->M, a->N, ep, st)
+                                 : launch_splitk_epilogue_ln<bf16_t>(slabs, slab.slab_elems, S, a->M, a->N, ep, st);
+  }
+  {
+    const int64_t groups = (int64_t)a->M * (a->N / 4);
+    ImtProfScope prof("gemm_splitk_epilogue", 0.0, (double)a->M * a->N * (4.0 * S + 2.0 * f.es), st);
+    auto kern = (a->dtype == IMT_F32) ? splitk_epilogue_kernel<float> : splitk_epilogue_kernel<bf16_t>;
+    hipLaunchKernelGGL(kern, dim3(imt_cdiv(groups, 256)), dim3(256), 0, st, slabs, slab.slab_elems, S, a->M, a->N, ep);
+    IMT_CHECK_LAUNCH();
+  }
+  return a->ln_out ? layernorm_behind(a, stream) : IMT_OK;
+}
+
+// ---- strategy: one launch.  choose_variant: which main loop it runs (splits: atomic split-K ranges, 1 = none); no side effects, a
+// function of the product's facts, the arguments, the switches and the share-CUs knob.
+Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits, bool share_cus) {
+  const bool tn = a->layout == IMT_TN;
+  // a->force_general carries a variant code for tests / tuning (and dbg bits in its hundreds)
+  int v = a->force_general % 100;
+  if (v == 0) {
+    // measured on MI355X (profiles/r01_v3_gemm_shapes.txt): about one wave of blocks -> the LDS-DMA ring (its long
+    // steady state wins when K >= 1024, a tie otherwise); larger grids -> three single-buffer blocks per CU.
+    // measured on MI355X (profiles/r01_v5_gemm_shapes.txt): the persistent wave-specialised kernel wins whenever a CU
+    // gets about one output tile or K is long (740 vs 480 TFLOP/s at 8192x512x2048); grids of many short-K tiles are
+    // still better served by three single-buffer blocks per CU overlapping each other's epilogues.
+    // (weight gradients with many output tiles and a short K -- few tokens: captioning, decoding-sized batches -- also run
+    // best on the persistent kernel: 30000 x 512 x 992 TN 64 against 92 us on the register-staged one, tools/tn_small_k.py)
+    if (f.pipe_ok && splits == 1 && (f.tiles <= 256 || a->K >= 1024 || tn)) v = V_WS;
+    else v = tn ? V_DBUF : V_SBUF;
+    // 256 x 256 tiles (profiles/r01_gemm_xl_study.txt): several rounds of short-K tiles (vocabulary projection 797 vs 681
+    // TFLOP/s, batched cross K/V), or one round whose epilogue touches a second matrix (GELU / GELU' / residual: 500 vs 430)
+    const bool second_matrix = (a->aux_mode != IMT_AUX_NONE && !(a->aux_mode == IMT_AUX_GELU_FWD && sw.no_xl_gelu)) || a->resid;
+    if (!sw.no_xl && f.pipe_ok && splits == 1 && !tn && !a->a_colsum && a->K < 1024 && (f.tiles256 >= 512 || (f.tiles256 >= 224 && second_matrix)))
+      v = V_XL;
+    // a weight gradient with about one 256-tile per CU and a long K (the vocabulary projection's dW: 30000 x 512 x 8128)
+    if (!sw.no_xl && !sw.no_xl_tn && f.pipe_ok && splits == 1 && tn && f.tiles256 >= 224 && f.tiles256 <= 256 && a->K >= 2048) v = V_XL;
+    // data-parallel knob (off by default, DESIGN.md section 6): when a collective's kernels hold some CUs, a persistent
+    // launch of exactly one tile per CU needs a full second round; three small workgroups per CU degrade gracefully
+    if (share_cus && v == V_WS && !tn && f.tiles > 192 && f.tiles <= 256 && a->K < 1024) v = V_SBUF;
+  }
+  // what a variant cannot run goes to its nearest relative that can
+  if (v == V_XL && (!f.pipe_ok || splits > 1 || (a->a_colsum && !tn))) v = V_SBUF;
+  if ((v == V_DMA3 || v == V_DMA4) && !f.pipe_ok) v = V_DBUF;
+  if (v == V_WS && (!f.pipe_ok || splits > 1)) v = V_SBUF;
+  return v >= V_DBUF && v <= V_XL ? (Variant)v : V_DBUF;  // (any other code has always meant the register-staged kernel)
+}
+int run_single(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits, int kps, void* stream) {
+  const Variant variant = choose_variant(a, f, sw, splits, sw.share_cus >= 0 ? sw.share_cus != 0 : g_share_cus != 0);
+  EpiParams ep = epi_params(a);
+  ep.atomic = (splits > 1); ep.dbg = a->force_general / 100 | sw.dbg;
+  // LayerNorm of the finished rows: in-launch (ln_rowblock_tail) when this is a one-tile-per-workgroup launch of the
+  // persistent kernel over whole 128-column tiles; otherwise a LayerNorm launch behind the GEMM
+  const bool ln_in_launch = a->ln_out && IMT_LN_TICKET && !sw.no_ln_ticket && variant == V_WS && f.tiles <= 256 && a->N % BN == 0 && a->N <= 1024 &&
+                            a->ln_tickets != nullptr && ((int64_t)(a->M - 1) * a->ldc + a->N) * f.es < (1ll << 31);
+  if (ln_in_launch) epi_set_ln(ep, a, a->ln_tickets);
+  int rc = check_ln_out(a, LN_SINGLE, splits, !ln_in_launch);
+  if (rc == IMT_OK) rc = dispatch(a, f, ep, splits, kps, variant, reinterpret_cast<hipStream_t>(stream));
+  return (rc == IMT_OK && a->ln_out && !ln_in_launch) ? layernorm_behind(a, stream) : rc;
+}
+
+}  // namespace
+
+extern "C" int64_t imt_gemm_splitk_ws_bytes(void) { return (int64_t)256 * BM * BN * 4 + 4096; }
 bool imt_gemm_ln_ticket_enabled() { return IMT_LN_TICKET != 0; }
 extern "C" int imt_set_gemm_share_cus(int share_cus) {
   const int prev = g_share_cus;
-  g_share_cus = share_cus ? 1 : 0;
-  return prev;
+  return g_share_cus = share_cus ? 1 : 0, prev;
 }
 
+// Validate, pick a strategy, run it.
 extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
   IMT_CHECK_ARG(a != nullptr, "imt_gemm: null args");
   IMT_CHECK_ARG(a->dtype == IMT_F32 || a->dtype == IMT_BF16, "imt_gemm: bad dtype %d", a->dtype);
   IMT_CHECK_ARG(a->M >= 0 && a->N >= 0 && a->K >= 0, "imt_gemm: negative dims");
   if (a->M == 0 || a->N == 0) return IMT_OK;
   IMT_CHECK_ARG(a->A && a->B && a->C, "imt_gemm: null operand");
-  const int al = (a->dtype == IMT_BF16) ? 8 : 4;
-  const int es = (a->dtype == IMT_BF16) ? 2 : 4;
+  const GemmFacts f = gemm_facts(a);
+  const int al = f.al;  // elements per 16-byte chunk
   IMT_CHECK_ARG(a->lda % al == 0 && a->ldb % al == 0, "imt_gemm: lda/ldb must be multiples of %d (16-B rows)", al);
   IMT_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0, "imt_gemm: A/B must be 16-B aligned");
   // contiguous extents of the vector loads must be chunk multiples
-  const int a_inner = (a->layout == IMT_TN) ? a->M : a->K;
-  const int b_inner = (a->layout == IMT_NT) ? a->K : a->N;
+  const int a_inner = (a->layout == IMT_TN) ? a->M : a->K, b_inner = (a->layout == IMT_NT) ? a->K : a->N;
   // A contiguous extent that is not a whole number of 16-byte chunks (a vocabulary of 193 entries ...) is accepted when
   // the leading dimension covers the rounded-up extent (the last chunk of a row then stays inside the row's storage)
   // and what the overhang reads cannot reach the result: output rows/columns past M/N are masked by the epilogue, and
@@ -1641,171 +1796,22 @@ extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
                 "imt_gemm: contiguous extents (%d,%d) must be multiples of %d (or, for NN/TN, padded by the leading dimension)",
                 a_inner, b_inner, al);
   IMT_CHECK_ARG(a->ldc % 4 == 0, "imt_gemm: ldc must be a multiple of 4");
-  const int c_f32 = (a->c_dtype == IMT_F32);
-  IMT_CHECK_ARG(c_f32 || a->c_dtype == a->dtype, "imt_gemm: c_dtype must be f32 or dtype");
+  IMT_CHECK_ARG(a->c_dtype == IMT_F32 || a->c_dtype == a->dtype, "imt_gemm: c_dtype must be f32 or dtype");
   IMT_CHECK_ARG(!a->a_colsum || a->layout == IMT_TN, "imt_gemm: a_colsum is a TN (weight-gradient) option");
-  if (a->aux_mode == IMT_AUX_SPLITK_WS) return gemm_splitk_slabs(a, stream);
-  int splits = a->split_k > 1 ? a->split_k : 1;
-  const int bk = (a->dtype == IMT_BF16) ? 64 : 32;
-  int kps = a->K;
-  if (splits > 1) {
-    IMT_CHECK_ARG(c_f32 && !a->bias && !a->resid && a->aux_mode == IMT_AUX_NONE && a->dropout_p == 0.f,
+  if (a->aux_mode == IMT_AUX_SPLITK_WS) return run_slabs(a, f, stream);
+  int splits = a->split_k > 1 ? a->split_k : 1, kps = a->K;
+  if (splits > 1) {  // atomic split-K: K ranges of whole tiles, every range non-empty
+    IMT_CHECK_ARG(a->c_dtype == IMT_F32 && !a->bias && !a->resid && a->aux_mode == IMT_AUX_NONE && a->dropout_p == 0.f,
                   "imt_gemm: split_k supports only fp32 atomic accumulation without epilogue");
-    kps = imt_cdiv(imt_cdiv(a->K, splits), bk) * bk;
+    kps = imt_cdiv(imt_cdiv(a->K, splits), f.bk) * f.bk;
     splits = imt_cdiv(a->K, kps);
   }
   if (a->aux_mode != IMT_AUX_NONE) IMT_CHECK_ARG(a->aux != nullptr, "imt_gemm: aux_mode needs aux");
-  // LDS-DMA pipeline: whole K tiles only (no zero-fill needed anywhere), 32-bit buffer offsets
-  const int64_t a_rows = (a->layout == IMT_TN) ? a->K : a->M, b_rows = (a->layout == IMT_NT) ? a->N : a->K;
-  // (TN: K-strided operands, a ragged last K tile is zero-filled by the descriptors' range check -- any K)
-  const bool pipe_ok = (a->K % bk == 0 || a->layout == IMT_TN) && (a->K / bk >= 2) && (a_rows * a->lda * es < (1ll << 31)) &&
-                       (b_rows * a->ldb * es < (1ll << 31));
-  // Long K that is not a whole number of tiles (the vocabulary dimension: dX = dlogits[.,30000] W): the LDS-DMA
-  // kernels need whole K tiles, so the ragged tail goes first as its own small product and the whole-tile body is
-  // accumulated on top by the persistent kernel (477 -> ~700 TFLOP/s on 8128x512x30000).  Only for epilogues that are
-  // linear in the product (bias / residual ride on the tail call).
-  if (a->force_general == 0 && splits == 1 && a->layout != IMT_TN && a->K % bk != 0 && a->K / bk >= 16 && a->aux_mode == IMT_AUX_NONE &&
-      a->dropout_p == 0.f && !a->a_colsum) {
-    const int kb = (a->K / bk) * bk, kt = a->K - kb;
-    imt_gemm_args tail = *a, body = *a;
-    const int64_t a_off = (a->layout == IMT_TN) ? (int64_t)kb * a->lda : kb;
-    const int64_t b_off = (a->layout == IMT_NT) ? kb : (int64_t)kb * a->ldb;
-    tail.K = kt;
-    tail.A = reinterpret_cast<const char*>(a->A) + a_off * es;
-    tail.B = reinterpret_cast<const char*>(a->B) + b_off * es;
-    body.K = kb; body.accumulate = 1; body.bias = nullptr; body.resid = nullptr;
-    tail.ln_out = nullptr; body.ln_out = nullptr;  // the LayerNorm (if any) follows the complete product
-    if (a->ln_out) {
-      IMT_CHECK_ARG(a->ln_gamma && a->ln_beta, "imt_gemm: ln_out needs ln_gamma and ln_beta");
-      IMT_CHECK_ARG(a->c_dtype == a->dtype && !a->accumulate, "imt_gemm: ln_out needs C of the compute type, no accumulate");
-      IMT_CHECK_ARG(a->ldc == a->N && a->ld_ln == a->N, "imt_gemm: ln_out behind a GEMM that cannot normalise in-launch needs contiguous C and ln_out");
-    }
-    int rc = imt_gemm(&tail, stream);
-    if (rc != IMT_OK) return rc;
-    rc = imt_gemm(&body, stream);
-    if (rc != IMT_OK || !a->ln_out) return rc;
-    return imt_layernorm_fwd(a->dtype, a->C, a->ln_gamma, a->ln_beta, a->ln_out, a->ln_mean, a->ln_rstd, a->M, a->N, a->ln_eps, 0.f, 0, stream);
-  }
-  // few output tiles, long K, a workspace for partial sums: K ranges on the persistent kernel + one epilogue launch
-  if (a->force_general == 0 && a->splitk_ws && splits == 1 && a->layout != IMT_TN && pipe_ok && a->N % 4 == 0 && !a->a_colsum) {
-    const int64_t tiles = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN);
-    const bool ln_fused = a->ln_out && a->aux_mode == IMT_AUX_NONE && a->N <= 1024 && !c_f32;
-    const int S = splitk_choice(tiles, a->K / bk, ln_fused);
-    const int64_t rows_pad = (int64_t)imt_cdiv(a->M, BM) * BM;  // edge tiles store only rows < M, slabs are addressed [m][n] with ld N
-    if (S > 1 && (int64_t)S * a->M * a->N * 4 <= a->splitk_ws_bytes && rows_pad > 0 && ((uintptr_t)a->splitk_ws & 15) == 0) {
-      if (a->aux_mode != IMT_AUX_NONE) IMT_CHECK_ARG(a->aux != nullptr, "imt_gemm: aux_mode needs aux");
-      if (a->ln_out) {
-        IMT_CHECK_ARG(a->ln_gamma && a->ln_beta, "imt_gemm: ln_out needs ln_gamma and ln_beta");
-        IMT_CHECK_ARG(a->c_dtype == a->dtype && !a->accumulate && a->ldc == a->N && a->ld_ln == a->N, "imt_gemm: ln_out needs contiguous C of the compute type");
-      }
-      hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-      EpiParams slab;
-      slab.C = a->splitk_ws; slab.ldc = a->N; slab.c_f32 = 1; slab.accumulate = 0;
-      slab.bias = nullptr; slab.resid = nullptr; slab.ldr = 0; slab.aux = nullptr; slab.ldaux = 0; slab.aux_mode = IMT_AUX_NONE;
-      slab.atomic = 0; slab.alpha = 1.0f; slab.alpha_dev = nullptr; slab.inv_keep = 1.0f; slab.drop_thresh = 0; slab.seed = 0;
-      slab.a_colsum = nullptr; slab.dbg = 0; slab.trace = nullptr;
-      slab.slab_elems = (int64_t)a->M * a->N; slab.splits = S;
-      int rc = (a->dtype == IMT_F32) ? dispatch<float>(a, slab, 1, a->K, 5, st) : dispatch<bf16_t>(a, slab, 1, a->K, 5, st);
-      if (rc != IMT_OK) return rc;
-      EpiParams ep;
-      ep.C = a->C; ep.ldc = a->ldc; ep.c_f32 = c_f32; ep.accumulate = a->accumulate;
-      ep.bias = a->bias; ep.resid = a->resid; ep.ldr = a->ldr;
-      ep.aux = a->aux; ep.ldaux = a->ldaux; ep.aux_mode = a->aux_mode; ep.atomic = 0;
-      ep.alpha = a->alpha; ep.alpha_dev = a->alpha_dev;
-      ep.drop_thresh = dropout_thresh(a->dropout_p);
-      ep.inv_keep = a->dropout_p > 0.f ? 1.0f / (1.0f - a->dropout_p) : 1.0f;
-      ep.seed = a->dropout_seed; ep.a_colsum = nullptr; ep.dbg = 0; ep.trace = nullptr; ep.slab_elems = 0;
-      if (ln_fused) {
-        // dense + bias + dropout + residual + LayerNorm: the epilogue launch normalises its rows itself
-        ep.ln_gamma = a->ln_gamma; ep.ln_beta = a->ln_beta; ep.ln_out = a->ln_out; ep.ld_ln = a->ld_ln;
-        ep.ln_mean = a->ln_mean; ep.ln_rstd = a->ln_rstd; ep.ln_eps = a->ln_eps;
-        ImtProfScope prof("gemm_splitk_epilogue_ln", 0.0, (double)a->M * a->N * (4.0 * S + 3.0 * es), st);
-        const float* slabs = reinterpret_cast<const float*>(a->splitk_ws);
-        return (a->dtype == IMT_F32) ? launch_splitk_epilogue_ln<float>(slabs, slab.slab_elems, S, a->M, a->N, ep, st)
-                                     : launch_splitk_epilogue_ln<bf16_t>(slabs, slab.slab_elems, S, a->M, a->N, ep, st);
-      }
-      {
-        const int64_t groups = (int64_t)a->M * (a->N / 4);
-        ImtProfScope prof("gemm_splitk_epilogue", 0.0, (double)a->M * a->N * (4.0 * S + 2.0 * es), st);
-        const float* slabs = reinterpret_cast<const float*>(a->splitk_ws);
-        if (a->dtype == IMT_F32)
-          hipLaunchKernelGGL(splitk_epilogue_kernel<float>, dim3(imt_cdiv(groups, 256)), dim3(256), 0, st, slabs, slab.slab_elems, S, a->M, a->N, ep);
-        else
-          hipLaunchKernelGGL(splitk_epilogue_kernel<bf16_t>, dim3(imt_cdiv(groups, 256)), dim3(256), 0, st, slabs, slab.slab_elems, S, a->M, a->N, ep);
-        IMT_CHECK_LAUNCH();
-      }
-      if (!a->ln_out) return IMT_OK;
-      return imt_layernorm_fwd(a->dtype, a->C, a->ln_gamma, a->ln_beta, a->ln_out, a->ln_mean, a->ln_rstd, a->M, a->N, a->ln_eps, 0.f, 0, stream);
-    }
-  }
-  const int64_t nblocks = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN) * splits;
-  // kernel variant: 1 = register-staged double buffer (2 blocks/CU), 2 = LDS-DMA 3-stage ring (1 block/CU),
-  // 3 = single buffer + register prefetch (4 blocks/CU).  a->force_general carries a variant code for tests/tuning.
-  int variant = a->force_general % 100;
-  static const int env_dbg = getenv("IMT_GEMM_DBG") ? atoi(getenv("IMT_GEMM_DBG")) : 0;  // tuning only
-  const int dbg = a->force_general / 100 | env_dbg;
-  // measured on MI355X (profiles/r01_v3_gemm_shapes.txt): about one wave of blocks -> the LDS-DMA ring (its long
-  // steady state wins when K >= 1024, a tie otherwise); larger grids -> three single-buffer blocks per CU.
-  // measured on MI355X (profiles/r01_v5_gemm_shapes.txt): the persistent wave-specialised kernel wins whenever a CU
-  // gets about one output tile or K is long (740 vs 480 TFLOP/s at 8192x512x2048); grids of many short-K tiles are
-  // still better served by three single-buffer blocks per CU overlapping each other's epilogues.
-  if (variant == 0) {
-    const int64_t tiles = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN);
-    // (weight gradients with many output tiles and a short K -- few tokens: captioning, decoding-sized batches -- also run
-    // best on the persistent kernel: 30000 x 512 x 992 TN 64 against 92 us on the register-staged one, tools/tn_small_k.py)
-    if (pipe_ok && splits == 1 && (tiles <= 256 || a->K >= 1024 || a->layout == IMT_TN)) variant = 5;
-    else variant = (a->layout == IMT_TN) ? 1 : 3;
-    // 256 x 256 tiles (profiles/r01_gemm_xl_study.txt): several rounds of short-K tiles (vocabulary projection 797 vs 681
-    // TFLOP/s, batched cross K/V), or one round whose epilogue touches a second matrix (GELU / GELU' / residual: 500 vs 430)
-    const int64_t tiles256 = (int64_t)imt_cdiv(a->M, 256) * imt_cdiv(a->N, 256);
-    static const bool no_xl = getenv("IMT_GEMM_NO_XL") != nullptr;
-    static const bool no_xl_gelu = getenv("IMT_GEMM_NO_XL_GELU") != nullptr;  // tuning only
-    if (!no_xl && pipe_ok && splits == 1 && a->layout != IMT_TN && !a->a_colsum && a->K < 1024 &&
-        (tiles256 >= 512 || (tiles256 >= 224 && ((a->aux_mode != IMT_AUX_NONE && !(a->aux_mode == IMT_AUX_GELU_FWD && no_xl_gelu)) || a->resid))))
-      variant = 6;
-    // a weight gradient with about one 256-tile per CU and a long K (the vocabulary projection's dW: 30000 x 512 x 8128)
-    static const bool no_xl_tn = getenv("IMT_GEMM_NO_XL_TN") != nullptr;
-    if (!no_xl && !no_xl_tn && pipe_ok && splits == 1 && a->layout == IMT_TN && tiles256 >= 224 && tiles256 <= 256 && a->K >= 2048) variant = 6;
-    // data-parallel knob (off by default, DESIGN.md section 6): when a collective's kernels hold some CUs, a persistent
-    // launch of exactly one tile per CU needs a full second round; three small workgroups per CU degrade gracefully
-    if (share_cus_policy() && variant == 5 && a->layout != IMT_TN && tiles > 192 && tiles <= 256 && a->K < 1024) variant = 3;
-  }
-  if (variant == 6 && (!pipe_ok || splits > 1 || (a->a_colsum && a->layout != IMT_TN))) variant = 3;
-  if ((variant == 2 || variant == 4) && !pipe_ok) variant = 1;
-  if (variant == 5 && (!pipe_ok || splits > 1)) variant = 3;
-  EpiParams ep;
-  ep.C = a->C; ep.ldc = a->ldc; ep.c_f32 = c_f32; ep.accumulate = a->accumulate;
-  ep.bias = a->bias; ep.resid = a->resid; ep.ldr = a->ldr;
-  ep.aux = a->aux; ep.ldaux = a->ldaux; ep.aux_mode = a->aux_mode;
-  ep.atomic = (splits > 1);
-  ep.alpha = a->alpha; ep.alpha_dev = a->alpha_dev;
-  ep.drop_thresh = dropout_thresh(a->dropout_p);
-  ep.inv_keep = a->dropout_p > 0.f ? 1.0f / (1.0f - a->dropout_p) : 1.0f;
-  ep.seed = a->dropout_seed;
-  ep.a_colsum = a->a_colsum;
-  ep.dbg = dbg;
-  ep.trace = nullptr;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // LayerNorm of the finished rows: in-launch (ln_rowblock_tail) when this is a one-tile-per-workgroup launch of the
-  // persistent kernel over whole 128-column tiles; otherwise a LayerNorm launch behind the GEMM
-  bool ln_in_launch = false;
-  if (a->ln_out) {
-    IMT_CHECK_ARG(a->ln_gamma && a->ln_beta, "imt_gemm: ln_out needs ln_gamma and ln_beta");
-    IMT_CHECK_ARG(a->c_dtype == a->dtype && splits == 1 && !a->accumulate, "imt_gemm: ln_out needs C of the compute type, no split-K, no accumulate");
-    static const bool no_ticket = getenv("IMT_GEMM_LN_TICKET") && atoi(getenv("IMT_GEMM_LN_TICKET")) == 0;  // tuning / tests
-    const int64_t tiles = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN);
-    ln_in_launch = IMT_LN_TICKET && !no_ticket && variant == 5 && tiles <= 256 && a->N % BN == 0 && a->N <= 1024 && a->ln_tickets != nullptr &&
-                   ((int64_t)(a->M - 1) * a->ldc + a->N) * es < (1ll << 31);
-    if (ln_in_launch) {
-      ep.ln_gamma = a->ln_gamma; ep.ln_beta = a->ln_beta; ep.ln_out = a->ln_out; ep.ld_ln = a->ld_ln;
-      ep.ln_mean = a->ln_mean; ep.ln_rstd = a->ln_rstd; ep.ln_tickets = a->ln_tickets; ep.ln_eps = a->ln_eps;
-    } else {
-      IMT_CHECK_ARG(a->ldc == a->N && a->ld_ln == a->N, "imt_gemm: ln_out behind a GEMM that cannot normalise in-launch needs contiguous C and ln_out");
-    }
-  }
-  const int rc = (a->dtype == IMT_F32) ? dispatch<float>(a, ep, splits, kps, variant, st) : dispatch<bf16_t>(a, ep, splits, kps, variant, st);
-  if (rc != IMT_OK || !a->ln_out || ln_in_launch) return rc;
-  return imt_layernorm_fwd(a->dtype, a->C, a->ln_gamma, a->ln_beta, a->ln_out, a->ln_mean, a->ln_rstd, a->M, a->N, a->ln_eps, 0.f, 0, stream);
+  const GemmSwitches& sw = gemm_switches();
+  const bool linear_epilogue = a->aux_mode == IMT_AUX_NONE && a->dropout_p == 0.f && !a->a_colsum;
+  if (a->force_general == 0 && splits == 1 && a->layout != IMT_TN && a->K % f.bk != 0 && a->K / f.bk >= 16 && linear_epilogue) return run_ragged_k(a, f, stream);
+  if (const int S = splitk_ws_splits(a, f, sw, splits); S > 1) return run_splitk_ws(a, f, S, stream);
+  return run_single(a, f, sw, splits, kps, stream);
 }
 
 extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* stream) {
@@ -1835,9 +1841,7 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
   }
   GroupArgs g;
   memset(&g, 0, sizeof(g));
-  g.count = count; g.alpha = list[0].alpha;
-  static const bool plain_order = getenv("IMT_GROUPED_PLAIN_ORDER") != nullptr;  // tuning only
-  g.alpha_pad_order = plain_order ? 1 : 0;
+  g.count = count; g.alpha = list[0].alpha; g.alpha_pad_order = gemm_switches().grouped_plain_order ? 1 : 0;
   int start = 0;
   double flops = 0, bytes = 0;
   for (int i = 0; i < count; ++i) {
@@ -1852,17 +1856,10 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
     bytes += ((double)a.M + a.N) * a.K * es + 4.0 * a.M * a.N;
   }
   g.total_tiles = start;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_grouped_tn_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_NST * STAGE_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_grouped_tn_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_NST * STAGE_BYTES);
-    attr_set = true;
-  }
+  static const bool once = allow_lds(gemm_grouped_tn_kernel<float>, GROUP_NST * STAGE_BYTES) && allow_lds(gemm_grouped_tn_kernel<bf16_t>, GROUP_NST * STAGE_BYTES);
   ImtProfScope prof(dtype == IMT_BF16 ? "gemm_bf16_tn_grouped" : "gemm_f32_tn_grouped", flops, bytes, st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(gemm_grouped_tn_kernel<float>, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);
-  else
-    hipLaunchKernelGGL(gemm_grouped_tn_kernel<bf16_t>, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);
+  auto kern = (dtype == IMT_F32) ? gemm_grouped_tn_kernel<float> : gemm_grouped_tn_kernel<bf16_t>;
+  hipLaunchKernelGGL(kern, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }
