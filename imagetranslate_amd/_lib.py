@@ -214,6 +214,10 @@ SIGNATURES = {
     "imt_obj_fold_w": (c_int, [_P, _P, c_int, c_int, _P]),
     "imt_obj_embed_grad": (c_int, [c_int, _P, _P, c_int64, _P, c_int64, c_int, _P]),
     "imt_gated_mix_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
+    "imt_attn_pool_plan": (c_int, [c_int, c_int, c_int]),
+    "imt_attn_pool_fwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "imt_attn_pool_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "imt_contrastive": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "imt_comm_unique_id_bytes": (c_int, []),
     "imt_comm_get_unique_id": (c_int, [_P]),
     "imt_comm_init": (c_int, [_P, c_int, c_int, POINTER(c_void_p)]),

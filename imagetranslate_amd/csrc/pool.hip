@@ -1,0 +1,367 @@
+// Contrastive tail of ImageMassSeq2Seq (src/image_model.py:231-264): one-vector attention pooling of a [rows, S, d] tensor to
+// unit vectors (forward and backward), and the image-to-text contrastive loss with its gradients.
+//
+// Pooling, one workgroup (4 waves) per sentence:
+//   score_s = x_s . w + b, a masked position is set to exactly -10000 (masked_fill, :241,246), p = softmax(score),
+//   v = sum_s p_s x_s, u = v / (|v| + 1e-4) (:255-258).
+// x is read from HBM once when the sentence fits in LDS beside the small per-position arrays (imt_attn_pool_plan == 1): the
+// score pass keeps the raw elements in LDS and the weighted sum reads them there.  Otherwise (plan 2) the weighted sum reads
+// x a second time; nothing reads it a third time.  The backward follows the same plan: dp_s = dv . x_s is the first read, the
+// pass that writes dx and accumulates dw the second.  All statistics and sums are fp32 and every reduction has a fixed order
+// (wave butterflies, then partial sums added in index order; dw / db as per-sentence partials folded in sentence order by a
+// second launch): the same call on the same data gives the same bits.
+#include "common.hpp"
+#include <math.h>
+
+namespace {
+
+constexpr int POOL_THREADS = 256;
+constexpr int POOL_PART_FLOATS = 1024;  // column-group partial sums: (256 / (d / 4)) groups x d floats <= 1024
+
+inline bool ok_dtype(int t) { return t == IMT_F32 || t == IMT_BF16; }
+inline int round4(int s) { return (s + 3) & ~3; }
+// LDS besides x: reduction scratch, two per-position arrays (scores / probabilities), the partial sums, one d-vector
+inline int64_t pool_small_bytes(int S, int d) { return 64 + 2 * (int64_t)round4(S) * 4 + POOL_PART_FLOATS * 4 + (int64_t)d * 4; }
+inline int64_t pool_x_bytes(int dtype, int S, int d) { return (int64_t)S * d * (dtype == IMT_BF16 ? 2 : 4); }
+
+struct PoolLds {
+  float* red; float* sc; float* pr; float* part; float* vec; unsigned char* xs;
+};
+IMT_DEVICE PoolLds pool_lds(unsigned char* smem, int S, int d) {
+  PoolLds l;
+  const int S4 = (S + 3) & ~3;
+  l.red = reinterpret_cast<float*>(smem);
+  l.sc = l.red + 16;
+  l.pr = l.sc + S4;
+  l.part = l.pr + S4;
+  l.vec = l.part + POOL_PART_FLOATS;
+  l.xs = reinterpret_cast<unsigned char*>(l.vec + d);
+  return l;
+}
+
+// sums / maxima over the 256 threads in a fixed order; every thread must call
+IMT_DEVICE float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+IMT_DEVICE float block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+IMT_DEVICE float dot4(f32x4 a, f32x4 b) { return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]; }
+
+// dot product of every position's row with vec[0..d) (global T or LDS fp32), one wave per position; out[s] = the sum.  The raw
+// elements are kept in LDS when keep_x.
+template <typename T, typename TV>
+IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T* xs, float* out, int S, int d, bool keep_x) {
+  constexpr int U = 4;  // positions per wave iteration: their loads are in flight together (one position's sum order is unchanged)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int s0 = wave * U; s0 < S; s0 += (POOL_THREADS / 64) * U) {
+    float acc[U] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = lane * 4; c < d; c += 256) {
+      const f32x4 vv = Vec4<TV>::load(vec + c);
+      typename Vec4<T>::type raw[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k)
+        if (s0 + k < S) raw[k] = Vec4<T>::load_raw(xr + (int64_t)(s0 + k) * d + c);
+#pragma unroll
+      for (int k = 0; k < U; ++k)
+        if (s0 + k < S) {
+          if (keep_x) *reinterpret_cast<typename Vec4<T>::type*>(xs + (int64_t)(s0 + k) * d + c) = raw[k];
+          acc[k] += dot4(Vec4<T>::cvt(raw[k]), vv);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const float a = wave_sum(acc[k]);
+      if (lane == 0 && s0 + k < S) out[s0 + k] = a;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(POOL_THREADS) void attn_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
+                                                                     const uint8_t* __restrict__ mask, float* __restrict__ u,
+                                                                     float* __restrict__ probs, float* __restrict__ norm, int S, int d,
+                                                                     int keep_x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PoolLds l = pool_lds(smem, S, d);
+  T* xs = reinterpret_cast<T*>(l.xs);
+  const int64_t row = blockIdx.x;
+  const T* xr = x + row * S * d;
+  const int t = threadIdx.x;
+  // scores (first read of x)
+  row_dots<T, T>(xr, w, xs, l.sc, S, d, keep_x != 0);
+  __syncthreads();
+  const float bias = to_f32<T>(b[0]);
+  float m = -INFINITY;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float v = (mask && !mask[row * S + s]) ? -10000.0f : l.sc[s] + bias;
+    l.sc[s] = v;
+    m = fmaxf(m, v);
+  }
+  m = block_max(m, l.red);
+  float sum = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float e = expf(l.sc[s] - m);
+    l.sc[s] = e;
+    sum += e;
+  }
+  sum = block_sum(sum, l.red);
+  const float inv = 1.0f / sum;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float p = l.sc[s] * inv;
+    l.sc[s] = p;
+    probs[row * S + s] = p;
+  }
+  __syncthreads();
+  // weighted sum: thread (g, cg) adds positions g, g + G, ... of column group cg; the G partial vectors are added in order
+  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
+  const int cg = t % ncol4, g = t / ncol4;
+  if (g < G) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = g; s < S; s += G) {
+      const f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      acc += xv * l.sc[s];
+    }
+    Vec4<float>::store(l.part + g * d + cg * 4, acc);
+  }
+  __syncthreads();
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (t < ncol4)
+    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
+  const float ss = block_sum(dot4(v, v), l.red);
+  const float r = sqrtf(ss);
+  if (t < ncol4) Vec4<float>::store(u + row * d + t * 4, v * (1.0f / (r + 1e-4f)));
+  if (t == 0) norm[row] = r;
+}
+
+// dx, and this sentence's partial dw [d] / db.  u = v / (r + eps), r = |v|:  dv = du / (r + eps) - u (du . u) / r;
+// dp_s = dv . x_s;  dscore_s = p_s (dp_s - sum_t p_t dp_t), 0 at a masked position (its score is a constant);
+// dx_s = p_s dv + dscore_s w;  dw = sum_s dscore_s x_s;  db = sum_s dscore_s.
+template <typename T>
+__global__ __launch_bounds__(POOL_THREADS) void attn_pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const uint8_t* __restrict__ mask,
+                                                                     const float* __restrict__ u, const float* __restrict__ probs,
+                                                                     const float* __restrict__ norm, const float* __restrict__ du,
+                                                                     const float* __restrict__ du_scale, T* __restrict__ dx,
+                                                                     float* __restrict__ dw_part, float* __restrict__ db_part, int S, int d,
+                                                                     int keep_x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PoolLds l = pool_lds(smem, S, d);
+  T* xs = reinterpret_cast<T*>(l.xs);
+  const int64_t row = blockIdx.x;
+  const T* xr = x + row * S * d;
+  const int t = threadIdx.x;
+  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
+  // dv
+  f32x4 uv = {0.f, 0.f, 0.f, 0.f}, gv = {0.f, 0.f, 0.f, 0.f};
+  if (t < ncol4) {
+    uv = Vec4<float>::load(u + row * d + t * 4);
+    gv = Vec4<float>::load(du + row * d + t * 4);
+    if (du_scale) gv *= du_scale[0];
+  }
+  const float gu = block_sum(dot4(gv, uv), l.red);
+  const float r = norm[row];
+  const float coef = r > 0.f ? gu / r : 0.f;
+  if (t < ncol4) Vec4<float>::store(l.vec + t * 4, gv * (1.0f / (r + 1e-4f)) - uv * coef);
+  for (int s = t; s < S; s += POOL_THREADS) l.pr[s] = probs[row * S + s];
+  __syncthreads();
+  // dp (first read of x)
+  row_dots<T, float>(xr, l.vec, xs, l.sc, S, d, keep_x != 0);
+  __syncthreads();
+  float c0 = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) c0 += l.pr[s] * l.sc[s];
+  c0 = block_sum(c0, l.red);
+  float dbl = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float ds = (mask && !mask[row * S + s]) ? 0.f : l.pr[s] * (l.sc[s] - c0);
+    l.sc[s] = ds;
+    dbl += ds;
+  }
+  dbl = block_sum(dbl, l.red);
+  // dx and dw (second read of x, or LDS)
+  const int cg = t % ncol4, g = t / ncol4;
+  if (g < G) {
+    const f32x4 wv = Vec4<T>::load(w + cg * 4), dv = Vec4<float>::load(l.vec + cg * 4);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = g; s < S; s += G) {
+      const f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      const float ds = l.sc[s];
+      Vec4<T>::store(dx + (row * S + s) * d + cg * 4, dv * l.pr[s] + wv * ds);
+      acc += xv * ds;
+    }
+    Vec4<float>::store(l.part + g * d + cg * 4, acc);
+  }
+  __syncthreads();
+  if (t < ncol4) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
+    Vec4<float>::store(dw_part + row * d + t * 4, v);
+  }
+  if (t == 0) db_part[row] = dbl;
+}
+
+// dw[c] += sum over sentences (in order) of dw_part[row, c]; thread d does the same for db
+__global__ __launch_bounds__(256) void attn_pool_fold_kernel(const float* __restrict__ dw_part, const float* __restrict__ db_part,
+                                                            float* __restrict__ dw, float* __restrict__ db, int64_t rows, int d) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c > d) return;
+  float s = 0.f;
+  if (c < d) {
+    for (int64_t r = 0; r < rows; ++r) s += dw_part[r * d + c];
+    dw[c] += s;
+  } else {
+    for (int64_t r = 0; r < rows; ++r) s += db_part[r];
+    db[0] += s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------- contrastive loss
+// Workgroup i: C_ij = img_i . txt_j for every j, row loss log(sum_j exp C_ij + 1e-4) - (C_ii + 1e-4) (:260-262),
+// dC_ij = (exp C_ij / (sum_j exp C_ij + 1e-4) - [i == j]) / B, d_img_i = sum_j dC_ij txt_j.
+__global__ __launch_bounds__(POOL_THREADS) void contrastive_rows_kernel(const float* __restrict__ img, const float* __restrict__ txt,
+                                                                        float* __restrict__ row_loss, float* __restrict__ dc,
+                                                                        float* __restrict__ d_img, int B, int N, int d) {
+  __shared__ float red[16];
+  __shared__ float c[IMT_CONTRASTIVE_MAX_N];
+  __shared__ __attribute__((aligned(16))) float iv[IMT_POOL_MAX_D];
+  const int i = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int ncol4 = d >> 2;
+  if (t < ncol4) Vec4<float>::store(iv + t * 4, Vec4<float>::load(img + (int64_t)i * d + t * 4));
+  __syncthreads();
+  for (int j = wave; j < N; j += POOL_THREADS / 64) {
+    float acc = 0.f;
+    for (int k = lane * 4; k < d; k += 256) acc += dot4(Vec4<float>::load(iv + k), Vec4<float>::load(txt + (int64_t)j * d + k));
+    acc = wave_sum(acc);
+    if (lane == 0) c[j] = acc;
+  }
+  __syncthreads();
+  float se = 0.f;
+  for (int j = t; j < N; j += POOL_THREADS) se += expf(c[j]);
+  se = block_sum(se, red);
+  const float den = se + 1e-4f;
+  if (t == 0) row_loss[i] = logf(den) - (c[i] + 1e-4f);
+  __syncthreads();
+  const float inv_b = 1.0f / (float)B;
+  for (int j = t; j < N; j += POOL_THREADS) {
+    const float g = (expf(c[j]) / den - (j == i ? 1.f : 0.f)) * inv_b;
+    c[j] = g;
+    dc[(int64_t)i * N + j] = g;
+  }
+  __syncthreads();
+  if (t < ncol4) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < N; ++j) acc += Vec4<float>::load(txt + (int64_t)j * d + t * 4) * c[j];
+    Vec4<float>::store(d_img + (int64_t)i * d + t * 4, acc);
+  }
+}
+
+// Workgroup j: d_txt_j = sum_i dC_ij img_i (in order); workgroup 0 also adds the row losses: loss = sum_i row_loss_i / B (:263)
+__global__ __launch_bounds__(POOL_THREADS) void contrastive_cols_kernel(const float* __restrict__ img, const float* __restrict__ dc,
+                                                                        const float* __restrict__ row_loss, float* __restrict__ d_txt,
+                                                                        float* __restrict__ loss, int B, int N, int d) {
+  const int j = blockIdx.x, t = threadIdx.x;
+  if (t < (d >> 2)) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < B; ++i) acc += Vec4<float>::load(img + (int64_t)i * d + t * 4) * dc[(int64_t)i * N + j];
+    Vec4<float>::store(d_txt + (int64_t)j * d + t * 4, acc);
+  }
+  if (j == 0 && t == 0) {
+    float s = 0.f;
+    for (int i = 0; i < B; ++i) s += row_loss[i];
+    loss[0] = s / (float)B;
+  }
+}
+
+// validate: everything that can be refused without touching the device
+int pool_validate(const char* what, int dtype, int64_t rows, int S, int d) {
+  IMT_CHECK_ARG(ok_dtype(dtype), "%s: bad dtype", what);
+  IMT_CHECK_ARG(rows >= 0 && rows <= 0x7fffffff, "%s: row count outside [0, 2^31)", what);
+  IMT_CHECK_ARG(S >= 1, "%s: S must be at least 1", what);
+  IMT_CHECK_ARG(S <= IMT_POOL_MAX_S, "%s: S above %d is not taken", what, IMT_POOL_MAX_S);
+  IMT_CHECK_ARG(d >= 4 && d % 4 == 0, "%s: d must be a positive multiple of 4", what);
+  IMT_CHECK_ARG(d <= IMT_POOL_MAX_D, "%s: d above %d is not taken", what, IMT_POOL_MAX_D);
+  return IMT_OK;
+}
+
+}  // namespace
+
+extern "C" int imt_attn_pool_plan(int dtype, int S, int d) {
+  const int rc = pool_validate("attn_pool_plan", dtype, 0, S, d);
+  if (rc != IMT_OK) return rc;
+  return pool_small_bytes(S, d) + pool_x_bytes(dtype, S, d) <= IMT_POOL_LDS_BYTES ? 1 : 2;
+}
+
+extern "C" int imt_attn_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, float* u, float* probs,
+                                 float* norm, int64_t rows, int S, int d, void* stream) {
+  const int rc = pool_validate("attn_pool_fwd", dtype, rows, S, d);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && b && u && probs && norm, "attn_pool_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
+  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
+  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
+  ImtProfScope prof("attn_pool_fwd", 2.0 * rows * S * d * 2, (keep ? 1.0 : 2.0) * xb, st);
+  if (dtype == IMT_F32)
+    hipLaunchKernelGGL(attn_pool_fwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w,
+                       (const float*)b, mask, u, probs, norm, S, d, keep);
+  else
+    hipLaunchKernelGGL(attn_pool_fwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       (const bf16_t*)b, mask, u, probs, norm, S, d, keep);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_attn_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* u, const float* probs,
+                                 const float* norm, const float* du, const float* du_scale, void* dx, float* dw, float* db, float* ws,
+                                 int64_t rows, int S, int d, void* stream) {
+  const int rc = pool_validate("attn_pool_bwd", dtype, rows, S, d);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && u && probs && norm && du && dx && dw && db && ws, "attn_pool_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
+  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
+  float* dw_part = ws;
+  float* db_part = ws + rows * d;
+  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
+  ImtProfScope prof("attn_pool_bwd", 2.0 * rows * S * d * 3, (keep ? 2.0 : 3.0) * xb, st);
+  if (dtype == IMT_F32)
+    hipLaunchKernelGGL(attn_pool_bwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w, mask,
+                       u, probs, norm, du, du_scale, (float*)dx, dw_part, db_part, S, d, keep);
+  else
+    hipLaunchKernelGGL(attn_pool_bwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       mask, u, probs, norm, du, du_scale, (bf16_t*)dx, dw_part, db_part, S, d, keep);
+  IMT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_pool_fold_kernel, dim3(imt_cdiv(d + 1, 256)), dim3(256), 0, st, dw_part, db_part, dw, db, rows, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_contrastive(const float* img, const float* txt, float* loss, float* d_img, float* d_txt, float* ws, int B, int N,
+                               int d, void* stream) {
+  IMT_CHECK_ARG(B >= 1, "contrastive: B must be at least 1");
+  IMT_CHECK_ARG(N >= B, "contrastive: fewer text vectors than images (the first B belong to the images)");
+  IMT_CHECK_ARG(N <= IMT_CONTRASTIVE_MAX_N, "contrastive: more than %d text vectors are not taken", IMT_CONTRASTIVE_MAX_N);
+  IMT_CHECK_ARG(d >= 4 && d % 4 == 0, "contrastive: d must be a positive multiple of 4");
+  IMT_CHECK_ARG(d <= IMT_POOL_MAX_D, "contrastive: d above %d is not taken", IMT_POOL_MAX_D);
+  IMT_CHECK_ARG(img && txt && loss && d_img && d_txt && ws, "contrastive: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  float* dc = ws;                       // [B, N]
+  float* row_loss = ws + (int64_t)B * N;  // [B]
+  ImtProfScope prof("contrastive", 6.0 * B * N * d, 4.0 * ((double)B * d + (double)N * d) * 3, st);
+  hipLaunchKernelGGL(contrastive_rows_kernel, dim3(B), dim3(POOL_THREADS), 0, st, img, txt, row_loss, dc, d_img, B, N, d);
+  IMT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(contrastive_cols_kernel, dim3(N), dim3(POOL_THREADS), 0, st, img, dc, row_loss, d_txt, loss, B, N, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}

@@ -16,6 +16,7 @@ ragged) are what the kernels see in real training.
 """
 import glob
 import marshal
+import random
 from typing import List, Optional
 
 import torch
@@ -201,13 +202,20 @@ def _with_objects(batch, features, paths):
 
 class ImageCaptionDataset(Dataset):
     """src/dataset.py:278-376 with region features in place of pixels: captions in file order, a batch closed when it
-    would hold more than ``max_img_per_batch`` images or 2 * L^3 * n > max_capacity * 1e6 (L = longest caption)."""
+    would hold more than ``max_img_per_batch`` images or 2 * L^3 * n > max_capacity * 1e6 (L = longest caption).
+    ``use_neg_samples`` (the reference's ImageCaptionDatasetwNegSamples, :385-398): every item also carries ``"neg"``, the
+    same min(number of captions, max(30, batch size)) captions for all rows of the batch, sampled without replacement from
+    all captions and padded with pad_idx, and ``"neg_mask"``.  They are drawn from a generator of the dataset's own
+    (``neg_seed``), not from the global ``random`` state: a seed pins the draws and nothing else is disturbed."""
 
     def __init__(self, root_img_dir: str, data_bin_file: str, max_capacity: int, text_processor, max_img_per_batch: int,
-                 lex_dict=None, ngpu: int = 1, use_neg_samples: bool = False, features: Optional[RegionFeatures] = None):
+                 lex_dict=None, ngpu: int = 1, use_neg_samples: bool = False, features: Optional[RegionFeatures] = None,
+                 neg_seed: int = 0):
         if lex_dict is not None:
             raise NotImplementedError("lexical proposals (--dict) are outside the hot path (SURVEY a5)")
         self.ngpu = ngpu
+        self.use_neg_samples = bool(use_neg_samples)
+        self._neg_rng = random.Random(neg_seed)
         self.pad_idx = text_processor.pad_token_id()
         self.features = features if features is not None else RegionFeatures(root_img_dir)
         self.batches, self.image_batches, self.all_captions, self.lang_ids = [], [], [], set()
@@ -246,6 +254,10 @@ class ImageCaptionDataset(Dataset):
         paths = [self.unique_images[i] for i in self.image_batches[item]]
         out = {"images": self.features.get(paths), "captions": texts, "pad_idx": pad_indices,
                "langs": torch.LongTensor([self.lang] * texts.size(0)), "caption_mask": mask, "proposal": None}
+        if self.use_neg_samples:
+            n = min(len(self.all_captions), max(30, int(texts.size(0))))
+            out["neg"] = pad_sequence(self._neg_rng.sample(self.all_captions, n), batch_first=True, padding_value=self.pad_idx)
+            out["neg_mask"] = out["neg"] != self.pad_idx
         return _with_objects(out, self.features, paths)
 
 

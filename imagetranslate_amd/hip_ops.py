@@ -560,6 +560,72 @@ def gated_mix_bwd(dy, a, b, gate, dgate):
     return da, db
 
 
+# ------------------------------------------------------------------------------------------- contrastive tail
+POOL_MAX_S, POOL_MAX_D, CONTRASTIVE_MAX_N = 4096, 1024, 4096  # include/imt_hip.h: IMT_POOL_MAX_S, IMT_POOL_MAX_D, IMT_CONTRASTIVE_MAX_N
+
+
+def attn_pool_plan(dtype, S, d):
+    """1: a sentence of the pooled tensor stays in LDS (read from memory once), 2: it is read twice (imt_attn_pool_plan)."""
+    plan = L.load().imt_attn_pool_plan(IMT_BF16 if dtype == torch.bfloat16 else IMT_F32, int(S), int(d))
+    L.check(min(plan, 0), "imt_attn_pool_plan")
+    return plan
+
+
+def _pool_mask(mask, rows, S):
+    if mask is None:
+        return None
+    assert tuple(mask.shape) == (rows, S) and mask.dtype in (torch.bool, torch.uint8)
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def attn_pool_fwd(x, w, b, mask=None, out=None):
+    """(u [rows, d], probs [rows, S], norm [rows]), all fp32, of the one-vector attention pooling of x [rows, S, d]
+    (imt_attn_pool_fwd); w [d] and b [1] in x's dtype, mask [rows, S] bool / uint8 or None; `out`: where u goes."""
+    _req_cuda(x, w, b, mask, out)
+    rows, S, d = x.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and b.dtype == x.dtype and w.numel() == d and b.numel() == 1
+    mask = _pool_mask(mask, rows, S)
+    u = out if out is not None else torch.empty((rows, d), device=x.device, dtype=torch.float32)
+    assert u.dtype == torch.float32 and u.is_contiguous() and tuple(u.shape) == (rows, d)
+    probs = torch.empty((rows, S), device=x.device, dtype=torch.float32)
+    norm = torch.empty((rows,), device=x.device, dtype=torch.float32)
+    L.check(L.load().imt_attn_pool_fwd(dt(x), _p(x), _p(w), _p(b), _p(mask), _p(u), _p(probs), _p(norm), rows, S, d, _stream()),
+            "imt_attn_pool_fwd")
+    return u, probs, norm
+
+
+def attn_pool_bwd(x, w, mask, u, probs, norm, du, dw, db, du_scale=None):
+    """dx [rows, S, d] in x's dtype; dw (fp32 [d]) and db (fp32 [1]) += the parameter gradients (imt_attn_pool_bwd,
+    deterministic).  du_scale: optional fp32 device scalar multiplied into du (an upstream loss gradient)."""
+    _req_cuda(x, w, mask, u, probs, norm, du, dw, db, du_scale)
+    rows, S, d = x.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and w.numel() == d
+    mask = _pool_mask(mask, rows, S)
+    for t, shape in ((u, (rows, d)), (probs, (rows, S)), (norm, (rows,)), (du, (rows, d)), (dw, (d,)), (db, (1,))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+    assert du_scale is None or (du_scale.dtype == torch.float32 and du_scale.numel() == 1)
+    dx = torch.empty_like(x)
+    ws = torch.empty((rows * d + rows,), device=x.device, dtype=torch.float32)
+    L.check(L.load().imt_attn_pool_bwd(dt(x), _p(x), _p(w), _p(mask), _p(u), _p(probs), _p(norm), _p(du), _p(du_scale), _p(dx), _p(dw),
+                                       _p(db), _p(ws), rows, S, d, _stream()), "imt_attn_pool_bwd")
+    return dx
+
+
+def contrastive(img, txt):
+    """(loss [1], d_img [B, d], d_txt [N, d]) of the image-to-text contrastive loss over fp32 unit vectors (imt_contrastive);
+    text row i < B belongs to image i."""
+    _req_cuda(img, txt)
+    B, d = img.shape
+    N = txt.shape[0]
+    assert img.dtype == txt.dtype == torch.float32 and img.is_contiguous() and txt.is_contiguous() and txt.shape[1] == d
+    loss = torch.empty((1,), device=img.device, dtype=torch.float32)
+    d_img, d_txt = torch.empty_like(img), torch.empty_like(txt)
+    ws = torch.empty((B * N + B,), device=img.device, dtype=torch.float32)
+    L.check(L.load().imt_contrastive(_p(img), _p(txt), _p(loss), _p(d_img), _p(d_txt), _p(ws), B, N, d, _stream()), "imt_contrastive")
+    return loss, d_img, d_txt
+
+
 def add_rows_dropout(x, add=None, out_dtype=None, dropout_p=0.0, dropout_seed=0):
     """out[r, :] = dropout(x[r, :] + add[r % add.shape[0], :]) for a 2-D x (imt_add_rows_dropout); add may be None."""
     _req_cuda(x, add)

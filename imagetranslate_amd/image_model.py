@@ -1,11 +1,14 @@
 """Image branch of the path -- drop-in for the on-path parts of the reference's ``src/image_model.py``:
-``ImageMassSeq2Seq`` (text branch ``:157-183``) and ``ImageCaptioning`` (``:267-377``).
+``ImageMassSeq2Seq`` (text branch ``:157-183``, gated text + image branch ``:185-230``, contrastive branch ``:231-264``) and
+``ImageCaptioning`` (``:267-377``).
 
 The CNN trunk (torchvision ResNet / Faster-RCNN, ``:14-124``) is OUT of scope (frozen
 feature extractor whose pretrained weights need a network fetch); region features ``[B, 49, C]`` enter at the
 ``fc`` layer: ``ImageHead`` = dropout -> fc (no bias) -> + location_embedding -> dropout (``:35-41,77-78``).
 The detector's output (box features, boxes, labels) enters pre-extracted as ``batch["objects"]``: ``ImageCaptioning``
 then runs its object stream (object rows ``:58-78``, ``obj_decoder`` and ``multistream_attention_gate`` ``:357-366``).
+``ImageMassSeq2Seq`` with ``batch=`` runs its decoder over the text states and over the image regions and mixes the two with
+``multimodal_attention_gate``, or, with negative samples, the contrastive loss on the fused pooling kernels (csrc/pool.hip).
 """
 import torch
 import torch.nn as nn
@@ -139,6 +142,52 @@ class _GatedMixFn(torch.autograd.Function):
         return None, da.view(ctx.shape), db.view(ctx.shape), None, None
 
 
+class _ContrastiveTailFn(torch.autograd.Function):
+    """Contrastive tail (src/image_model.py:240-263) as one node: ``imt_attn_pool_fwd`` on the caption states (masked by
+    src_pads), the negative-sample states (masked by neg_mask), both with encoder_attention_w, and on the image regions with
+    image_attention_w (unmasked), the two text sets written into one [B + Nn, d] buffer (the reference's cat, :250); then
+    ``imt_contrastive`` gives the loss and, in the same pass, its gradients with respect to the unit vectors.  Backward: three
+    ``imt_attn_pool_bwd`` calls (the upstream loss gradient enters as a device scalar) return the gradients the encoder stack
+    and the image head receive; d(encoder_attention_w), d(image_attention_w) accumulate into the flat gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, enc_states, src_mask, neg_states, neg_mask, img_states, model):
+        from .param_store import store_of
+        store = store_of(model).ensure()
+        dtype = enc_states.dtype
+        flat = store.params_for(dtype)
+        d = enc_states.shape[-1]
+        B, Nn = enc_states.shape[0], neg_states.shape[0]
+        if img_states.shape[0] != B:
+            raise ValueError("contrastive loss: %d images for %d captions" % (img_states.shape[0], B))
+        offs = [store.offset(p) for p in (model.encoder_attention_w.weight, model.encoder_attention_w.bias,
+                                          model.image_attention_w.weight, model.image_attention_w.bias)]
+        we, be, wi, bi = flat[offs[0]:offs[0] + d], flat[offs[1]:offs[1] + 1], flat[offs[2]:offs[2] + d], flat[offs[3]:offs[3] + 1]
+        enc, neg, img = enc_states.contiguous(), neg_states.to(dtype).contiguous(), img_states.to(dtype).contiguous()
+        txt = torch.empty((B + Nn, d), device=enc.device, dtype=torch.float32)
+        _, p_e, n_e = O.attn_pool_fwd(enc, we, be, src_mask, out=txt[:B])
+        _, p_n, n_n = O.attn_pool_fwd(neg, we, be, neg_mask, out=txt[B:])
+        img_u, p_i, n_i = O.attn_pool_fwd(img, wi, bi, None)
+        loss, d_img, d_txt = O.contrastive(img_u, txt)
+        ctx.store, ctx.offs, ctx.dims = store, offs, (B, Nn, d)
+        ctx.masks = (src_mask, neg_mask)
+        ctx.save_for_backward(enc, neg, img, we, wi, txt, img_u, p_e, n_e, p_n, n_n, p_i, n_i, d_img, d_txt)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        enc, neg, img, we, wi, txt, img_u, p_e, n_e, p_n, n_n, p_i, n_i, d_img, d_txt = ctx.saved_tensors
+        B, Nn, d = ctx.dims
+        grad, offs = ctx.store.grad, ctx.offs
+        g = g.detach().to(torch.float32).reshape(1).contiguous()
+        gw_e, gb_e = grad[offs[0]:offs[0] + d], grad[offs[1]:offs[1] + 1]
+        d_enc = O.attn_pool_bwd(enc, we, ctx.masks[0], txt[:B], p_e, n_e, d_txt[:B], gw_e, gb_e, du_scale=g)
+        d_neg = O.attn_pool_bwd(neg, we, ctx.masks[1], txt[B:], p_n, n_n, d_txt[B:], gw_e, gb_e, du_scale=g)
+        d_im = O.attn_pool_bwd(img, wi, None, img_u, p_i, n_i, d_img, grad[offs[2]:offs[2] + d], grad[offs[3]:offs[3] + 1], du_scale=g)
+        ctx.store.attach_grad_views()
+        return None, d_enc, None, d_neg, None, d_im, None
+
+
 def gated_mix(model, gate_param, a, b):
     """Autograd-aware sigmoid-gated mix of two [..., d] streams with a gate parameter of ``model``'s flat store."""
     from .param_store import store_of
@@ -261,9 +310,76 @@ class ImageMassSeq2Seq(MassSeq2Seq):
     def _un(x):
         return x[0] if isinstance(x, list) else x
 
+    def _mix_image_stream(self, text_output, image_embeddings, batch_lang, **dec_kw):
+        """The SAME decoder a second time, over the image regions with no key mask (src/image_model.py:213-216), and the
+        sigmoid-gated mix of the two outputs (:217-219).  The pass draws its own dropout seed; the shared decoder parameters
+        receive both passes' gradients (the stack runtime accumulates into the flat gradient)."""
+        decoder = self.decoder if not self.lang_dec else self.decoder[batch_lang]
+        dec_kw["encoder_attention_mask"] = None
+        fixed = getattr(decoder, "_imt_dropout_seed", None)
+        if fixed is not None:  # a pinned seed (tests): the second pass still gets masks of its own
+            decoder._imt_dropout_seed = int(fixed) + 1
+        try:
+            image_output = decoder(encoder_states=image_embeddings, **dec_kw)
+        finally:
+            if fixed is not None:
+                decoder._imt_dropout_seed = fixed
+        return gated_mix(self, self.multimodal_attention_gate, text_output, image_output)
+
+    def _encode_text_and_image(self, src_inputs, src_pads, src_langs, batch):
+        """(encoder states, image embeddings, src_pads on the device) of src/image_model.py:185-190.  The reference's head
+        returns (grid, objects) and its ``encode`` keeps that tuple (:153 against :82), so the branch cannot run there; the
+        build takes element 0, the grid embeddings, which is plainly what :213 and :252 mean."""
+        if src_inputs is None:
+            raise ValueError("ImageMassSeq2Seq with batch=: src_inputs is required (src/image_model.py:185)")
+        device = self.encoder.embeddings.word_embeddings.weight.device
+        src_inputs = src_inputs.to(device)
+        src_pads = (src_inputs != self.text_processor.pad_token_id()) if src_pads is None else src_pads.to(device)
+        src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
+        encoder_states = MassSeq2Seq.encode(self, src_inputs, src_pads, src_langs_t)[0]
+        images = batch["images"]
+        image_embeddings = self.image_model(images[0] if isinstance(images, list) else images, self._imt_compute_dtype)[0]
+        return encoder_states, image_embeddings, src_pads
+
+    def _multimodal_rows(self, src_inputs, src_pads, tgt_inputs, src_langs, tgt_langs, pad_idx, tgt_positions, batch, proposals):
+        """Non-pad decoder rows of the gated text + image branch (src/image_model.py:192-226)."""
+        assert tgt_inputs is not None
+        device = self.encoder.embeddings.word_embeddings.weight.device
+        encoder_states, image_embeddings, src_pads = self._encode_text_and_image(src_inputs, src_pads, src_langs, batch)
+        tgt_inputs = tgt_inputs.to(device)
+        tgt_mask = tgt_inputs != pad_idx
+        langs = tgt_langs if tgt_langs is not None else src_langs
+        batch_lang = int(langs[0])
+        tgt_langs_t = self._lang_grid(langs, tgt_inputs.size(-1), device)
+        pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
+        rows = self._decode(encoder_states, src_pads, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=pos,
+                            proposals=proposals, pad_idx=pad_idx, img_states=image_embeddings)
+        return rows, tgt_inputs, tgt_mask, batch_lang
+
+    def _contrastive_loss(self, src_inputs, src_pads, src_langs, tgt_langs, batch, neg_samples, neg_mask):
+        """src/image_model.py:231-264: the captions, the negative samples and the image regions pooled to unit vectors, and the
+        image-to-text contrastive loss (one fused tail, ``_ContrastiveTailFn``).  Scalar fp32 loss."""
+        from .param_store import store_of
+        device = self.encoder.embeddings.word_embeddings.weight.device
+        encoder_states, image_embeddings, src_pads = self._encode_text_and_image(src_inputs, src_pads, src_langs, batch)
+        langs = tgt_langs if tgt_langs is not None else src_langs
+        neg_samples, neg_mask = neg_samples.to(device), neg_mask.to(device)
+        neg_langs = self._uniform_grid(neg_samples.size(0), neg_samples.size(-1), int(langs[0]), device)  # :235
+        neg_states = MassSeq2Seq.encode(self, neg_samples, neg_mask, neg_langs)[0]
+        anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
+        return _ContrastiveTailFn.apply(anchor, encoder_states, src_pads, neg_states, neg_mask, image_embeddings, self)
+
     def forward(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, pad_idx: int = 0,
                 tgt_positions=None, batch=None, neg_samples=None, neg_mask=None, proposals=None,
                 log_softmax: bool = False, **kwargs):
+        """``batch`` given (src/image_model.py:185-264): with ``neg_samples`` / ``neg_mask`` the scalar contrastive loss, else the
+        gated text + image branch -- the decoder runs over the text encoder states (key mask ``src_pads``) and again over the image
+        regions (no key mask), the two outputs are mixed by ``sigmoid(multimodal_attention_gate + 1e-7)``.
+
+        Deviations from the reference's text, both forced: the image embeddings are element 0 of what the image head returns (the
+        reference keeps the (grid, objects) tuple, :153, and fails); and ``tgt_langs``, which both branches read (:197, :235) but
+        the reference trainer never passes (src/train_image_mt.py:218-236), defaults to ``src_langs`` -- the masked caption is
+        recovered, and the negatives are written, in the captions' own language, as in the MASS step."""
         u = self._un
         batch, src_langs, tgt_langs, src_pads = u(batch), u(src_langs), u(tgt_langs), u(src_pads)
         src_inputs, tgt_positions, tgt_inputs, proposals = u(src_inputs), u(tgt_positions), u(tgt_inputs), u(proposals)
@@ -271,15 +387,27 @@ class ImageMassSeq2Seq(MassSeq2Seq):
             return MassSeq2Seq.forward(self, src_inputs=src_inputs, tgt_inputs=tgt_inputs, src_langs=src_langs,
                                        tgt_langs=tgt_langs, pad_idx=pad_idx, tgt_positions=tgt_positions,
                                        proposals=proposals, log_softmax=log_softmax)
-        raise NotImplementedError(
-            "ImageMassSeq2Seq image+text branch: the reference passes a tuple as encoder_states and cannot run "
-            "(src/image_model.py:153 vs :82, SURVEY a16); not part of the hot path")
+        if neg_samples is not None:
+            return self._contrastive_loss(src_inputs, src_pads, src_langs, tgt_langs, batch, u(neg_samples), u(neg_mask))
+        rows, _, _, batch_lang = self._multimodal_rows(src_inputs, src_pads, tgt_inputs, src_langs, tgt_langs, pad_idx,
+                                                       tgt_positions, batch, proposals)
+        return self._project(rows, batch_lang, log_softmax)
 
     def loss_fused(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None,
-                   pad_idx: int = 0, tgt_positions=None, batch=None, proposals=None, epsilon: float = 0.1, **kwargs):
+                   pad_idx: int = 0, tgt_positions=None, batch=None, proposals=None, epsilon: float = 0.1, neg_samples=None,
+                   neg_mask=None, **kwargs):
+        """(loss, ntokens).  With ``batch``: the gated text + image branch through the fused projection + loss, or, with
+        ``neg_samples``, the contrastive loss and 0 tokens (nothing is predicted, src/train_image_mt.py:274-276)."""
         u = self._un
-        if u(batch) is not None:
-            raise NotImplementedError("image+text branch is not on the hot path")
+        batch = u(batch)
+        if batch is not None:
+            if neg_samples is not None:
+                return self._contrastive_loss(u(src_inputs), u(src_pads), u(src_langs), u(tgt_langs), batch, u(neg_samples),
+                                              u(neg_mask)), 0
+            rows, tgt_inputs, tgt_mask, batch_lang = self._multimodal_rows(u(src_inputs), u(src_pads), u(tgt_inputs), u(src_langs),
+                                                                           u(tgt_langs), pad_idx, u(tgt_positions), batch,
+                                                                           u(proposals))
+            return self._loss_from_rows(rows, tgt_inputs, tgt_mask, batch_lang, epsilon)
         return MassSeq2Seq.loss_fused(self, u(src_inputs), u(tgt_inputs), u(src_langs), tgt_langs=u(tgt_langs),
                                       pad_idx=pad_idx, tgt_positions=u(tgt_positions), epsilon=epsilon,
                                       proposals=u(proposals))

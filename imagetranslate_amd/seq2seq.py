@@ -351,7 +351,7 @@ class Seq2Seq(nn.Module):
         return idx.to(torch.int32), tgt_inputs[:, 1:].reshape(-1)[idx]
 
     def _decode(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=None,
-                proposals=None, pad_idx=0, sel_idx=None, obj_states=None):
+                proposals=None, pad_idx=0, sel_idx=None, obj_states=None, img_states=None):
         decoder = self.decoder if not self.lang_dec else self.decoder[batch_lang]
         info = self.__dict__.get("_imt_grid_info", {}).get(id(tgt_langs_t))
         if info is not None:  # a cached uniform grid: use the (T-1)-wide one instead of a non-contiguous slice
@@ -361,6 +361,8 @@ class Seq2Seq(nn.Module):
         dec_kw = dict(input_ids=tgt_inputs[:, :-1], encoder_attention_mask=enc_mask, tgt_query_mask=tgt_mask[:, :-1],
                       position_ids=position_ids, token_type_ids=types)
         decoder_output = decoder(encoder_states=encoder_states, **dec_kw)
+        if img_states is not None:  # ImageMassSeq2Seq's text + image branch: second pass over the regions, gated (src/image_model.py:213-219)
+            decoder_output = self._mix_image_stream(decoder_output, img_states, batch_lang, **dec_kw)
         if obj_states is not None:  # ImageCaptioning's object stream, mixed in before attend_proposal (src/image_model.py:357-369)
             decoder_output = self._mix_object_stream(decoder_output, obj_states, batch_lang, **dec_kw)
         if self.use_proposals:

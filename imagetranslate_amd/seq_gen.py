@@ -17,6 +17,11 @@ What differs is HOW a step is computed:
     ``obj_decoder`` over the object rows (its own cross K/V with Tk = N, workspace and self cache; the slot table is
     shared) and its state is mixed into the image decoder's through the sigmoid gate before the projection
     (``:164-180``; no key mask, the object rows of a sentence serve all its beams like the image states).
+  * ``src_inputs=`` together with ``images=`` on an ``ImageMassSeq2Seq`` (``:105-106,180-188``): the text and the image are both
+    encoded (the image embeddings are element 0 of the image head's output; ``image_embed=``, when given as well, replaces that
+    encoding), and per step the decoder runs over the text states with the source mask and over the image states without one,
+    mixed through ``multimodal_attention_gate``.  With ``kv_cache`` the second pass is a second incremental decoder over the SAME
+    stack, built like the object stream's.  (``src_inputs=`` with ``image_embed=`` alone stays the text search, as in ``:94``.)
 Ties between equal scores (``torch.topk`` leaves them unspecified, and ``:194-196`` creates them on purpose) are
 broken towards the lowest flat index.  ``:216`` is taken as floor division (torch 1.4 semantics).
 """
@@ -119,27 +124,35 @@ class BeamDecoder(nn.Module):
 
         # ---- encoder side (once per search, :94-107)
         enc_mask = None
-        obj_fc = None
-        if src_inputs is not None and images is None:
+        obj_fc = img_states = None
+        if src_inputs is not None:
             src_mask = src_mask.to(device)
             src_langs_t = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1))
             encoder_states = model.encode(src_inputs, src_mask, src_langs_t)[0]
             enc_mask = src_mask.to(torch.uint8).contiguous()
-        elif src_inputs is None:
+            if images is not None:  # a source sentence AND an image (:105-106): the decoder also attends to the regions
+                if not hasattr(model, "multimodal_attention_gate"):
+                    raise ValueError("text + image beam search needs an ImageMassSeq2Seq (multimodal_attention_gate)")
+                if image_embed is not None:
+                    img_states = image_embed.to(device)
+                else:  # element 0 of the image head's output (the reference keeps the tuple and fails)
+                    img_states = model.image_model(images.to(device), model._imt_compute_dtype)[0]
+        else:
             if image_embed is None:
                 encoder_states, obj_fc = model.encode(images=images.to(device), **({"objects": objects} if objects is not None else {}))
             else:
                 encoder_states = image_embed.to(device)
                 if objects is not None and "obj_decoder" in model._modules:
                     obj_fc = model.image_model.objects_forward(objects, model._imt_compute_dtype)
-        else:
-            raise NotImplementedError(
-                "image+text beam search: the reference's multimodal encode cannot run (SURVEY a16)")
         dtype = model._imt_compute_dtype
         encoder_states = encoder_states.to(dtype).contiguous()
         Tk = encoder_states.size(1)
         if obj_fc is not None:
             obj_fc = obj_fc.to(dtype).contiguous()
+        if img_states is not None:
+            if img_states.size(0) != batch_size:
+                raise ValueError("text + image beam search: %d images for %d sentences" % (img_states.size(0), batch_size))
+            img_states = img_states.to(dtype).contiguous()
 
         eos = model.text_processor.sep_token_id()
         V = model.config.vocab_size
@@ -177,6 +190,12 @@ class BeamDecoder(nn.Module):
         if obj_fc is not None:
             obj_decoder = model.obj_decoder if not model.lang_dec else model.obj_decoder[batch_lang]
             go = store.offset(model.multistream_attention_gate)
+            gate = flat[go:go + model.config.hidden_size]
+        elif img_states is not None:
+            # the second stream is the SAME decoder over the image regions, no key mask (:184-188); from here on it is handled
+            # like the object stream: `obj_fc` = the second stream's encoder side, `obj_decoder` the stack that reads it
+            obj_decoder, obj_fc = decoder, img_states
+            go = store.offset(model.multimodal_attention_gate)
             gate = flat[go:go + model.config.hidden_size]
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         lib = L.load()
@@ -251,7 +270,7 @@ class BeamDecoder(nn.Module):
             inc_obj.check()
         if inc is not None:
             inc.check()
-        if obj_fc is not None:
+        if obj_fc is not None and img_states is None:
             model.image_model.check_object_labels(wait=True)  # device labels: the search synchronises here anyway   # raises if a one-launch decoder step was abandoned (bounded waits); one sync, the outputs are read next anyway
         if n_cols == 1:   # no step ran (max_len <= 1, or beam 1 with every first token EOS): one row per sentence
             outputs = st.hist[st.cur][:B, :1]

@@ -3,7 +3,9 @@
 clipping + inverse-sqrt Adam, dev-set loss, best-checkpoint saving, one process per GPU under torch.distributed.
 Round 3 adds the back-translation phase (``--fstep`` / ``--langs`` / ``--bt-beam``, src/train_image_mt.py:108-198,509-533): after
 ``--step`` ordinary steps the optimizer schedule is reset and every monolingual batch is translated by the model itself (KV-cached
-beam search, no gradient) and trained on as (translation -> original).  What the reference trainer does around the step that needs
+beam search, no gradient) and trained on as (translation -> original).  ``--image DIR`` with the caption file of ``--train`` adds
+image-caption batches (``:202-237``): per batch ``--mmode`` picks the masked-caption step (the gated text + image branch) or the
+contrastive step; back-translation over image batches is not built and refused.  What the reference trainer does around the step that needs
 absent packages (apex, sacrebleu, the torchvision image pipeline) is left out; the model step itself is the HIP path."""
 import datetime
 import math
@@ -37,6 +39,13 @@ class ImageMTTrainer:
         # MASS span / replacement draws: a generator of this rank's own, so that the ranks' batch ORDER (drawn from a
         # generator every rank seeds identically, below) never depends on how many MASS batches a rank has seen
         self._mass_rng = random.Random((seed + 1) * 7919 + rank)
+        # image batches (--mmode): the mixed mode's coin and the masked step's mask_prob ~ U(mask_prob, 1) come from a
+        # generator of their own, so that the MASS draws above do not depend on how many image batches a rank has seen
+        self.mm_mode = kwargs.get("mm_mode", "mixed")
+        if self.mm_mode not in ("mixed", "masked", "contrastive"):
+            raise ValueError("--mmode must be mixed, masked or contrastive, got %r" % (self.mm_mode,))
+        self._img_rng = random.Random((seed + 2) * 104729 + rank)
+        self.image_steps, self.last_image_step = 0, None  # image batches consumed; (kind, loss) of the last one
         self.generator = None  # BeamDecoder of the back-translation phase (built on first use)
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
@@ -71,6 +80,36 @@ class ImageMTTrainer:
         loss.backward()
         scale = self.sync.finish() if self.sync is not None else 1.0
         self._finish_micro_step(loss, accum, scale)
+        return loss.detach(), int(ntokens)
+
+    # one image-caption batch (src/train_image_mt.py:202-237): --mmode picks the masked-caption step (the gated text + image
+    # branch) or the contrastive step; "mixed" flips a seeded coin (:207)
+    def image_step(self, batch, accum: int = 1):
+        batch = {k: (v[0] if isinstance(v, list) else v) for k, v in batch.items()}
+        tp = self.model.text_processor
+        if self.sync is not None:
+            # the gradient exchange is launched layer by layer as the decoder's backward finishes, and the gated branch runs
+            # that backward twice: a bucket would leave before the second pass has added to it
+            raise NotImplementedError("image batches under data parallelism are not built (one process, one GPU)")
+        masked_step = self.mm_mode == "masked" or (self.mm_mode == "mixed" and self._img_rng.random() <= .5)
+        if masked_step:
+            # "for image masking, we are allowed to mask more than mask_prob" (:212-213)
+            mask_prob = min(self._img_rng.uniform(self.mask_prob, 1.0), 1.0 - 1e-6)
+            src = batch["captions"].cuda()  # a device copy: the dataset's tensor is never modified
+            masked = mass_mask_device(mask_prob, batch["pad_idx"], src, tp, seed=self._img_rng.getrandbits(62))
+            loss, ntokens = self.model.loss_fused(src_inputs=masked["src_text"], tgt_inputs=masked["to_recover"],
+                                                  tgt_positions=masked["positions"], src_pads=batch["caption_mask"],
+                                                  pad_idx=tp.pad_token_id(), src_langs=batch["langs"], tgt_langs=batch["langs"],
+                                                  batch=batch)
+        else:  # "nothing to predict" (:274-276): the loss is back-propagated as it is and counts no tokens
+            loss, ntokens = self.model.loss_fused(src_inputs=batch["captions"], src_pads=batch["caption_mask"],
+                                                  neg_samples=batch["neg"], neg_mask=batch["neg_mask"],
+                                                  pad_idx=tp.pad_token_id(), src_langs=batch["langs"], tgt_langs=batch["langs"],
+                                                  batch=batch)
+        loss.backward()
+        self._finish_micro_step(loss, accum, 1.0)
+        self.image_steps += 1
+        self.last_image_step = ("masked" if masked_step else "contrastive", loss.detach())
         return loss.detach(), int(ntokens)
 
     @staticmethod
@@ -127,12 +166,12 @@ class ImageMTTrainer:
         self.model.train()
         return total / max(count, 1)
 
-    def epoch_order(self, n_mt: int, n_mass: int):
+    def epoch_order(self, n_mt: int, n_mass: int, n_img: int = 0):
         """This rank's share of the epoch's batches: the same shuffle on every rank (a generator seeded with seed + epoch,
         nothing else draws from it), padded by wrapping around to a multiple of the world size like torch's
         DistributedSampler (src/train_image_mt.py:586-589), then strided -- every rank runs the SAME number of steps, so
         no rank is left waiting in an all-reduce when an epoch ends."""
-        order = [("mt", i) for i in range(n_mt)] + [("mass", i) for i in range(n_mass)]
+        order = [("mt", i) for i in range(n_mt)] + [("mass", i) for i in range(n_mass)] + [("img", i) for i in range(n_img)]
         random.Random(self.seed + self.epoch).shuffle(order)
         if self.world_size > 1 and order:
             short = (-len(order)) % self.world_size
@@ -141,8 +180,11 @@ class ImageMTTrainer:
 
     def train_epoch(self, mt_data=None, mass_data=None, dev_data=None, step: int = 0, max_step: int = 10 ** 9,
                     save_path: str = None, log_every: int = 50, eval_every: int = 500, accum: int = 1, fine_tune: bool = False,
-                    lang_directions=None):
-        order = self.epoch_order(len(mt_data or []), len(mass_data or []))
+                    lang_directions=None, img_data=None):
+        if fine_tune and img_data is not None and len(img_data) > 0:
+            raise NotImplementedError("back-translation over image batches (src/train_image_mt.py:108-198 with is_img_batch) "
+                                      "is not built")
+        order = self.epoch_order(len(mt_data or []), len(mass_data or []), len(img_data) if img_data is not None else 0)
         self.epoch += 1
         meter, t0 = LossMeter(), datetime.datetime.now()
         for kind, i in order:
@@ -151,6 +193,8 @@ class ImageMTTrainer:
             try:
                 if kind == "mt":
                     loss, n = self.mt_step(mt_data[i], accum)
+                elif kind == "img":
+                    loss, n = self.image_step(img_data[i], accum)
                 elif fine_tune:  # back-translation phase: the monolingual batches are translated and trained on (:108-198)
                     loss, n = self.bt_step(mass_data[i], lang_directions, accum)
                 else:
@@ -235,12 +279,37 @@ def reject_off_path(options, lm_supported: bool = False):
                                       "src/train_image_mt.py:319-321,449-462); use --pretrained to continue from saved weights" % flag)
 
 
+def load_image_data(options, tp):
+    """--image DIR with the caption file of --train (src/train_image_mt.py:468-473, :636-645): the image-caption batches, or
+    None without --image.  DIR must hold a readable features.pt (dataset.RegionFeatures); negative samples are drawn unless
+    every image step is a masked one."""
+    if not options.image_dir:
+        return None
+    feats = os.path.join(options.image_dir, "features.pt")
+    if not os.path.isfile(feats) or not os.access(feats, os.R_OK):
+        raise FileNotFoundError("--image %s: no readable features.pt (pre-extracted region features, see dataset.RegionFeatures)"
+                                % options.image_dir)
+    if not options.train_path:
+        raise ValueError("--image needs the caption file (--train)")
+    return dataset.ImageCaptionDataset(root_img_dir=options.image_dir, data_bin_file=options.train_path,
+                                       max_capacity=int(options.img_capacity), text_processor=tp,
+                                       max_img_per_batch=int(options.max_image), use_neg_samples=options.mm_mode != "masked",
+                                       neg_seed=options.seed)
+
+
 def train(options):
     reject_off_path(options)
+    if getattr(options, "image_dir", "") and len([l for l in (options.bt_langs or "").split(",") if l.strip()]) >= 2 \
+            and options.finetune_step > 0:
+        raise NotImplementedError("--image with --langs / --fstep: back-translation over image batches (src/train_image_mt.py:108-198 "
+                                  "with is_img_batch) is not built; give --fstep 0 or drop --langs")
     rank, world = init_distributed()
     random.seed(options.seed)
     torch.manual_seed(options.seed)
     tp = TextProcessor(options.tokenizer_path)
+    img_train = load_image_data(options, tp)  # before the model is built: a missing features.pt fails at once
+    if img_train is not None and world > 1:
+        raise NotImplementedError("--image under data parallelism is not built (ImageMTTrainer.image_step)")
     if options.pretrained_path:
         model = ImageMassSeq2Seq.load(ImageMassSeq2Seq, options.pretrained_path, tok_dir=options.tokenizer_path)
     else:
@@ -254,7 +323,7 @@ def train(options):
     # (GradSync broadcasts rank 0's parameters, like the DDP constructor at src/train_image_mt.py:73)
     trainer = ImageMTTrainer(model, mask_prob=options.mask_prob, clip=options.clip, optimizer=optimizer, rank=rank, world_size=world,
                              seed=options.seed, bt_beam_width=options.bt_beam_width, max_len_a=options.max_len_a,
-                             max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio)
+                             max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio, mm_mode=options.mm_mode)
     pad = tp.pad_token_id()
     mk = lambda cls, path, **kw: cls(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad,
                                      max_seq_len=options.max_seq_len, ngpu=1, **kw, **path)
@@ -269,14 +338,15 @@ def train(options):
         if pth.strip():
             mt_dev = (mt_dev or []) + mk(dataset.MTDataset, dict(batch_pickle_dir=pth.strip())).batches
     if rank == 0:
-        print("MT batches", len(mt_train), "MASS batches", len(mass_train), "dev batches", len(mt_dev or []), flush=True)
+        print("MT batches", len(mt_train), "MASS batches", len(mass_train), "image batches", len(img_train or []),
+              "dev batches", len(mt_dev or []), flush=True)
     step = 0
     for epoch in range(options.num_epochs):
         if step >= options.step:
             break
         step = trainer.train_epoch(mt_data=mt_train, mass_data=mass_train, dev_data=mt_dev, step=step, max_step=options.step,
                                    save_path=options.model_path, log_every=options.log_steps, eval_every=options.eval_steps,
-                                   accum=options.accum)
+                                   accum=options.accum, img_data=img_train)
     # back-translation phase (src/train_image_mt.py:509-533): optimizer schedule reset, then --fstep more steps in which the
     # monolingual batches are back-translated.  The reference's flag default is 125000 steps; here the phase runs only when a
     # language pair is given (--langs), which is what makes it well-defined.

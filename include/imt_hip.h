@@ -403,6 +403,39 @@ int imt_obj_embed_grad(int dtype, const int64_t* labels, const void* dx, int64_t
 int imt_gated_mix_bwd(int dtype, const void* dy, const void* a, const void* b, const void* gate, void* da, void* db,
                       float* dgate, float* partial_ws, int64_t rows, int d, void* stream);
 
+/* ------------------------------------------------------------------ contrastive tail of ImageMassSeq2Seq
+ * src/image_model.py:240-263.  Three tensors (caption states, negative-sample states, image regions) are pooled to unit vectors
+ * by a learned one-vector attention, then the images are scored against every text vector.
+ * imt_attn_pool_fwd (:240-243 / :245-248 / :252-253 and the normalisation :255-258), one workgroup per sentence of
+ *   x [rows, S, d] (`dtype`, contiguous): score_s = x_s . w + b (w [d], b [1] in `dtype`); where mask ([rows, S] bytes, NULL = no
+ *   mask) is 0 the score is set to exactly -10000 (masked_fill: an all-masked sentence pools to the plain average);
+ *   p = softmax_s(score); v = sum_s p_s x_s; u = v / (|v|_2 + 1e-4).  Outputs, all fp32: u [rows, d], and for the backward
+ *   probs [rows, S] and norm [rows] = |v|_2.  Softmax statistics and every sum are fp32.
+ * imt_attn_pool_plan: how often a sentence is read from memory -- 1: it stays in LDS after the score pass (its S * d elements
+ *   fit beside the per-position arrays in IMT_POOL_LDS_BYTES), 2: the weighted sum reads it a second time.  Never more.  The
+ *   backward follows the same plan.  IMT_ERR_BAD_ARG for a shape the kernels do not take (below).
+ * imt_attn_pool_bwd: du [rows, d] fp32 (times du_scale[0] when that device scalar is given) -> dx [rows, S, d] in `dtype`
+ *   (OVERWRITTEN), and dw [d] / db [1] ACCUMULATED into fp32 (the flat gradient buffer).  Per-sentence partial sums go to ws
+ *   (rows * d + rows floats) and a second launch adds them in sentence order: no float atomics, two identical calls give
+ *   bit-identical dw / db.
+ * imt_contrastive (:260-263): img [B, d], txt [N, d] fp32 unit vectors, txt row i < B belonging to image i;
+ *   C = img txt^T, loss[0] = sum_i (log(sum_j exp C_ij + 1e-4) - (C_ii + 1e-4)) / B, and d loss / d img, d loss / d txt
+ *   (OVERWRITTEN, fp32).  ws: B * N + B floats.  Fixed summation order throughout.
+ * Refused before any launch with IMT_ERR_BAD_ARG: a NULL tensor, S < 1, S > IMT_POOL_MAX_S, d not a multiple of 4 (the vector
+ * width) or above IMT_POOL_MAX_D, N < B, N > IMT_CONTRASTIVE_MAX_N. */
+#define IMT_POOL_MAX_S 4096
+#define IMT_POOL_MAX_D 1024
+#define IMT_POOL_LDS_BYTES 65536
+#define IMT_CONTRASTIVE_MAX_N 4096
+int imt_attn_pool_plan(int dtype, int S, int d);
+int imt_attn_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, float* u, float* probs,
+                      float* norm, int64_t rows, int S, int d, void* stream);
+int imt_attn_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* u, const float* probs,
+                      const float* norm, const float* du, const float* du_scale, void* dx, float* dw, float* db, float* ws,
+                      int64_t rows, int S, int d, void* stream);
+int imt_contrastive(const float* img, const float* txt, float* loss, float* d_img, float* d_txt, float* ws, int B, int N, int d,
+                    void* stream);
+
 
 /* ------------------------------------------------------------------ whole encoder / decoder stacks
  * The host-side runtime that chains the kernels above for BertEncoderModel.forward (src/bert_seq2seq.py:103-144)
