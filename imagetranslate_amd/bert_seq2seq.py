@@ -164,6 +164,15 @@ def _attn_block(store, att: BertAttention, split_kv: bool = False):
     return (b, kv_w, kv_b) if split_kv else b
 
 
+def dropout_seed(module, active: bool, salt: int = 0) -> int:
+    """Dropout seed of one forward (the backward regenerates the same masks from it): 0 when dropout is not ``active``,
+    the module's pinned ``_imt_dropout_seed`` (tests) + ``salt``, else one draw from torch's generator."""
+    if not active:
+        return 0
+    fixed = getattr(module, "_imt_dropout_seed", None)
+    return int(fixed) + salt if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
 class _Pretrained(nn.Module):
     """Shared behaviour of the two stacks (stands in for HF BertPreTrainedModel)."""
 
@@ -269,12 +278,9 @@ class _Pretrained(nn.Module):
             if m.dtype == torch.bool:
                 return m.contiguous().view(torch.uint8)
             return m.to(dtype=torch.uint8).contiguous()
-        anchor = store.anchor() if torch.is_grad_enabled() else None
-        # dropout seed of this forward (the backward regenerates the same masks from it); tests pin it
-        fixed = getattr(self, "_imt_dropout_seed", None)
-        seed = (int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if self.training else 0
-        return _StackFn.apply(anchor, enc_states, self, store, dtype, ids, type_ids, pos_ids, u8(key_mask), u8(query_mask),
-                              u8(mask3d), bool(causal), u8(enc_mask), bool(self.training), seed)
+        seed = dropout_seed(self, self.training)
+        return _StackFn.apply(store.anchor_if_grad(), enc_states, self, store, dtype, ids, type_ids, pos_ids, u8(key_mask),
+                              u8(query_mask), u8(mask3d), bool(causal), u8(enc_mask), bool(self.training), seed)
 
 
 class _StackFn(torch.autograd.Function):
@@ -311,7 +317,7 @@ class _StackFn(torch.autograd.Function):
         # later): lets an optimizer step that is still running on its side stream finish the other segments meanwhile
         lo_key = ("_imt_params_lo", store.layout_version)
         if mod.__dict__.get("_imt_params_lo_key") != lo_key:
-            mod.__dict__["_imt_params_lo"] = min(store.offset(p) for p in mod.parameters())
+            mod.__dict__["_imt_params_lo"] = store.span(mod.parameters())[0]
             mod.__dict__["_imt_params_lo_key"] = lo_key
         ev_arr = None
         handles = store.site_events(mod) if not desc.is_decoder else None
@@ -350,8 +356,7 @@ class _StackFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         store, mod, dtype, io = ctx.store, ctx.mod, ctx.dtype, ctx.io
-        if store.layout_version != ctx.layout_version:
-            raise L.ImtError("parameter layout changed between forward and backward")
+        store.check_layout(ctx.layout_version, "stack")
         desc, _keep = mod._desc(store, dtype)
         desc.params = ctx.keep[-1].data_ptr()
         desc.grads = store.grad.data_ptr()
@@ -396,33 +401,23 @@ class _LinearFn(torch.autograd.Function):
         store = store_of(holder).ensure()
         if id(weight) not in store.index:
             raise L.ImtError("parameter is not part of its model's flat store")
-        dtype = x.dtype
-        flat = store.params_for(dtype)
-        wo = store.offset(weight)
-        N, K = weight.shape
-        w = flat[wo:wo + N * K].view(N, K)
-        b = None
-        if bias is not None:
-            bo = store.offset(bias)
-            b = flat[bo:bo + N]
+        w, b = store.views(x.dtype, weight, bias)
         x = x.contiguous()
         y = O.gemm(x, w, O.IMT_NT, bias=b)
-        ctx.store, ctx.wo, ctx.bo, ctx.shape = store, wo, (store.offset(bias) if bias is not None else -1), (N, K)
+        ctx.store, ctx.params, ctx.layout_version = store, (weight, bias), store.layout_version
         ctx.save_for_backward(x, w)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        store = ctx.store
-        N, K = ctx.shape
+        store, (weight, bias) = ctx.store, ctx.params
+        store.check_layout(ctx.layout_version, "linear")
         dy = O.rows16(dy.to(x.dtype))  # [M, out_features]: rows stay 16-byte aligned for any vocabulary size
-        M = dy.shape[0]
         dx = O.gemm(dy, w, O.IMT_NN) if ctx.needs_input_grad[0] else None
-        gw = store.grad[ctx.wo:ctx.wo + N * K].view(N, K)
-        sk = max(1, min(M // 256, 512 // max(1, ((N + 127) // 128) * ((K + 127) // 128))))
-        O.gemm(dy, x, O.IMT_TN, out=gw, accumulate=(sk == 1), split_k=sk,
-               a_colsum=store.grad[ctx.bo:ctx.bo + N] if ctx.bo >= 0 else None)
+        sk = O.dw_split_k(dy.shape[0], *weight.shape, 256)
+        O.gemm(dy, x, O.IMT_TN, out=store.grad_view(weight), accumulate=(sk == 1), split_k=sk,
+               a_colsum=store.grad_view(bias) if bias is not None else None)
         store.attach_grad_views()
         return dx, None, None, None
 

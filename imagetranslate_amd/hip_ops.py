@@ -121,6 +121,12 @@ def splitk_workspace(device):
     return ws
 
 
+def dw_split_k(rows: int, N: int, K: int, rows_per_split: int) -> int:
+    """K-splits of a weight-gradient TN GEMM ``dy^T x -> [N, K]`` over ``rows`` rows: one per ``rows_per_split`` rows, as
+    long as the 128 x 128 output tiles times the splits stay within 512 workgroups."""
+    return max(1, min(rows // rows_per_split, 512 // max(1, ((N + 127) // 128) * ((K + 127) // 128))))
+
+
 def gemm_grouped_tn(problems):
     """problems: list of dicts(A=dy[K,M], B=x[K,N], out=fp32 grad [M,N], a_colsum=optional) -> one launch."""
     arr = (L.GemmArgs * len(problems))()

@@ -14,8 +14,9 @@ import torch
 import torch.nn as nn
 
 from . import hip_ops as O
-from .bert_seq2seq import BertDecoderModel, _Pretrained
+from .bert_seq2seq import BertDecoderModel, _Pretrained, dropout_seed
 from .mass_seq2seq import MassSeq2Seq
+from .param_store import store_of
 from .seq2seq import future_mask  # noqa: F401
 
 
@@ -28,16 +29,9 @@ class _ImageHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, x, head, dtype, p, seed):
-        from .param_store import store_of
         store = store_of(head).ensure()
-        flat = store.params_for(dtype)
-        w_p, loc_p = head.fc.weight, head.location_embedding.weight
-        d, C = w_p.shape
-        R = loc_p.shape[0]
-        wo, lo = store.offset(w_p), store.offset(loc_p)
-        w = flat[wo:wo + d * C].view(d, C)
-        loc = flat[lo:lo + R * d].view(R, d)
-        B = x.shape[0]
+        w, loc = store.views(dtype, head.fc.weight, head.location_embedding.weight)
+        (d, C), R, B = w.shape, loc.shape[0], x.shape[0]
         if x.shape[1] != R:
             raise ValueError("image head: %d regions given, location_embedding has %d" % (x.shape[1], R))
         if x.dtype not in (torch.float32, torch.bfloat16):
@@ -45,20 +39,22 @@ class _ImageHeadFn(torch.autograd.Function):
         xd = O.add_rows_dropout(x.reshape(B * R, C).contiguous(), None, out_dtype=dtype, dropout_p=p, dropout_seed=seed)
         y = O.gemm(xd, w, O.IMT_NT, splitk_ws=O.splitk_workspace(xd.device))
         out = O.add_rows_dropout(y, loc, dropout_p=p, dropout_seed=seed + 1)
-        ctx.store, ctx.wo, ctx.lo, ctx.dims, ctx.p, ctx.seed = store, wo, lo, (B, R, d, C), p, seed
+        ctx.store, ctx.head, ctx.layout_version = store, head, store.layout_version
+        ctx.dims, ctx.p, ctx.seed = (B, R, d, C), p, seed
         ctx.save_for_backward(xd)
         return out.view(B, R, d)
 
     @staticmethod
     def backward(ctx, dout):
         (xd,) = ctx.saved_tensors
-        store = ctx.store
+        store, head = ctx.store, ctx.head
+        store.check_layout(ctx.layout_version, "image head")
         B, R, d, C = ctx.dims
         dy = O.add_rows_dropout(dout.to(xd.dtype).reshape(B * R, d).contiguous(), None, dropout_p=ctx.p, dropout_seed=ctx.seed + 1)
-        O.colsum(dy.view(B, R * d), store.grad[ctx.lo:ctx.lo + R * d])              # d(location_embedding) += sum over images
-        gw = store.grad[ctx.wo:ctx.wo + d * C].view(d, C)
-        sk = max(1, min((B * R) // 256, 512 // max(1, ((d + 127) // 128) * ((C + 127) // 128))))
-        O.gemm(dy, xd, O.IMT_TN, out=gw, accumulate=(sk == 1), split_k=sk)           # d(fc.weight) += dy^T x
+        # d(location_embedding) += sum over images; d(fc.weight) += dy^T x
+        O.colsum(dy.view(B, R * d), store.grad_view(head.location_embedding.weight).view(-1))
+        sk = O.dw_split_k(B * R, d, C, 256)
+        O.gemm(dy, xd, O.IMT_TN, out=store.grad_view(head.fc.weight), accumulate=(sk == 1), split_k=sk)
         store.attach_grad_views()
         return None, None, None, None, None, None
 
@@ -86,32 +82,30 @@ class _ObjectHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, feats, boxes, labels, head, dtype, p, seed, status):
-        from .param_store import store_of
         store = store_of(head).ensure()
-        flat = store.params_for(dtype)
-        w_p, e_p = head.object_feat_fc.weight, head.object_embedding.weight
-        d, K = w_p.shape
-        wo, eo = store.offset(w_p), store.offset(e_p)
+        w, emb = store.views(dtype, head.object_feat_fc.weight, head.object_embedding.weight)
+        d, K = w.shape
         B, N = labels.shape
         x, w_pad = O.obj_rows(labels.reshape(-1).contiguous(), feats.reshape(B * N, -1).contiguous(),
-                              boxes.reshape(B * N, 4).contiguous(), flat[eo:eo + e_p.numel()], flat[wo:wo + d * K], d, dtype,
-                              status=status)
+                              boxes.reshape(B * N, 4).contiguous(), emb.view(-1), w.view(-1), d, dtype, status=status)
         y = O.relu_dropout_(O.gemm(x, w_pad, O.IMT_NT, splitk_ws=O.splitk_workspace(x.device)), p, seed)
-        ctx.store, ctx.wo, ctx.eo, ctx.dims, ctx.p, ctx.seed = store, wo, eo, (B, N, d, K), p, seed
+        ctx.store, ctx.head, ctx.layout_version = store, head, store.layout_version
+        ctx.dims, ctx.p, ctx.seed = (B, N, d, K), p, seed
         ctx.save_for_backward(x, w_pad, y, labels)
         return y.view(B, N, d)
 
     @staticmethod
     def backward(ctx, dout):
         x, w_pad, y, labels = ctx.saved_tensors
-        store = ctx.store
+        store, head = ctx.store, ctx.head
+        store.check_layout(ctx.layout_version, "object head")
         B, N, d, K = ctx.dims
         dz = O.relu_dropout_bwd(dout.to(y.dtype).reshape(B * N, d).contiguous(), y, ctx.p, ctx.seed)
         dw = torch.empty(w_pad.shape, device=x.device, dtype=torch.float32)
         O.gemm(dz, x, O.IMT_TN, out=dw)                                                   # dz^T X  [d, Kp]
-        O.obj_fold_w(dw, store.grad[ctx.wo:ctx.wo + d * K], d)                             # d(object_feat_fc.weight) +=
+        O.obj_fold_w(dw, store.grad_view(head.object_feat_fc.weight).view(-1), d)         # d(object_feat_fc.weight) +=
         dxe = O.gemm(dz, w_pad[:, :d], O.IMT_NN, splitk_ws=O.splitk_workspace(x.device))  # d(embedding rows) [R, d]
-        O.obj_embed_grad(labels.reshape(-1).contiguous(), dxe, store.grad[ctx.eo:ctx.eo + O.OBJ_LABELS * d])
+        O.obj_embed_grad(labels.reshape(-1).contiguous(), dxe, store.grad_view(head.object_embedding.weight).view(-1))
         store.attach_grad_views()
         return None, None, None, None, None, None, None, None, None
 
@@ -122,13 +116,11 @@ class _GatedMixFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, a, b, model, gate_param):
-        from .param_store import store_of
         store = store_of(model).ensure()
         d = a.shape[-1]
-        go = store.offset(gate_param)
-        gate = store.params_for(a.dtype)[go:go + d]
+        gate = store.views(a.dtype, gate_param)[0].view(-1)
         a2, b2 = a.reshape(-1, d).contiguous(), b.to(a.dtype).reshape(-1, d).contiguous()
-        ctx.store, ctx.go, ctx.shape = store, go, a.shape
+        ctx.store, ctx.gate_param, ctx.layout_version, ctx.shape = store, gate_param, store.layout_version, a.shape
         ctx.save_for_backward(a2, b2, gate)
         return O.gated_mix(a2, b2, gate).view(a.shape)
 
@@ -136,8 +128,9 @@ class _GatedMixFn(torch.autograd.Function):
     def backward(ctx, dout):
         a2, b2, gate = ctx.saved_tensors
         d = a2.shape[1]
+        ctx.store.check_layout(ctx.layout_version, "gated mix")
         da, db = O.gated_mix_bwd(dout.to(a2.dtype).reshape(-1, d).contiguous(), a2, b2, gate,
-                                 ctx.store.grad[ctx.go:ctx.go + d])
+                                 ctx.store.grad_view(ctx.gate_param).view(-1))
         ctx.store.attach_grad_views()
         return None, da.view(ctx.shape), db.view(ctx.shape), None, None
 
@@ -152,24 +145,22 @@ class _ContrastiveTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, enc_states, src_mask, neg_states, neg_mask, img_states, model):
-        from .param_store import store_of
         store = store_of(model).ensure()
         dtype = enc_states.dtype
-        flat = store.params_for(dtype)
         d = enc_states.shape[-1]
         B, Nn = enc_states.shape[0], neg_states.shape[0]
         if img_states.shape[0] != B:
             raise ValueError("contrastive loss: %d images for %d captions" % (img_states.shape[0], B))
-        offs = [store.offset(p) for p in (model.encoder_attention_w.weight, model.encoder_attention_w.bias,
-                                          model.image_attention_w.weight, model.image_attention_w.bias)]
-        we, be, wi, bi = flat[offs[0]:offs[0] + d], flat[offs[1]:offs[1] + 1], flat[offs[2]:offs[2] + d], flat[offs[3]:offs[3] + 1]
+        we, be, wi, bi = store.views(dtype, model.encoder_attention_w.weight, model.encoder_attention_w.bias,
+                                     model.image_attention_w.weight, model.image_attention_w.bias)
+        we, wi = we.view(-1), wi.view(-1)  # nn.Linear(d, 1) weights are [1, d]
         enc, neg, img = enc_states.contiguous(), neg_states.to(dtype).contiguous(), img_states.to(dtype).contiguous()
         txt = torch.empty((B + Nn, d), device=enc.device, dtype=torch.float32)
         _, p_e, n_e = O.attn_pool_fwd(enc, we, be, src_mask, out=txt[:B])
         _, p_n, n_n = O.attn_pool_fwd(neg, we, be, neg_mask, out=txt[B:])
         img_u, p_i, n_i = O.attn_pool_fwd(img, wi, bi, None)
         loss, d_img, d_txt = O.contrastive(img_u, txt)
-        ctx.store, ctx.offs, ctx.dims = store, offs, (B, Nn, d)
+        ctx.store, ctx.model, ctx.layout_version, ctx.dims = store, model, store.layout_version, (B, Nn, d)
         ctx.masks = (src_mask, neg_mask)
         ctx.save_for_backward(enc, neg, img, we, wi, txt, img_u, p_e, n_e, p_n, n_n, p_i, n_i, d_img, d_txt)
         return loss.view(())
@@ -178,21 +169,21 @@ class _ContrastiveTailFn(torch.autograd.Function):
     def backward(ctx, g):
         enc, neg, img, we, wi, txt, img_u, p_e, n_e, p_n, n_n, p_i, n_i, d_img, d_txt = ctx.saved_tensors
         B, Nn, d = ctx.dims
-        grad, offs = ctx.store.grad, ctx.offs
+        store, model = ctx.store, ctx.model
+        store.check_layout(ctx.layout_version, "contrastive tail")
         g = g.detach().to(torch.float32).reshape(1).contiguous()
-        gw_e, gb_e = grad[offs[0]:offs[0] + d], grad[offs[1]:offs[1] + 1]
+        gw_e, gb_e = store.grad_view(model.encoder_attention_w.weight).view(-1), store.grad_view(model.encoder_attention_w.bias)
+        gw_i, gb_i = store.grad_view(model.image_attention_w.weight).view(-1), store.grad_view(model.image_attention_w.bias)
         d_enc = O.attn_pool_bwd(enc, we, ctx.masks[0], txt[:B], p_e, n_e, d_txt[:B], gw_e, gb_e, du_scale=g)
         d_neg = O.attn_pool_bwd(neg, we, ctx.masks[1], txt[B:], p_n, n_n, d_txt[B:], gw_e, gb_e, du_scale=g)
-        d_im = O.attn_pool_bwd(img, wi, None, img_u, p_i, n_i, d_img, grad[offs[2]:offs[2] + d], grad[offs[3]:offs[3] + 1], du_scale=g)
-        ctx.store.attach_grad_views()
+        d_im = O.attn_pool_bwd(img, wi, None, img_u, p_i, n_i, d_img, gw_i, gb_i, du_scale=g)
+        store.attach_grad_views()
         return None, d_enc, None, d_neg, None, d_im, None
 
 
 def gated_mix(model, gate_param, a, b):
     """Autograd-aware sigmoid-gated mix of two [..., d] streams with a gate parameter of ``model``'s flat store."""
-    from .param_store import store_of
-    anchor = store_of(model).ensure().anchor() if torch.is_grad_enabled() else None
-    return _GatedMixFn.apply(anchor, a, b, model, gate_param)
+    return _GatedMixFn.apply(store_of(model).ensure().anchor_if_grad(), a, b, model, gate_param)
 
 
 class ImageHead(nn.Module):
@@ -208,13 +199,10 @@ class ImageHead(nn.Module):
 
     def forward(self, grid_hidden, compute_dtype=torch.float32):
         """grid_hidden: region features [B, regions, feat_dim] (the reference's x8.view().permute(), :35-36)."""
-        from .param_store import store_of
         x = grid_hidden.to(self.fc.weight.device)
         p = float(self.dropout) if self.training else 0.0
-        fixed = getattr(self, "_imt_dropout_seed", None)
-        seed = (int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if p > 0 else 0
-        anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
-        return _ImageHeadFn.apply(anchor, x, self, compute_dtype, p, seed), None
+        seed = dropout_seed(self, p > 0)
+        return _ImageHeadFn.apply(store_of(self).ensure().anchor_if_grad(), x, self, compute_dtype, p, seed), None
 
     def add_object_head(self, embed_dim: int):
         """object_feat_fc (Linear(d + 1031 -> d), no bias) and object_embedding (91 labels), src/image_model.py:110-116.
@@ -228,7 +216,6 @@ class ImageHead(nn.Module):
         detections.  Labels must lie in [0, 91).  Host labels are checked here; for device labels imt_obj_rows zeroes an
         out-of-range row and raises a status word that is read back without waiting (``check_object_labels``): the error
         surfaces at the next call once that step has run, or at once with ``wait=True``."""
-        from .param_store import store_of
         if not _objects_present(objects) or getattr(self, "object_feat_fc", None) is None:
             return None
         dev = self.object_feat_fc.weight.device
@@ -249,9 +236,8 @@ class ImageHead(nn.Module):
             feats = feats.float()
         boxes = objects["boxes"].to(device=dev, dtype=torch.float32)
         p = float(self.dropout) if self.training else 0.0
-        fixed = getattr(self, "_imt_dropout_seed", None)
-        seed = (int(fixed) + 2 if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if p > 0 else 0
-        anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
+        seed = dropout_seed(self, p > 0, salt=2)
+        anchor = store_of(self).ensure().anchor_if_grad()
         out = _ObjectHeadFn.apply(anchor, feats, boxes, labels, self, compute_dtype, p, seed, status)
         if status is not None:  # cumulative device word -> pinned host copy, read once its event has completed
             host = self.__dict__.get("_imt_label_status_host")
@@ -314,7 +300,7 @@ class ImageMassSeq2Seq(MassSeq2Seq):
         """The SAME decoder a second time, over the image regions with no key mask (src/image_model.py:213-216), and the
         sigmoid-gated mix of the two outputs (:217-219).  The pass draws its own dropout seed; the shared decoder parameters
         receive both passes' gradients (the stack runtime accumulates into the flat gradient)."""
-        decoder = self.decoder if not self.lang_dec else self.decoder[batch_lang]
+        decoder = self._decoder_for(batch_lang)
         dec_kw["encoder_attention_mask"] = None
         fixed = getattr(decoder, "_imt_dropout_seed", None)
         if fixed is not None:  # a pinned seed (tests): the second pass still gets masks of its own
@@ -332,7 +318,7 @@ class ImageMassSeq2Seq(MassSeq2Seq):
         build takes element 0, the grid embeddings, which is plainly what :213 and :252 mean."""
         if src_inputs is None:
             raise ValueError("ImageMassSeq2Seq with batch=: src_inputs is required (src/image_model.py:185)")
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         src_inputs = src_inputs.to(device)
         src_pads = (src_inputs != self.text_processor.pad_token_id()) if src_pads is None else src_pads.to(device)
         src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
@@ -344,29 +330,20 @@ class ImageMassSeq2Seq(MassSeq2Seq):
     def _multimodal_rows(self, src_inputs, src_pads, tgt_inputs, src_langs, tgt_langs, pad_idx, tgt_positions, batch, proposals):
         """Non-pad decoder rows of the gated text + image branch (src/image_model.py:192-226)."""
         assert tgt_inputs is not None
-        device = self.encoder.embeddings.word_embeddings.weight.device
         encoder_states, image_embeddings, src_pads = self._encode_text_and_image(src_inputs, src_pads, src_langs, batch)
-        tgt_inputs = tgt_inputs.to(device)
-        tgt_mask = tgt_inputs != pad_idx
-        langs = tgt_langs if tgt_langs is not None else src_langs
-        batch_lang = int(langs[0])
-        tgt_langs_t = self._lang_grid(langs, tgt_inputs.size(-1), device)
-        pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
-        rows = self._decode(encoder_states, src_pads, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=pos,
-                            proposals=proposals, pad_idx=pad_idx, img_states=image_embeddings)
-        return rows, tgt_inputs, tgt_mask, batch_lang
+        return self._target_rows(encoder_states, src_pads, tgt_inputs, None, tgt_langs if tgt_langs is not None else src_langs,
+                                 pad_idx, tgt_positions, proposals, img_states=image_embeddings)
 
     def _contrastive_loss(self, src_inputs, src_pads, src_langs, tgt_langs, batch, neg_samples, neg_mask):
         """src/image_model.py:231-264: the captions, the negative samples and the image regions pooled to unit vectors, and the
         image-to-text contrastive loss (one fused tail, ``_ContrastiveTailFn``).  Scalar fp32 loss."""
-        from .param_store import store_of
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         encoder_states, image_embeddings, src_pads = self._encode_text_and_image(src_inputs, src_pads, src_langs, batch)
         langs = tgt_langs if tgt_langs is not None else src_langs
         neg_samples, neg_mask = neg_samples.to(device), neg_mask.to(device)
         neg_langs = self._uniform_grid(neg_samples.size(0), neg_samples.size(-1), int(langs[0]), device)  # :235
         neg_states = MassSeq2Seq.encode(self, neg_samples, neg_mask, neg_langs)[0]
-        anchor = store_of(self).ensure().anchor() if torch.is_grad_enabled() else None
+        anchor = store_of(self).ensure().anchor_if_grad()
         return _ContrastiveTailFn.apply(anchor, encoder_states, src_pads, neg_states, neg_mask, image_embeddings, self)
 
     def forward(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, pad_idx: int = 0,
@@ -479,27 +456,22 @@ class ImageCaptioning(ImageMassSeq2Seq):
             return image_embeddings, object_fc
         return MassSeq2Seq.encode(self, src_inputs, src_mask, src_langs)
 
+    def _obj_decoder_for(self, batch_lang):
+        return self.obj_decoder[batch_lang] if self.lang_dec else self.obj_decoder
+
     def _mix_object_stream(self, decoder_output, object_fc, batch_lang, **dec_kw):
         """Second decoder pass over object_fc (no key mask: padded object rows take part, src/image_model.py:357-361) and
         the sigmoid-gated mix with the image decoder's output (:362-366)."""
-        obj_decoder = self.obj_decoder if not self.lang_dec else self.obj_decoder[batch_lang]
-        object_output = obj_decoder(encoder_states=object_fc, **dec_kw)
+        object_output = self._obj_decoder_for(batch_lang)(encoder_states=object_fc, **dec_kw)
         return gated_mix(self, self.multistream_attention_gate, decoder_output, object_output)
 
     def _caption_rows(self, batch, src_pads, tgt_inputs, tgt_langs, tgt_mask, pad_idx, tgt_positions, proposals):
         u = self._un
         tgt_positions, tgt_inputs, tgt_mask, tgt_langs = u(tgt_positions), u(tgt_inputs), u(tgt_mask), u(tgt_langs)
-        device = self.encoder.embeddings.word_embeddings.weight.device
         image_embeddings, object_fc = self.encode(images=batch["images"], objects=batch.get("objects"))
         assert tgt_inputs is not None
-        tgt_inputs = tgt_inputs.to(device)
-        tgt_mask = tgt_mask.to(device)
-        batch_lang = int(tgt_langs[0])
-        tgt_langs_t = self._lang_grid(tgt_langs, tgt_inputs.size(-1), device)
-        pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
-        rows = self._decode(image_embeddings, u(src_pads), tgt_inputs, tgt_mask, tgt_langs_t, batch_lang,
-                            position_ids=pos, proposals=proposals, pad_idx=pad_idx, obj_states=object_fc)
-        return rows, tgt_inputs, tgt_mask, batch_lang
+        return self._target_rows(image_embeddings, u(src_pads), tgt_inputs, tgt_mask, tgt_langs, pad_idx, tgt_positions,
+                                 proposals, obj_states=object_fc)
 
     def forward(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, tgt_mask=None,
                 pad_idx: int = 0, tgt_positions=None, batch=None, proposals=None, log_softmax: bool = False,

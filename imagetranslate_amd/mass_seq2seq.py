@@ -18,19 +18,13 @@ class MassSeq2Seq(Seq2Seq):
         return src_inputs, tgt_inputs, src_langs, tgt_positions
 
     def _mass_rows(self, src_inputs, tgt_inputs, src_langs, pad_idx, tgt_positions, proposals):
-        device = self.encoder.embeddings.word_embeddings.weight.device
-        tgt_inputs = tgt_inputs.to(device)
+        device = self._device
+        tgt_inputs = tgt_inputs.to(device)  # (first, as it always was: the copies to the device come before the encoder's launches)
         src_inputs = src_inputs.to(device)
         src_pads = src_inputs != pad_idx
-        tgt_mask = tgt_inputs != pad_idx
         src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
-        batch_lang = int(src_langs[0])
         encoder_states = self.encode(src_inputs, src_pads, src_langs_t)[0]
-        tgt_langs = self._lang_grid(src_langs, tgt_inputs.size(-1), device)
-        pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
-        rows = self._decode(encoder_states, src_pads, tgt_inputs, tgt_mask, tgt_langs, batch_lang, position_ids=pos,
-                            proposals=proposals, pad_idx=pad_idx)
-        return rows, tgt_inputs, tgt_mask, batch_lang
+        return self._target_rows(encoder_states, src_pads, tgt_inputs, None, src_langs, pad_idx, tgt_positions, proposals)
 
     def forward(self, src_inputs, tgt_inputs, src_langs, tgt_langs=None, pad_idx: int = 0, tgt_positions=None,
                 log_softmax: bool = False, proposals=None):
@@ -38,8 +32,7 @@ class MassSeq2Seq(Seq2Seq):
                                                                                  tgt_positions)
         if tgt_langs is not None:
             # back-translation / MT loss (:27-30)
-            device = self.encoder.embeddings.word_embeddings.weight.device
-            tgt_inputs = tgt_inputs.to(device)
+            tgt_inputs = tgt_inputs.to(self._device)
             src_pads = src_inputs != pad_idx
             tgt_mask = tgt_inputs != pad_idx
             return Seq2Seq.forward(self, src_inputs=src_inputs, src_mask=src_pads, tgt_inputs=tgt_inputs,
@@ -54,8 +47,7 @@ class MassSeq2Seq(Seq2Seq):
         src_inputs, tgt_inputs, src_langs, tgt_positions = self._unwrap_mass_args(src_inputs, tgt_inputs, src_langs,
                                                                                  tgt_positions)
         if tgt_langs is not None:
-            device = self.encoder.embeddings.word_embeddings.weight.device
-            tgt_inputs = tgt_inputs.to(device)
+            tgt_inputs = tgt_inputs.to(self._device)
             return Seq2Seq.loss_fused(self, src_inputs, tgt_inputs, src_inputs != pad_idx, tgt_inputs != pad_idx,
                                       src_langs, tgt_langs, epsilon=epsilon, proposals=proposals)
         rows, tgt_inputs, tgt_mask, batch_lang = self._mass_rows(src_inputs, tgt_inputs, src_langs, pad_idx,

@@ -146,7 +146,7 @@ class GradSync:
         shared = {id(l.attention) for l in m.encoder.encoder.layer}
 
         def end_of(params):
-            return max(st.offset(p) + p.numel() for p in params)
+            return st.span(params)[1]
 
         for dec in decs:
             layers = list(dec.decoder.layer)
@@ -181,11 +181,7 @@ class GradSync:
         ranges = [(0, st.total)]
         outs = self._output_layers()
         if active_head is not None and len(outs) > 1:
-            spans = []
-            for o in outs:
-                lo = min(st.offset(o.layer.weight), st.offset(o.layer.bias))
-                hi = max(st.offset(o.layer.weight) + o.layer.weight.numel(), st.offset(o.layer.bias) + o.layer.bias.numel())
-                spans.append((lo, hi))
+            spans = [st.span((o.layer.weight, o.layer.bias)) for o in outs]
             heads_lo, heads_hi = min(s[0] for s in spans), max(s[1] for s in spans)
             # the heads must be one contiguous run at the front of the buffer with nothing else in between
             covered = sum(hi - lo for lo, hi in spans)
@@ -220,8 +216,7 @@ class GradSync:
     def output_layers_done(self):
         """Call after the loss backward has produced the vocabulary-projection gradients (they sit at the front of the
         flat buffer)."""
-        st = self.store
-        self._advance(max(st.offset(o.layer.bias) + o.layer.bias.numel() for o in self._output_layers()))
+        self._advance(self.store.span(o.layer.bias for o in self._output_layers())[1])
 
     def _on_segment(self, stack_module, layer_index):
         end = self._milestones.get((id(stack_module), layer_index))
@@ -269,6 +264,16 @@ def clip_in_place(optimizer, store, max_norm: float, grad_scale: float = 1.0):
     O.clip_scale(store.grad, optimizer._grad_norm_sq(store), float(max_norm), float(grad_scale))
 
 
+def finish_micro_step(model, optimizer, sync, clip: float, update: bool, overlap_next_forward: bool = False):
+    """What follows every backward (src/train_image_mt.py:291-295): wait for the gradient exchange, then the fused clip +
+    Adam step at the end of an accumulation window (``update``), else the clip of the accumulated gradient in place."""
+    scale = sync.finish() if sync is not None else 1.0
+    if update:
+        optimizer.step(max_grad_norm=clip, grad_scale=scale, zero_grad=True, overlap_next_forward=overlap_next_forward)
+    else:
+        clip_in_place(optimizer, store_of(model.encoder).ensure(), clip, scale)
+
+
 def train_step(model, optimizer, batch, sync: Optional[GradSync] = None, clip: float = 1.0, epsilon: float = 0.1,
                update: bool = True, active_head: Optional[int] = None, loss_weight: float = 1.0):
     """One micro-step of the MT hot path == body of ImageMTTrainer.train_epoch (src/train_image_mt.py:239-295):
@@ -289,12 +294,6 @@ def train_step(model, optimizer, batch, sync: Optional[GradSync] = None, clip: f
         sync.begin_step(active_head)
     loss, ntokens = _loss_of(model, batch, epsilon)
     (loss if loss_weight == 1.0 else loss * loss_weight).backward()
-    scale = 1.0
-    if sync is not None:
-        scale = sync.finish()
-    if update:
-        optimizer.step(max_grad_norm=clip, grad_scale=scale, zero_grad=True,
-                       overlap_next_forward=os.environ.get("IMT_ADAM_OVERLAP", "0") != "0")
-    else:
-        clip_in_place(optimizer, store_of(model.encoder).ensure(), clip, scale)
+    finish_micro_step(model, optimizer, sync, clip, update,
+                      overlap_next_forward=os.environ.get("IMT_ADAM_OVERLAP", "0") != "0")
     return loss, ntokens

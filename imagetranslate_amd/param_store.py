@@ -130,12 +130,45 @@ class FlatParams:
     def offset(self, p: nn.Parameter) -> int:
         return self.index[id(p)]
 
+    # ------------------------------------------------------------------ typed access to one parameter
+    def _view(self, buf, p):
+        off = self.index[id(p)]
+        return buf[off:off + p.numel()].view(p.shape)
+
+    def views(self, dtype: torch.dtype, *params, flat=None):
+        """One view per parameter, shaped like it, into the flat buffer of the compute dtype (ONE ``params_for`` call: in
+        bf16 that call sums the version counters of every entry).  None (an absent bias) stays None.  A kernel that wants
+        ``[d]`` from a ``[1, d]`` gate or an ``nn.Linear(d, 1)`` weight flattens at the call site with ``.view(-1)``.
+        ``flat``: the ``params_for(dtype)`` result of a caller that needs the whole buffer as well (no second call)."""
+        if flat is None:
+            flat = self.params_for(dtype)
+        return [None if p is None else self._view(flat, p) for p in params]
+
+    def grad_view(self, p: nn.Parameter) -> torch.Tensor:
+        """fp32 gradient of ``p`` in the flat gradient buffer, shaped like ``p``."""
+        return self._view(self.grad, p)
+
+    def span(self, params):
+        """(lowest offset, highest offset + numel) of ``params`` in the flat buffers."""
+        ranges = [(self.index[id(p)], self.index[id(p)] + p.numel()) for p in params]
+        return min(lo for lo, _ in ranges), max(hi for _, hi in ranges)
+
+    def anchor_if_grad(self):
+        return self.anchor() if torch.is_grad_enabled() else None
+
+    def check_layout(self, version: int, what: str):
+        """Backward of an autograd node that addressed the flat buffers in its forward: refuse to write gradients at
+        offsets of a layout that has been rebuilt since."""
+        if self.layout_version != version:
+            from ._lib import ImtError
+            raise ImtError("parameter layout changed between forward and backward (%s)" % what)
+
     # ------------------------------------------------------------------ views used by the runtime
     def attach_grad_views(self):
         for p, off, n in self.entries:
             g = p.grad
             if g is None or g.data_ptr() != self.grad.data_ptr() + 4 * off:
-                p.grad = self.grad[off:off + n].view(p.shape)
+                p.grad = self.grad_view(p)
 
     def zero_grad(self):
         self.wait_updates(0)
@@ -169,9 +202,8 @@ class FlatParams:
         cached = mod.__dict__.get("_imt_site_ranges")
         if cached is None or cached[0] != key:
             def rng(params):
-                ps = [p for p in params if id(p) in self.index]
-                return (min(self.offset(p) for p in ps), max(self.offset(p) + p.numel() for p in ps))
-            sites = [rng(list(mod.embeddings.parameters()))] + [rng(list(l.parameters())) for l in mod._stack_layers()]
+                return self.span(p for p in params if id(p) in self.index)
+            sites = [rng(mod.embeddings.parameters())] + [rng(l.parameters()) for l in mod._stack_layers()]
             cached = (key, sites)
             mod.__dict__["_imt_site_ranges"] = cached
         out = []

@@ -110,7 +110,7 @@ def _pad(rows, pad_idx):
 @torch.no_grad()
 def score_pack(model, pack, pad_idx):
     """``{(source index in the pack, tid): score}`` of one pack: one encoder batch, one ``Seq2Seq.score`` per language."""
-    device = model.encoder.embeddings.word_embeddings.weight.device
+    device = model._device
     src = _pad([p[1] for p in pack], pad_idx).to(device)
     src_mask = src != pad_idx
     src_langs = model._lang_grid(torch.tensor([int(p[2]) for p in pack], dtype=torch.long), src.size(1), device)

@@ -74,27 +74,22 @@ class _FusedXentFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, targets, epsilon, ignore_index):
-        store = weight._imt_store()
-        store.ensure()
-        dtype = x.dtype
-        flat = store.params_for(dtype)
-        V, K = weight.shape
-        wo, bo = store.offset(weight), store.offset(bias)
-        w = flat[wo:wo + V * K].view(V, K)
-        b = flat[bo:bo + V]
+        store = weight._imt_store().ensure()
+        w, b = store.views(x.dtype, weight, bias)
         x = x.contiguous()
         n = x.shape[0]
         logits = O.gemm(x, w, O.IMT_NT, bias=b)
         rows = O.xent_fused_fwd_bwd(logits, targets, epsilon, ignore_index, 1.0 / max(n, 1))  # logits <- dlogits
-        ctx.store, ctx.wo, ctx.bo, ctx.shape = store, wo, bo, (V, K)
+        ctx.store, ctx.params, ctx.layout_version = store, (weight, bias), store.layout_version
         ctx.save_for_backward(x, w, logits)
         return O.scaled_sum(rows, 1.0 / max(n, 1))
 
     @staticmethod
     def backward(ctx, g):
         x, w, dlogits = ctx.saved_tensors
-        store = ctx.store
-        V, K = ctx.shape
+        store, (weight, bias) = ctx.store, ctx.params
+        store.check_layout(ctx.layout_version, "fused loss")
+        V, K = weight.shape
         g = g.float().reshape(1).contiguous()  # upstream scalar stays on the device (no host sync)
         n = dlogits.shape[0]
         tiles256 = ((n + 255) // 256) * ((K + 255) // 256)
@@ -108,10 +103,9 @@ class _FusedXentFn(torch.autograd.Function):
             O.gemm(dlogits, w, O.IMT_NN, out=dx, aux=slabs, aux_mode=O.IMT_AUX_SPLITK_WS, split_k=splits, alpha_dev=g)
         else:
             dx = O.gemm(dlogits, w, O.IMT_NN, alpha_dev=g, splitk_ws=O.splitk_workspace(dlogits.device))  # few rows: K ranges (imt_gemm)
-        gw = store.grad[ctx.wo:ctx.wo + V * K].view(V, K)
-        sk = max(1, min(n // 512, 512 // max(1, ((V + 127) // 128) * ((K + 127) // 128))))
-        O.gemm(dlogits, x, O.IMT_TN, out=gw, accumulate=(sk == 1), split_k=sk, alpha_dev=g,
-               a_colsum=store.grad[ctx.bo:ctx.bo + V])  # bias gradient fused: dlogits is read once
+        sk = O.dw_split_k(n, V, K, 512)
+        O.gemm(dlogits, x, O.IMT_TN, out=store.grad_view(weight), accumulate=(sk == 1), split_k=sk, alpha_dev=g,
+               a_colsum=store.grad_view(bias))  # bias gradient fused: dlogits is read once
         store.attach_grad_views()
         hook = getattr(store, "output_hook", None)
         if hook is not None:
@@ -273,12 +267,22 @@ class Seq2Seq(nn.Module):
         else:
             super().zero_grad(set_to_none=set_to_none)
 
+    @property
+    def _device(self):
+        return self.encoder.embeddings.word_embeddings.weight.device
+
+    def _output_layer(self, batch_lang):
+        return self.output_layer if (not self.lang_dec) and self.tie_embed else self.output_layer[batch_lang]
+
+    def _decoder_for(self, batch_lang):
+        return self.decoder[batch_lang] if self.lang_dec else self.decoder
+
     # ------------------------------------------------------------------ reference API
     def init_from_lm(self, lm):
         raise NotImplementedError("init_from_lm depends on the reference's broken LM class (SURVEY section 2 #17)")
 
     def encode(self, src_inputs, src_mask, src_langs, images=None):
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         if src_inputs.device != device:
             src_inputs = src_inputs.to(device)
             src_mask = src_mask.to(device)
@@ -289,7 +293,7 @@ class Seq2Seq(nn.Module):
     def attend_proposal(self, decoder_output, proposals, pad_idx):
         """src/seq2seq.py:110-144 (lexical proposals, off by default): plain torch ops on the GPU, not a kernel
         target.  Includes the reference's no-op mask fill (:132)."""
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         proposals = proposals.to(device)
         attend_mask = (proposals == pad_idx)
         dt = decoder_output.dtype
@@ -352,7 +356,7 @@ class Seq2Seq(nn.Module):
 
     def _decode(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=None,
                 proposals=None, pad_idx=0, sel_idx=None, obj_states=None, img_states=None):
-        decoder = self.decoder if not self.lang_dec else self.decoder[batch_lang]
+        decoder = self._decoder_for(batch_lang)
         info = self.__dict__.get("_imt_grid_info", {}).get(id(tgt_langs_t))
         if info is not None:  # a cached uniform grid: use the (T-1)-wide one instead of a non-contiguous slice
             types = self._uniform_grid(info[0], tgt_langs_t.size(1) - 1, info[1], tgt_langs_t.device)
@@ -374,9 +378,23 @@ class Seq2Seq(nn.Module):
             return flat  # no padding: the ordered selection of every row is the identity -- no gather / scatter launches
         return _SelectRowsFn.apply(flat, sel_idx)
 
+    def _target_rows(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, langs, pad_idx, tgt_positions, proposals,
+                     **streams):
+        """Target side shared by the MASS, text + image and captioning forwards: (non-pad decoder rows, ``tgt_inputs`` and
+        ``tgt_mask`` on the device, language of the batch).  ``tgt_mask`` None: every non-pad position.  ``streams``:
+        ``img_states=`` / ``obj_states=`` of ``_decode``."""
+        device = self._device
+        tgt_inputs = tgt_inputs.to(device)
+        tgt_mask = (tgt_inputs != pad_idx) if tgt_mask is None else tgt_mask.to(device)
+        batch_lang = int(langs[0])
+        tgt_langs_t = self._lang_grid(langs, tgt_inputs.size(-1), device)
+        pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
+        rows = self._decode(encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=pos,
+                            proposals=proposals, pad_idx=pad_idx, **streams)
+        return rows, tgt_inputs, tgt_mask, batch_lang
+
     def _project(self, rows, batch_lang, log_softmax):
-        output_layer = self.output_layer if (not self.lang_dec) and self.tie_embed else self.output_layer[batch_lang]
-        outputs = output_layer(rows)
+        outputs = self._output_layer(batch_lang)(rows)
         if log_softmax:
             outputs = _LogSoftmaxFn.apply(outputs)
         return outputs
@@ -384,7 +402,7 @@ class Seq2Seq(nn.Module):
     def forward(self, src_inputs, tgt_inputs, src_mask, tgt_mask, src_langs, tgt_langs, proposals=None,
                 log_softmax: bool = False):
         "Take in and process masked src and target sequences."
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         batch_lang = int(tgt_langs[0])
         src_langs = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1))
         tgt_langs = tgt_langs.unsqueeze(-1).expand(-1, tgt_inputs.size(-1)).to(device)
@@ -405,7 +423,7 @@ class Seq2Seq(nn.Module):
         `ntokens`: int(tgt_mask[:, 1:].sum()) when the caller has it on the host (the reference computes it from the
         batch at train_image_mt.py:253-256; our datasets put it in the batch dict) -- the step then needs no host
         synchronisation at all.  Returns (loss, ntokens)."""
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         batch_lang = int(tgt_langs[0])
         src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
         tgt_langs_t = self._lang_grid(tgt_langs, tgt_inputs.size(-1), device)
@@ -420,7 +438,7 @@ class Seq2Seq(nn.Module):
     def _loss_from_rows(self, rows, tgt_inputs, tgt_mask, batch_lang, epsilon, targets=None):
         if targets is None:
             targets = tgt_inputs[:, 1:][tgt_mask[:, 1:]].contiguous()
-        output_layer = self.output_layer if (not self.lang_dec) and self.tie_embed else self.output_layer[batch_lang]
+        output_layer = self._output_layer(batch_lang)
         loss = _FusedXentFn.apply(rows, output_layer.layer.weight, output_layer.layer.bias, targets, float(epsilon),
                                   int(self.text_processor.pad_token_id()))
         return loss, int(targets.numel())
@@ -438,7 +456,7 @@ class Seq2Seq(nn.Module):
         ``[rows]`` log-probs of the non-pad positions in (sentence, position) order and the ``[B + 1]`` row offsets."""
         if self.use_proposals:
             raise NotImplementedError("score() does not support lexical proposals")
-        device = self.encoder.embeddings.word_embeddings.weight.device
+        device = self._device
         batch_lang = int(tgt_langs[0])
         tgt_langs_t = self._lang_grid(tgt_langs, tgt_inputs.size(-1), device)
         tgt_inputs, tgt_mask, src_mask = tgt_inputs.to(device), tgt_mask.to(device), src_mask.to(device)
@@ -461,14 +479,10 @@ class Seq2Seq(nn.Module):
         rows = self._decode(encoder_states, src_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang,
                             pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
         # the projection operands in the compute dtype, straight from the flat store (as _LinearFn takes them)
-        output_layer = self.output_layer if (not self.lang_dec) and self.tie_embed else self.output_layer[batch_lang]
-        weight, bias = output_layer.layer.weight, output_layer.layer.bias
-        store = store_of(output_layer).ensure()
-        flat = store.params_for(rows.dtype)
-        V, K = weight.shape
-        wo, bo = store.offset(weight), store.offset(bias)
-        logprob, _, scores = O.score_rows(rows.contiguous(), flat[wo:wo + V * K].view(V, K), flat[bo:bo + V], targets.contiguous(),
-                                          seg_offsets=offsets, normalize=normalize)
+        output_layer = self._output_layer(batch_lang)
+        weight, bias = store_of(output_layer).ensure().views(rows.dtype, output_layer.layer.weight, output_layer.layer.bias)
+        logprob, _, scores = O.score_rows(rows.contiguous(), weight, bias, targets.contiguous(), seg_offsets=offsets,
+                                          normalize=normalize)
         return (scores, logprob, offsets) if return_token_logprobs else scores
 
     def state_dict(self, *args, **kwargs):

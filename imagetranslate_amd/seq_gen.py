@@ -107,7 +107,7 @@ class BeamDecoder(nn.Module):
             beam_width = self.beam_width
         if pad_idx is None:
             pad_idx = model.text_processor.pad_token_id()
-        device = model.encoder.embeddings.word_embeddings.weight.device
+        device = model._device
         if device.type != "cuda":
             raise L.ImtError("imagetranslate_amd: beam search needs the model on the GPU (no CPU fallback)")
         batch_lang = int(tgt_langs[0])
@@ -166,8 +166,7 @@ class BeamDecoder(nn.Module):
             max_lens_host = torch.LongTensor([max_len_func(int(x)) for x in src_sizes])
         max_lens = max_lens_host.to(device)
 
-        decoder = model.decoder if not model.lang_dec else model.decoder[batch_lang]
-        output_layer = model.output_layer if (not model.lang_dec) and model.tie_embed else model.output_layer[batch_lang]
+        decoder, output_layer = model._decoder_for(batch_lang), model._output_layer(batch_lang)
 
         first_tokens = first_tokens.to(device=device, dtype=torch.int64).contiguous()
         B, beam = batch_size, int(beam_width)
@@ -180,23 +179,18 @@ class BeamDecoder(nn.Module):
         langs = tgt_langs.to(device=device, dtype=torch.int64)
         type_rows = [langs.contiguous(), torch.repeat_interleave(langs, beam, 0).contiguous()]
 
-        store = store_of(decoder).ensure()
-        flat = store.params_for(dtype)
-        w_out, b_out = output_layer.layer.weight, output_layer.layer.bias
-        wo, bo = store.offset(w_out), store.offset(b_out)
-        W = flat[wo:wo + w_out.numel()].view(w_out.shape)
-        bias = flat[bo:bo + b_out.numel()]
-        obj_decoder = gate = None
+        obj_decoder = gate_param = None
         if obj_fc is not None:
-            obj_decoder = model.obj_decoder if not model.lang_dec else model.obj_decoder[batch_lang]
-            go = store.offset(model.multistream_attention_gate)
-            gate = flat[go:go + model.config.hidden_size]
+            obj_decoder, gate_param = model._obj_decoder_for(batch_lang), model.multistream_attention_gate
         elif img_states is not None:
             # the second stream is the SAME decoder over the image regions, no key mask (:184-188); from here on it is handled
             # like the object stream: `obj_fc` = the second stream's encoder side, `obj_decoder` the stack that reads it
-            obj_decoder, obj_fc = decoder, img_states
-            go = store.offset(model.multimodal_attention_gate)
-            gate = flat[go:go + model.config.hidden_size]
+            obj_decoder, obj_fc, gate_param = decoder, img_states, model.multimodal_attention_gate
+        store = store_of(decoder).ensure()
+        flat = store.params_for(dtype)  # the whole buffer as well: the incremental decoders' descriptors point at it
+        W, bias, gate = store.views(dtype, output_layer.layer.weight, output_layer.layer.bias, gate_param, flat=flat)
+        if gate is not None:
+            gate = gate.view(-1)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         lib = L.load()
 

@@ -14,8 +14,6 @@ import torch
 from . import dataset
 from .image_model import ImageCaptioning, ImageMassSeq2Seq
 from .option_parser import get_img_options_parser
-from .parallel import clip_in_place
-from .param_store import store_of
 from .seq2seq import Seq2Seq
 from .seq_gen import BeamDecoder, get_outputs_until_eos
 from .textprocessor import TextProcessor
@@ -39,15 +37,14 @@ class ImageCaptionTrainer(ImageMTTrainer):
         if not bool(batch["caption_mask"][:, 1:].any()):
             if self.sync is not None and self.world_size > 1:
                 self.sync.begin_step()
-                self._finish_micro_step(None, accum, self.sync.finish())
+                self._finish_micro_step(accum)
             return 0.0, 0
         if self.sync is not None:
             self.sync.begin_step()
         loss, ntokens = model.loss_fused(tgt_inputs=batch["captions"], tgt_mask=batch["caption_mask"], pad_idx=tp.pad_token_id(),
                                          tgt_langs=batch["langs"], batch=batch)
         loss.backward()
-        scale = self.sync.finish() if self.sync is not None else 1.0
-        self._finish_micro_step(loss, accum, scale)
+        self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
 
     @torch.no_grad()

@@ -18,7 +18,7 @@ from torch.nn.utils.rnn import pad_sequence
 from . import dataset
 from .image_model import ImageMassSeq2Seq
 from .option_parser import get_img_options_parser
-from .parallel import GradSync, clip_in_place, train_step
+from .parallel import GradSync, finish_micro_step, train_step
 from .textprocessor import TextProcessor
 from .utils import build_optimizer, mass_mask_device
 
@@ -50,14 +50,10 @@ class ImageMTTrainer:
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
 
-    def _finish_micro_step(self, loss, accum: int, scale: float):
+    def _finish_micro_step(self, accum: int):
         """clip after EVERY backward, step every `accum` (src/train_image_mt.py:291-295)."""
         self.micro_step += 1
-        if self.micro_step % max(1, accum) == 0:
-            self.optimizer.step(max_grad_norm=self.clip, grad_scale=scale, zero_grad=True)
-        else:
-            from .param_store import store_of
-            clip_in_place(self.optimizer, store_of(self.model.encoder).ensure(), self.clip, scale)
+        finish_micro_step(self.model, self.optimizer, self.sync, self.clip, update=self.micro_step % max(1, accum) == 0)
 
     # one MT batch (src/train_image_mt.py:239-295)
     def mt_step(self, batch, accum: int = 1, loss_weight: float = 1.0):
@@ -78,8 +74,7 @@ class ImageMTTrainer:
                                               src_langs=batch["langs"], pad_idx=tp.pad_token_id(),
                                               tgt_positions=masked["positions"])
         loss.backward()
-        scale = self.sync.finish() if self.sync is not None else 1.0
-        self._finish_micro_step(loss, accum, scale)
+        self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
 
     # one image-caption batch (src/train_image_mt.py:202-237): --mmode picks the masked-caption step (the gated text + image
@@ -107,7 +102,7 @@ class ImageMTTrainer:
                                                   pad_idx=tp.pad_token_id(), src_langs=batch["langs"], tgt_langs=batch["langs"],
                                                   batch=batch)
         loss.backward()
-        self._finish_micro_step(loss, accum, 1.0)
+        self._finish_micro_step(accum)
         self.image_steps += 1
         self.last_image_step = ("masked" if masked_step else "contrastive", loss.detach())
         return loss.detach(), int(ntokens)
@@ -150,8 +145,7 @@ class ImageMTTrainer:
         loss, ntokens = model.loss_fused(src_inputs=translations, tgt_inputs=src, src_langs=dst_langs, tgt_langs=batch["langs"],
                                          pad_idx=pad)
         loss.backward()
-        scale = self.sync.finish() if self.sync is not None else 1.0
-        self._finish_micro_step(loss, accum, scale)
+        self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
 
     @torch.no_grad()

@@ -154,11 +154,10 @@ class AdamInverseSqrtWithWarmup(torch.optim.Optimizer):
         root = st._root()
         try:
             enc_layers = list(root.encoder.encoder.layer)
-            starts = [min(st.offset(p) for p in lyr.ordered_params()) for lyr in enc_layers]  # flat order: top layer first
-            e = root.encoder.embeddings
-            emb_lo = min(st.offset(p) for p in e.parameters())
+            starts = [st.span(lyr.ordered_params())[0] for lyr in enc_layers]  # flat order: top layer first
+            emb_lo = st.span(root.encoder.embeddings.parameters())[0]
             decs = list(root.decoder) if isinstance(root.decoder, torch.nn.ModuleList) else [root.decoder]
-            dec_lo = min(st.offset(p) for d in decs for p in d.parameters())
+            dec_lo = st.span(p for d in decs for p in d.parameters())[0]
             enc_lo = min(starts)
         except Exception:
             return None

@@ -59,7 +59,7 @@ def _worker(rank, world, port, q):
             assert len(b) >= 3, b  # several buckets -> overlap opportunities
         # parameter .grad views see the reduced values
         p = m.output_layer[0].layer.bias
-        assert torch.equal(p.grad, st.grad[st.offset(p):st.offset(p) + p.numel()])
+        assert torch.equal(p.grad, st.grad_view(p))
         q.put((rank, "ok"))
     except Exception as e:  # pragma: no cover
         import traceback

@@ -325,7 +325,6 @@ def test_one_launch_step_with_objects_against_chain(cuda, monkeypatch):
     types = torch.ones(B, dtype=torch.long, device="cuda")
     slots = torch.arange(B, dtype=torch.int32, device="cuda").unsqueeze(1).expand(B, T).contiguous()
     store = store_of(m.decoder).ensure()
-    go = store.offset(m.multistream_attention_gate)
     lib = L.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     states = {}
@@ -335,6 +334,7 @@ def test_one_launch_step_with_objects_against_chain(cuda, monkeypatch):
         with torch.no_grad():
             emb, obj = m.encode(images=b["images"].cuda(), objects=b["objects"])
         flat = store.params_for(dtype)
+        gate = store.views(dtype, m.multistream_attention_gate)[0].view(-1)
         inc = _Incremental(lib, m.decoder, store, dtype, flat, emb.contiguous(), None, B, 1, T, stream)
         inc_obj = _Incremental(lib, m.obj_decoder, store, dtype, flat, obj.contiguous(), None, B, 1, T, stream)
         h, ho = (torch.empty(B, 512, dtype=dtype, device="cuda") for _ in range(2))
@@ -342,7 +342,7 @@ def test_one_launch_step_with_objects_against_chain(cuda, monkeypatch):
         for t in range(T):
             inc.step(t, B, 1, ids[t].contiguous(), types, slots, h)
             inc_obj.step(t, B, 1, ids[t].contiguous(), types, slots, ho)
-            out.append(O.gated_mix(h, ho, flat[go:go + 512]).float())
+            out.append(O.gated_mix(h, ho, gate).float())
         inc_obj.check()
         inc.check()
         states[(mode, dtype)] = out
@@ -447,3 +447,40 @@ def test_train_and_caption_cli_with_objects(cuda, tmp_path, capsys):
                    max_len=16, objects=bt["objects"])
         for p, h in zip(bt["paths"], hyps):
             assert lines[p] == tp.decode(h[1:].tolist())
+
+
+# ------------------------------------------------------------------------------------------------ stale layout
+@pytest.mark.parametrize("node", ["linear", "fused_loss", "image_head", "object_head", "gated_mix", "contrastive_tail"])
+def test_backward_after_a_rebuilt_layout_is_refused(cuda, node):
+    """Every node that addresses the flat buffers records the layout version in forward; after a rebuild its backward
+    raises instead of writing gradients at the offsets of the old layout (nothing reaches the new gradient buffer)."""
+    from imagetranslate_amd._lib import ImtError
+    from imagetranslate_amd.image_model import ImageCaptioning, _ContrastiveTailFn, gated_mix
+    from imagetranslate_amd.param_store import store_of
+    from imagetranslate_amd.seq2seq import _FusedXentFn
+    torch.manual_seed(0)
+    m = ImageCaptioning(R.SyntheticTextProcessor(1000), lang_dec=False, enc_layer=1, dec_layer=1, embed_dim=128, intermediate_dim=256,
+                        num_attention_heads=4, image_feat_dim=64, use_obj=True).cuda().eval()
+    store = store_of(m.encoder).ensure()
+    g = torch.Generator().manual_seed(1)
+    rows = lambda *shape: torch.randn(*shape, generator=g).cuda().requires_grad_()
+    if node == "linear":
+        out = m.output_layer[1](rows(5, 128))
+    elif node == "fused_loss":
+        lin = m.output_layer[1].layer
+        out = _FusedXentFn.apply(rows(5, 128), lin.weight, lin.bias, torch.randint(6, 1000, (5,), generator=g).cuda(), 0.1, 0)
+    elif node == "image_head":
+        out = m.image_model(torch.randn(2, 49, 64, generator=g))[0]
+    elif node == "object_head":
+        out = m.image_model.objects_forward(_objects(2, 5, counts=[5, 2], seed=3))
+    elif node == "gated_mix":
+        out = gated_mix(m, m.multistream_attention_gate, rows(2, 3, 128), rows(2, 3, 128))
+    else:
+        mask = torch.ones(2, 6, dtype=torch.bool, device="cuda")
+        out = _ContrastiveTailFn.apply(store.anchor_if_grad(), rows(2, 6, 128), mask, rows(2, 6, 128), mask, rows(2, 49, 128), m)
+    assert out.requires_grad
+    store.rebuild()
+    with pytest.raises(ImtError, match="parameter layout changed between forward and backward"):
+        out.float().sum().backward()
+    torch.cuda.synchronize()
+    assert float(store.grad.abs().sum()) == 0.0

@@ -93,3 +93,72 @@ def test_optimizer_lr_schedule_matches_oracle():
     for t in [0, 1, 4, 5, 6, 100, 10 ** 6]:
         assert opt.get_lr_for_step(t) == pytest.approx(R.inverse_sqrt_lr(t, 1e-4, 5))
     assert opt.param_groups[0]["lr"] == 1e-7
+
+
+def _small(**kw):
+    return _ours(**dict(dict(lang_dec=False, enc_layer=2, dec_layer=2, embed_dim=64, intermediate_dim=128, num_attention_heads=4), **kw))
+
+
+def test_flat_store_typed_views():
+    from imagetranslate_amd._lib import ImtError
+    from imagetranslate_amd.param_store import store_of
+    m = _small()
+    st = store_of(m.encoder).ensure()
+    lin = m.output_layer[1].layer
+    w, b, none = st.views(torch.float32, lin.weight, lin.bias, None)
+    assert none is None
+    for v, p in ((w, lin.weight), (b, lin.bias)):
+        assert v.shape == p.shape and v.dtype == torch.float32
+        assert v.data_ptr() == st.flat.data_ptr() + 4 * st.offset(p) == p.data_ptr()
+    for p in m.parameters():
+        g = st.grad_view(p)
+        assert g.shape == p.shape and g.data_ptr() == p.grad.data_ptr() == st.grad.data_ptr() + 4 * st.offset(p)
+    for lyr in list(m.encoder.encoder.layer) + list(m.decoder.decoder.layer):
+        ps = lyr.ordered_params()
+        assert st.span(ps) == (min(st.offset(p) for p in ps), max(st.offset(p) + p.numel() for p in ps))
+        assert st.span(iter(ps)) == st.span(ps)
+    assert st.span([lin.bias]) == (st.offset(lin.bias), st.offset(lin.bias) + 1000)
+    with torch.no_grad():
+        assert st.anchor_if_grad() is None
+    assert st.anchor_if_grad() is st.anchor() and st.anchor().requires_grad
+    version = st.layout_version
+    st.check_layout(version, "test")  # unchanged layout: no error
+    st.rebuild()
+    with pytest.raises(ImtError, match="parameter layout changed between forward and backward"):
+        st.check_layout(version, "test")
+    st.check_layout(st.layout_version, "test")
+
+
+def test_dropout_seed_cases():
+    from imagetranslate_amd.bert_seq2seq import dropout_seed
+    mod = torch.nn.Module()
+    torch.manual_seed(5)
+    before = torch.get_rng_state()
+    assert dropout_seed(mod, False) == 0 and dropout_seed(mod, False, salt=2) == 0
+    mod._imt_dropout_seed = 7
+    assert dropout_seed(mod, False) == 0  # inactive wins over a pinned seed
+    assert dropout_seed(mod, True) == 7 and dropout_seed(mod, True, salt=2) == 9
+    assert torch.equal(torch.get_rng_state(), before)  # neither case draws
+    mod._imt_dropout_seed = None
+    seed = dropout_seed(mod, True, salt=2)
+    after = torch.get_rng_state()
+    torch.set_rng_state(before)
+    assert seed == int(torch.randint(0, 2 ** 62, (1,)))  # the draw itself, no salt
+    assert torch.equal(torch.get_rng_state(), after)     # exactly one randint
+    assert not torch.equal(after, before)
+
+
+@pytest.mark.parametrize("lang_dec", [False, True])
+@pytest.mark.parametrize("tie_embed", [False, True])
+def test_output_layer_and_decoder_choice(lang_dec, tie_embed):
+    m = _small(lang_dec=lang_dec, tie_embed=tie_embed)
+    for lang in (0, 1):
+        if not lang_dec and tie_embed:
+            assert not isinstance(m.output_layer, torch.nn.ModuleList) and m._output_layer(lang) is m.output_layer
+        else:
+            assert m._output_layer(lang) is m.output_layer[lang]
+        assert m._decoder_for(lang) is (m.decoder[lang] if lang_dec else m.decoder)
+    assert m._device == m.encoder.embeddings.word_embeddings.weight.device
+    c = _ours("ImageCaptioning", lang_dec=lang_dec, tie_embed=tie_embed, enc_layer=2, dec_layer=2, embed_dim=64,
+              intermediate_dim=128, num_attention_heads=4)
+    assert c._obj_decoder_for(1) is (c.obj_decoder[1] if lang_dec else c.obj_decoder)

@@ -71,10 +71,8 @@ def run_config(name, calls):
     seg_of_row = torch.repeat_interleave(torch.arange(counts.numel(), device=dev), counts)
     out_layer = model.output_layer[1]
     store = store_of(out_layer).ensure()
-    flat = store.params_for(torch.bfloat16)
-    V, K = out_layer.layer.weight.shape
-    wo, bo = store.offset(out_layer.layer.weight), store.offset(out_layer.layer.bias)
-    w, bias = flat[wo:wo + V * K].view(V, K), flat[bo:bo + V]
+    w, bias = store.views(torch.bfloat16, out_layer.layer.weight, out_layer.layer.bias)
+    V, K = w.shape
     N = rows.shape[0]
 
     def tail_fused():
