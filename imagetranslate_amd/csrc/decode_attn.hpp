@@ -66,6 +66,12 @@ IMT_DEVICE void attn_decode_wave(const imt_attn_decode_args& a, int w) {
   const T* Kb = reinterpret_cast<const T*>(a.K) + h * DH + 8 * c;
   const T* Vb = reinterpret_cast<const T*>(a.V) + h * DH + 8 * c;
   float m = -INFINITY, l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // The reference adds -10000 to the score of a masked key.  Done in fp32 that rounds the score to the spacing of floats at 10000
+  // (2^-10): harmless while an unmasked key dwarfs it, but a sentence whose keys are ALL masked is the plain softmax of its raw scores
+  // and would carry that rounding (3e-4 in the weights).  So the bias is kept out of the sum: a lane group's (m, l, o) covers its
+  // unmasked keys once it has `seen` one -- what the masked keys before it gave is dropped, exp(-10000) == 0 -- and its masked keys,
+  // with their raw scores, until then.
+  bool seen = false;
   // UNR key groups per iteration: their slot lookups, then their K/V row segments, are all in flight before the first
   // dependent softmax update (one group per iteration was a chain of exposed load latencies: 18.7 us at 145 keys)
   // bf16 rows wait in registers as loaded (16 bytes = 4 registers each), so more groups fit: six = 48 keys of a 64-wide head per
@@ -107,8 +113,9 @@ IMT_DEVICE void attn_decode_wave(const imt_attn_decode_args& a, int w) {
 #pragma unroll
       for (int x = 1; x < CH; x <<= 1) s += __shfl_xor(s, x, 64);
       s *= a.scale;
-      if (a.key_mask && !mk[u]) s += -10000.0f;
-      if (valid) {
+      const bool open = !a.key_mask || mk[u];
+      if (valid && (open || !seen)) {
+        if (open && !seen) { seen = true; m = -INFINITY; }
         const float mn = fmaxf(m, s);
         const float corr = __expf(m - mn), p = __expf(s - mn);  // exp(-inf) == 0 on the first key
         l = l * corr + p;
@@ -118,7 +125,9 @@ IMT_DEVICE void attn_decode_wave(const imt_attn_decode_args& a, int w) {
       }
     }
   }
-  // merge the G lane groups (lanes with equal c)
+  // merge the G lane groups (lanes with equal c); groups that saw masked keys only count for nothing beside one that did not
+  const bool any_seen = __any(seen);  // (all 64 lanes vote: not inside the condition below)
+  if (!seen && any_seen) m = -INFINITY;
   float M = m;
 #pragma unroll
   for (int x = CH; x < 64; x <<= 1) M = fmaxf(M, __shfl_xor(M, x, 64));

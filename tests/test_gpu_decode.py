@@ -10,6 +10,7 @@ import torch
 from oracle import reference_model as R
 from oracle import seq_gen as OG
 from tests.util import assert_close, beam_inputs, beam_state_dict, caption_beam_inputs, load_toy
+from tests.util import call_beam_step as _call_beam_step, ref_beam_step as _ref_beam_step
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -54,12 +55,54 @@ def test_attention_decode_cross_mask(cuda, dtype):
     mask[2, :] = False  # fully masked sentence: -10000 on every key -> plain softmax of the raw scores
     out = O.attention_decode(q, kv[0, 0, :d], kv[0, 0, d:], Tk, H, ld_row=Tk * 2 * d, ld_pos=2 * d, rep=rep,
                              key_mask=mask.to(torch.uint8).cuda())
-    k = kv.float().cpu()[:, :, :d].view(B, Tk, H, dh).repeat_interleave(rep, 0)
-    v = kv.float().cpu()[:, :, d:].view(B, Tk, H, dh).repeat_interleave(rep, 0)
-    s = torch.einsum("rhd,rkhd->rhk", q.float().cpu().view(-1, H, dh), k) / math.sqrt(dh)
-    s = s + (1.0 - mask.float().repeat_interleave(rep, 0))[:, None, :] * -10000.0
+    # fp64 reference: an fp32 one rounds the raw scores of the fully masked sentence to the spacing of floats at 10000 (3e-4 in its
+    # softmax weights), which the kernel does not (decode_attn.hpp keeps the mask bias out of the sum)
+    k = kv.double().cpu()[:, :, :d].view(B, Tk, H, dh).repeat_interleave(rep, 0)
+    v = kv.double().cpu()[:, :, d:].view(B, Tk, H, dh).repeat_interleave(rep, 0)
+    s = torch.einsum("rhd,rkhd->rhk", q.double().cpu().view(-1, H, dh), k) / math.sqrt(dh)
+    s = s + (1.0 - mask.double().repeat_interleave(rep, 0))[:, None, :] * -10000.0
     ref = torch.einsum("rhk,rkhd->rhd", torch.softmax(s, -1), v).reshape(-1, d)
     assert_close(out.float().cpu(), ref, 1e-5 if dtype == torch.float32 else 1.5e-2, "decode attention (cross)")
+
+
+def _cross_mask_case(dh, H, dtype):
+    """Tk = 150 keys (several iterations of attn_decode_wave, whose last key group is clamped), rep = 5; sentences with 150,
+    97 and 1 unmasked keys and a fully masked one.  In sentences 0 and 1 one key is given the largest raw score of the
+    whole sentence and then masked out: a kernel that drops a mask bit in a later iteration is dominated by that key."""
+    g = torch.Generator().manual_seed(11 + dh)
+    B, rep, Tk = 4, 5, 150
+    d = H * dh
+    kv = torch.randn(B, Tk, 2 * d, generator=g)
+    q = torch.randn(B * rep, d, generator=g).to(dtype)
+    mask = (torch.arange(Tk)[None] < torch.tensor([150, 97, 1, 150])[:, None])
+    hot = {0: 140, 1: 70}
+    for b, j in hot.items():
+        kv[b, j, :d] = 2.0 * q[b * rep + 1].float()
+    kv = kv.to(dtype)
+    k = kv.double()[:, :, :d].view(B, Tk, H, dh).repeat_interleave(rep, 0)
+    v = kv.double()[:, :, d:].view(B, Tk, H, dh).repeat_interleave(rep, 0)
+    s = torch.einsum("rhd,rkhd->rhk", q.double().view(-1, H, dh), k) / math.sqrt(dh)
+    for b, j in hot.items():
+        best = s[b * rep:(b + 1) * rep].masked_fill(~mask[b][None, None, :], -1e30).amax((0, 1)).argmax()
+        assert int(best) == j, "the masked-out key must be the one with the largest raw score"
+        mask[b, j] = False
+    mask[3, :] = False  # fully masked sentence: -10000 on every key -> plain softmax of the raw scores
+    s = s + (1.0 - mask.double().repeat_interleave(rep, 0))[:, None, :] * -10000.0
+    ref = torch.einsum("rhk,rkhd->rhd", torch.softmax(s, -1), v).reshape(-1, d)
+    return q, kv, mask, ref
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dh,H", [(64, 8), (32, 4)])
+def test_attention_decode_cross_mask_many_iterations(cuda, dtype, dh, H):
+    """Key mask over several key iterations against fp64 softmax attention with the reference's (1 - m) * -10000."""
+    import imagetranslate_amd.hip_ops as O
+    q, kv, mask, ref = _cross_mask_case(dh, H, dtype)
+    B, Tk, d, rep = kv.size(0), kv.size(1), H * dh, q.size(0) // kv.size(0)
+    kv, q = kv.cuda(), q.cuda()
+    out = O.attention_decode(q, kv[0, 0, :d], kv[0, 0, d:], Tk, H, ld_row=Tk * 2 * d, ld_pos=2 * d, rep=rep,
+                             key_mask=mask.to(torch.uint8).cuda())
+    assert_close(out.float().cpu(), ref, 1e-5 if dtype == torch.float32 else 1.5e-2, "decode attention (cross, 150 keys)")
 
 
 def test_attention_decode_rejects_bad_args(cuda):
@@ -71,62 +114,6 @@ def test_attention_decode_rejects_bad_args(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ beam step
-def _ref_beam_step(logits, scores, sizes, eos_in, max_lens, hist, step, B, beam, rep, V, ratio, pad, eos):
-    """The reference's step (src/seq_gen.py:193-227) on CPU tensors with the oracle's stable top-k."""
-    lp = torch.log_softmax(logits, -1)
-    over = (max_lens < step + 1)
-    lp[eos_in.bool()] = 0
-    if step > 1:
-        lp[over.repeat_interleave(rep)] = 0
-    total = scores.unsqueeze(-1) + lp
-    if beam > 1:
-        total = total / torch.pow((sizes + 6.0) / 6.0, ratio).unsqueeze(-1)
-    top, idx = OG.stable_topk(total.view(B, -1), beam)
-    if step > 1:
-        idx[over] = pad
-        flat = idx.view(-1)
-        flat[eos_in.bool()] = pad
-        parent = idx // V
-    else:
-        parent = torch.zeros_like(idx)
-    word = idx % V
-    prow = (torch.arange(B)[:, None] * rep + parent).view(-1)
-    new_hist = torch.cat([hist[prow, :step], word.view(-1, 1)], 1)
-    new_sizes = sizes[prow] + (word.view(-1) != pad)
-    new_eos = (new_hist == eos).any(1)
-    return top.view(-1), new_sizes, new_eos, new_hist, prow
-
-
-def _call_beam_step(logits, scores, sizes, eos_in, max_lens, hist, slots_in, step, B, beam, rep, V, t_max, ratio, pad, eos):
-    """One imt_beam_step through the C ABI on copies of the given CPU tensors; returns the output buffers."""
-    import imagetranslate_amd.hip_ops as O
-    from imagetranslate_amd import _lib as L
-    dev = "cuda"
-    rows, r_out = B * rep, B * beam
-    z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)
-    d_logits, d_scores, d_sizes = logits.cuda(), scores.cuda(), sizes.cuda()
-    d_eos, d_max, d_hist = eos_in.to(torch.uint8).cuda(), max_lens.cuda(), hist.cuda()
-    d_slots = slots_in.cuda()
-    cs, ci = z(rows, beam, dtype=torch.float32), z(rows, beam, dtype=torch.int32)
-    o_scores, o_sizes, o_eos = z(r_out, dtype=torch.float32), z(r_out, dtype=torch.float32), z(r_out, dtype=torch.uint8)
-    o_hist, o_slots = z(r_out, t_max, dtype=torch.int64), z(r_out, t_max, dtype=torch.int32)
-    o_parent, o_tok, cnt = z(r_out, dtype=torch.int32), z(r_out, dtype=torch.int64), z(t_max, dtype=torch.int32)
-    a = L.BeamArgs()
-    a.B, a.beam, a.rep, a.V, a.step, a.t_max = B, beam, rep, V, step, t_max
-    a.logits, a.ld = d_logits.data_ptr(), V
-    a.scores_in, a.sizes_in, a.eos_in = d_scores.data_ptr(), d_sizes.data_ptr(), d_eos.data_ptr()
-    a.max_lens, a.hist_in, a.slots_in = d_max.data_ptr(), d_hist.data_ptr(), d_slots.data_ptr()
-    a.len_penalty_ratio, a.pad_idx, a.eos = ratio, pad, eos
-    a.cand_scores, a.cand_idx = cs.data_ptr(), ci.data_ptr()
-    a.scores_out, a.sizes_out, a.eos_out = o_scores.data_ptr(), o_sizes.data_ptr(), o_eos.data_ptr()
-    a.hist_out, a.slots_out, a.parent_out, a.tokens_out = o_hist.data_ptr(), o_slots.data_ptr(), o_parent.data_ptr(), o_tok.data_ptr()
-    a.eos_count = cnt.data_ptr()
-    O.beam_step(a)
-    torch.cuda.synchronize()
-    return dict(scores=o_scores.cpu(), sizes=o_sizes.cpu(), eos=o_eos.cpu(), hist=o_hist.cpu(), slots=o_slots.cpu(),
-                parent=o_parent.cpu(), tokens=o_tok.cpu(), eos_count=cnt.cpu(), cand_idx=ci.cpu(), cand_scores=cs.cpu())
-
-
 @pytest.mark.parametrize("beam,step", [(4, 1), (4, 3), (1, 1), (1, 4), (7, 2)])
 def test_beam_step_matches_reference_step(cuda, beam, step):
     g = torch.Generator().manual_seed(beam * 10 + step)
@@ -244,6 +231,32 @@ def test_beam_decoder_fp32_tokens_bit_exact(cuda, kv_cache):
         got = BeamDecoder(ours, beam_width=5, kv_cache=kv_cache, sync_every=3)(pad_idx=0, **inp, **kw)
         assert [g.tolist() for g in got] == [e.tolist() for e in exp], name
         assert [g.tolist() for g in got] == [t.tolist() for t in gold[name]["tokens"]], name + " (fixture)"
+
+
+def _oracle_fp64(ref, **kw):
+    """The oracle's search with every tensor in double precision (weights, scores, sizes, the length penalty)."""
+    import copy
+    torch.set_default_dtype(torch.float64)
+    try:
+        return OG.BeamDecoder(copy.deepcopy(ref).double(), beam_width=5)(**kw)
+    finally:
+        torch.set_default_dtype(torch.float32)
+
+
+@pytest.mark.parametrize("kv_cache", [True, False], ids=["kv_cache", "recompute"])
+def test_beam_decoder_wide_beam_fp32_tokens_bit_exact(cuda, kv_cache):
+    """Beam 12 (above 8: the general row top-k kernel on every step) on the sharp and on the soft toy weights.  The inputs
+    qualify for an exact comparison because the oracle finds the same tokens in fp32 and in fp64 (checked first, on the CPU)."""
+    from imagetranslate_amd.seq_gen import BeamDecoder
+    inp = beam_inputs()
+    for name, state in [("sharp", _fixture_state()), ("soft", _fixture_state(2.5, 2.5))]:
+        ref, ours = _pair(state=state)
+        for kw in (dict(beam_width=12), dict(beam_width=12, unpad_output=False)):
+            exp = OG.BeamDecoder(ref, beam_width=5)(pad_idx=0, **inp, **kw)
+            exp64 = _oracle_fp64(ref, pad_idx=0, **inp, **kw)
+            assert [e.tolist() for e in exp] == [e.tolist() for e in exp64], "fp32 and fp64 oracle disagree: choose another beam width"
+            got = BeamDecoder(ours, beam_width=5, kv_cache=kv_cache, sync_every=3)(pad_idx=0, **inp, **kw)
+            assert [g.tolist() for g in got] == [e.tolist() for e in exp], (name, kw)
 
 
 def test_beam_decoder_soft_distribution_and_sync_period(cuda):

@@ -149,3 +149,41 @@ def test_row_kernel_argument_checks(lib):
     assert lib.imt_layernorm_fwd(9, 0x1000, 0x1000, 0x1000, 0x1000, None, None, 4, 8, 1e-12, 0.0, 0, None) == ERR
     assert lib.imt_abi_sizeof(b"imt_gemm_args") == ctypes.sizeof(L.GemmArgs)
     assert lib.imt_abi_sizeof(None) == -1
+
+
+def _beam_args(**kw):
+    """A well-formed imt_beam_args (pointers are never dereferenced on the host) with the given fields replaced."""
+    a = L.BeamArgs()
+    a.B, a.beam, a.rep, a.V, a.step, a.t_max = 2, 4, 4, 100, 3, 8
+    a.ld, a.len_penalty_ratio, a.pad_idx, a.eos = 104, 0.8, 0, 4
+    for i, (f, t) in enumerate(L.BeamArgs._fields_):
+        if t is ctypes.c_void_p:
+            setattr(a, f, 0x10000 * (i + 1))
+    for f, v in kw.items():
+        setattr(a, f, v)
+    return a
+
+
+def test_beam_step_argument_checks(lib):
+    bad = lambda **kw: lib.imt_beam_step(ctypes.byref(_beam_args(**kw)), None)
+    assert lib.imt_beam_step(None, None) == ERR and b"null args" in lib.imt_last_error()
+    assert bad(B=0) == ERR
+    for beam in (0, 33):
+        assert bad(beam=beam, rep=beam) == ERR and b"out of range" in lib.imt_last_error(), beam
+    assert bad(V=3) == ERR and b"out of range" in lib.imt_last_error()             # V < beam
+    for rep in (0, 2, 3, 5):
+        assert bad(rep=rep) == ERR and b"rep must be" in lib.imt_last_error(), rep
+    assert bad(step=0) == ERR and b"outside" in lib.imt_last_error()
+    for step in (8, 9):                                                            # step >= t_max
+        assert bad(step=step) == ERR and b"outside" in lib.imt_last_error(), step
+    assert bad(step=2, rep=1) == ERR and b"first step" in lib.imt_last_error()     # step > 1 with rep == 1
+    assert bad(pad_idx=-1) == ERR and b"pad_idx" in lib.imt_last_error()
+    assert bad(pad_idx=400) == ERR and b"pad_idx" in lib.imt_last_error()          # pad_idx >= beam * V
+    for f in ("logits", "scores_in", "eos_in", "max_lens", "hist_in", "cand_scores", "cand_idx"):
+        assert bad(**{f: None}) == ERR and b"null input" in lib.imt_last_error(), f
+    for f in ("scores_out", "eos_out", "hist_out", "parent_out", "tokens_out"):
+        assert bad(**{f: None}) == ERR and b"null output" in lib.imt_last_error(), f
+    for f in ("sizes_in", "sizes_out"):                                            # beam > 1 without sizes
+        assert bad(**{f: None}) == ERR and b"sizes required" in lib.imt_last_error(), f
+    for f in ("slots_in", "slots_out"):                                            # exactly one of the slot tables
+        assert bad(**{f: None}) == ERR and b"slots_in/slots_out" in lib.imt_last_error(), f

@@ -134,3 +134,97 @@ def caption_beam_inputs():
     g = torch.Generator().manual_seed(3)
     return dict(images=torch.randn(B, 49, 64, generator=g), first_tokens=torch.full((B,), 5, dtype=torch.long),
                 tgt_langs=torch.ones(B, dtype=torch.long))
+
+
+# ------------------------------------------------------------------------------------------- imt_beam_step helpers
+def ref_beam_step(logits, scores, sizes, eos_in, max_lens, hist, step, B, beam, rep, V, ratio, pad, eos, dtype=None,
+                  return_sorted=False):
+    """The reference's step (src/seq_gen.py:193-227) on CPU tensors with the oracle's stable top-k (value descending, flat
+    index ascending).  ``dtype=torch.float64`` does every score computation (log_softmax, the zeroing, scores + lp, the
+    division by pow((sizes + 6) / 6, ratio)) in double precision; ``return_sorted`` adds the sentences' candidate scores in
+    selection order ([B, rep * V]) for beam_reference_is_unambiguous."""
+    sizes_in = sizes
+    if dtype is not None:
+        logits, scores, sizes = logits.to(dtype), scores.to(dtype), sizes.to(dtype)
+    lp = torch.log_softmax(logits, -1)
+    over = (max_lens < step + 1)
+    lp[eos_in.bool()] = 0
+    if step > 1:
+        lp[over.repeat_interleave(rep)] = 0
+    total = scores.unsqueeze(-1) + lp
+    if beam > 1:
+        total = total / torch.pow((sizes + 6.0) / 6.0, ratio).unsqueeze(-1)
+    vals, order = torch.sort(total.view(B, -1), dim=1, descending=True, stable=True)
+    top, idx = vals[:, :beam].contiguous(), order[:, :beam].contiguous()
+    if step > 1:
+        idx[over] = pad
+        flat = idx.view(-1)
+        flat[eos_in.bool()] = pad
+        parent = idx // V
+    else:
+        parent = torch.zeros_like(idx)
+    word = idx % V
+    prow = (torch.arange(B)[:, None] * rep + parent).view(-1)
+    new_hist = torch.cat([hist[prow, :step], word.view(-1, 1)], 1)
+    new_sizes = sizes_in[prow] + (word.view(-1) != pad)
+    new_eos = (new_hist == eos).any(1)
+    out = (top.view(-1), new_sizes, new_eos, new_hist, prow)
+    return out + (vals,) if return_sorted else out
+
+
+def beam_reference_is_unambiguous(vals, beam, gap=1e-4):
+    """The condition on the INPUTS under which an fp32 kernel can be compared token for token with the fp64 reference:
+    among each sentence's best beam + 1 candidates (``vals``: [B, n] fp64, selection order) every adjacent pair is either
+    bit-equal -- a constructed tie, decided by the index alone -- or at least ``gap`` apart.  A run of ties that reaches
+    past the best beam + 1 is followed to its end and the step below it checked too (nothing within rounding of the
+    selected candidates but outside them).  Returns (ok, smallest non-zero gap seen)."""
+    ok, smallest = True, float("inf")
+    for row in vals:
+        n = min(beam + 1, row.numel())
+        n = int((row >= row[n - 1]).sum())          # through the end of the tie run of the last one (row is sorted)
+        d = row[:min(n + 1, row.numel())]
+        d = d[:-1] - d[1:]
+        d = d[d != 0]
+        if d.numel():
+            smallest = min(smallest, float(d.min()))
+            ok = ok and bool((d >= gap).all())
+    return ok, smallest
+
+
+def call_beam_step(logits, scores, sizes, eos_in, max_lens, hist, slots_in, step, B, beam, rep, V, t_max, ratio, pad, eos,
+                   ld=None, offset=0, pad_fill=0.0):
+    """One imt_beam_step through the C ABI on copies of the given CPU tensors; returns the output buffers.  The logits rows
+    are laid out ``ld`` (default V) floats apart in a device buffer, starting ``offset`` floats into it (the buffer itself
+    is 16-byte aligned); the columns [V, ld) of every row hold ``pad_fill``."""
+    import imagetranslate_amd.hip_ops as O
+    from imagetranslate_amd import _lib as L
+    dev = "cuda"
+    rows, r_out = B * rep, B * beam
+    ld = V if ld is None else ld
+    assert ld >= V and logits.shape == (rows, V)
+    z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)
+    buf = torch.full((offset + rows * ld,), pad_fill, dtype=torch.float32, device=dev)
+    assert buf.data_ptr() % 16 == 0
+    d_logits = buf[offset:].view(rows, ld)
+    d_logits[:, :V] = logits.cuda()
+    d_scores, d_sizes = scores.cuda(), sizes.cuda()
+    d_eos, d_max, d_hist = eos_in.to(torch.uint8).cuda(), max_lens.cuda(), hist.cuda()
+    d_slots = slots_in.cuda()
+    cs, ci = z(rows, beam, dtype=torch.float32), z(rows, beam, dtype=torch.int32)
+    o_scores, o_sizes, o_eos = z(r_out, dtype=torch.float32), z(r_out, dtype=torch.float32), z(r_out, dtype=torch.uint8)
+    o_hist, o_slots = z(r_out, t_max, dtype=torch.int64), z(r_out, t_max, dtype=torch.int32)
+    o_parent, o_tok, cnt = z(r_out, dtype=torch.int32), z(r_out, dtype=torch.int64), z(t_max, dtype=torch.int32)
+    a = L.BeamArgs()
+    a.B, a.beam, a.rep, a.V, a.step, a.t_max = B, beam, rep, V, step, t_max
+    a.logits, a.ld = d_logits.data_ptr(), ld
+    a.scores_in, a.sizes_in, a.eos_in = d_scores.data_ptr(), d_sizes.data_ptr(), d_eos.data_ptr()
+    a.max_lens, a.hist_in, a.slots_in = d_max.data_ptr(), d_hist.data_ptr(), d_slots.data_ptr()
+    a.len_penalty_ratio, a.pad_idx, a.eos = ratio, pad, eos
+    a.cand_scores, a.cand_idx = cs.data_ptr(), ci.data_ptr()
+    a.scores_out, a.sizes_out, a.eos_out = o_scores.data_ptr(), o_sizes.data_ptr(), o_eos.data_ptr()
+    a.hist_out, a.slots_out, a.parent_out, a.tokens_out = o_hist.data_ptr(), o_slots.data_ptr(), o_parent.data_ptr(), o_tok.data_ptr()
+    a.eos_count = cnt.data_ptr()
+    O.beam_step(a)
+    torch.cuda.synchronize()
+    return dict(scores=o_scores.cpu(), sizes=o_sizes.cpu(), eos=o_eos.cpu(), hist=o_hist.cpu(), slots=o_slots.cpu(),
+                parent=o_parent.cpu(), tokens=o_tok.cpu(), eos_count=cnt.cpu(), cand_idx=ci.cpu(), cand_scores=cs.cpu())
