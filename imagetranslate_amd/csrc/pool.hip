@@ -56,10 +56,23 @@ IMT_DEVICE float block_max(float v, float* red) {
 }
 IMT_DEVICE float dot4(f32x4 a, f32x4 b) { return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]; }
 
+// Dropout of the pooled tensor (sentence pooling of Caption2Image): the decision for element i of the flattened tensor is the one
+// imt_add_rows_dropout makes under the same seed; base = flat index of the sentence's first element.  thresh == 0: no dropout.
+struct PoolDrop {
+  uint32_t thresh; float inv_keep; uint64_t seed, base;
+};
+// 1 / (1 - p) where elements idx0 .. idx0 + 3 (idx0 % 4 == 0) are kept, 0 where they are dropped
+IMT_DEVICE f32x4 drop_scale4(const PoolDrop& dr, uint64_t idx0) {
+  f32x4 s = {1.f, 1.f, 1.f, 1.f};
+  dropout_apply4(s, dr.seed, idx0, dr.thresh, dr.inv_keep);
+  return s;
+}
+
 // dot product of every position's row with vec[0..d) (global T or LDS fp32), one wave per position; out[s] = the sum.  The raw
-// elements are kept in LDS when keep_x.
-template <typename T, typename TV>
-IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T* xs, float* out, int S, int d, bool keep_x) {
+// elements are kept in LDS when keep_x.  DROP: the row is dropout(x) (the raw elements are what LDS keeps).
+template <typename T, typename TV, bool DROP = false>
+IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T* xs, float* out, int S, int d, bool keep_x,
+                         const PoolDrop dr = PoolDrop()) {
   constexpr int U = 4;  // positions per wave iteration: their loads are in flight together (one position's sum order is unchanged)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int s0 = wave * U; s0 < S; s0 += (POOL_THREADS / 64) * U) {
@@ -74,7 +87,13 @@ IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T
       for (int k = 0; k < U; ++k)
         if (s0 + k < S) {
           if (keep_x) *reinterpret_cast<typename Vec4<T>::type*>(xs + (int64_t)(s0 + k) * d + c) = raw[k];
-          acc[k] += dot4(Vec4<T>::cvt(raw[k]), vv);
+          if constexpr (DROP) {
+            f32x4 xv = Vec4<T>::cvt(raw[k]);
+            if (dr.thresh) xv *= drop_scale4(dr, dr.base + (uint64_t)(s0 + k) * d + c);
+            acc[k] += dot4(xv, vv);
+          } else {
+            acc[k] += dot4(Vec4<T>::cvt(raw[k]), vv);
+          }
         }
     }
 #pragma unroll
@@ -83,6 +102,35 @@ IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T
       if (lane == 0 && s0 + k < S) out[s0 + k] = a;
     }
   }
+}
+
+// l.sc[s]: x_s . w  ->  p_s = softmax over s of (x_s . w + bias, or exactly -10000 where mask is 0); also written to probs.  The
+// statements of attn_pool_fwd_kernel's softmax, for the sentence pooling below (that kernel keeps its own copy: as a call the
+// compiler schedules it differently, and its machine code is kept as it was).
+IMT_DEVICE void pool_softmax(const PoolLds& l, const uint8_t* __restrict__ mask, float* __restrict__ probs, float bias, int64_t row,
+                             int S) {
+  const int t = threadIdx.x;
+  float m = -INFINITY;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float v = (mask && !mask[row * S + s]) ? -10000.0f : l.sc[s] + bias;
+    l.sc[s] = v;
+    m = fmaxf(m, v);
+  }
+  m = block_max(m, l.red);
+  float sum = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float e = expf(l.sc[s] - m);
+    l.sc[s] = e;
+    sum += e;
+  }
+  sum = block_sum(sum, l.red);
+  const float inv = 1.0f / sum;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float p = l.sc[s] * inv;
+    l.sc[s] = p;
+    probs[row * S + s] = p;
+  }
+  __syncthreads();
 }
 
 template <typename T>
@@ -224,6 +272,140 @@ __global__ __launch_bounds__(256) void attn_pool_fold_kernel(const float* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------- sentence pooling (Caption2Image)
+// src/image_model.py:430-436: xd = dropout(x) (training), score_s = xd_s . w + b, masked_fill(-10000), p = softmax(score),
+// v = sum_s p_s xd_s -- no normalisation; v is written in the compute dtype (it feeds the decoder GEMM).  Same plan as above:
+// LDS keeps the RAW sentence, the dropout factor of an element is recomputed from its index wherever the element is used.
+template <typename T>
+__global__ __launch_bounds__(POOL_THREADS) void sent_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
+                                                                     const uint8_t* __restrict__ mask, T* __restrict__ v_out,
+                                                                     float* __restrict__ probs, int S, int d, int keep_x, uint32_t thresh,
+                                                                     float inv_keep, uint64_t seed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PoolLds l = pool_lds(smem, S, d);
+  T* xs = reinterpret_cast<T*>(l.xs);
+  const int64_t row = blockIdx.x;
+  const T* xr = x + row * S * d;
+  const int t = threadIdx.x;
+  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
+  row_dots<T, T, true>(xr, w, xs, l.sc, S, d, keep_x != 0, dr);
+  __syncthreads();
+  pool_softmax(l, mask, probs, to_f32<T>(b[0]), row, S);
+  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
+  const int cg = t % ncol4, g = t / ncol4;
+  if (g < G) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = g; s < S; s += G) {
+      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      if (thresh) xv *= drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
+      acc += xv * l.sc[s];
+    }
+    Vec4<float>::store(l.part + g * d + cg * 4, acc);
+  }
+  __syncthreads();
+  if (t < ncol4) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
+    Vec4<T>::store(v_out + row * d + t * 4, v);
+  }
+}
+
+// dp_s = dv . xd_s;  dscore_s = p_s (dp_s - sum_t p_t dp_t), 0 at a masked position;  d(xd_s) = p_s dv + dscore_s w, and
+// dx = the dropout's backward of that (same mask, same scale);  dw = sum_s dscore_s xd_s;  db = sum_s dscore_s (per-sentence
+// partials, folded by attn_pool_fold_kernel).
+template <typename T>
+__global__ __launch_bounds__(POOL_THREADS) void sent_pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const uint8_t* __restrict__ mask,
+                                                                     const float* __restrict__ probs, const T* __restrict__ dv_in,
+                                                                     T* __restrict__ dx, float* __restrict__ dw_part,
+                                                                     float* __restrict__ db_part, int S, int d, int keep_x, uint32_t thresh,
+                                                                     float inv_keep, uint64_t seed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PoolLds l = pool_lds(smem, S, d);
+  T* xs = reinterpret_cast<T*>(l.xs);
+  const int64_t row = blockIdx.x;
+  const T* xr = x + row * S * d;
+  const int t = threadIdx.x;
+  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
+  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
+  if (t < ncol4) Vec4<float>::store(l.vec + t * 4, Vec4<T>::load(dv_in + row * d + t * 4));
+  for (int s = t; s < S; s += POOL_THREADS) l.pr[s] = probs[row * S + s];
+  __syncthreads();
+  // dp (first read of x)
+  row_dots<T, float, true>(xr, l.vec, xs, l.sc, S, d, keep_x != 0, dr);
+  __syncthreads();
+  float c0 = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) c0 += l.pr[s] * l.sc[s];
+  c0 = block_sum(c0, l.red);
+  float dbl = 0.f;
+  for (int s = t; s < S; s += POOL_THREADS) {
+    const float ds = (mask && !mask[row * S + s]) ? 0.f : l.pr[s] * (l.sc[s] - c0);
+    l.sc[s] = ds;
+    dbl += ds;
+  }
+  dbl = block_sum(dbl, l.red);
+  // dx and dw (second read of x, or LDS)
+  const int cg = t % ncol4, g = t / ncol4;
+  if (g < G) {
+    const f32x4 wv = Vec4<T>::load(w + cg * 4), dv = Vec4<float>::load(l.vec + cg * 4);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = g; s < S; s += G) {
+      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      const float ds = l.sc[s];
+      f32x4 gx = dv * l.pr[s] + wv * ds;
+      if (thresh) {
+        const f32x4 sc = drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
+        xv *= sc;
+        gx *= sc;
+      }
+      Vec4<T>::store(dx + (row * S + s) * d + cg * 4, gx);
+      acc += xv * ds;
+    }
+    Vec4<float>::store(l.part + g * d + cg * 4, acc);
+  }
+  __syncthreads();
+  if (t < ncol4) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
+    Vec4<float>::store(dw_part + row * d + t * 4, v);
+  }
+  if (t == 0) db_part[row] = dbl;
+}
+
+// ------------------------------------------------------------------------------------------- L2 distance (Caption2Image loss)
+// torch.dist(pred, target, 2) / B (src/train_txt2image.py:67) and its gradient in one call.  First launch: workgroup g adds
+// the squared differences of its grid-stride share of the 4-element groups -> part[g]; second launch: every workgroup adds the
+// partials in index order (the same bits everywhere), workgroup 0 writes the loss, all write dpred = (pred - target) / (r B),
+// zeros where r == 0 (torch's subgradient of the norm at 0).
+template <typename T>
+__global__ __launch_bounds__(256) void l2_partial_kernel(const T* __restrict__ pred, const T* __restrict__ target, float* __restrict__ part,
+                                                         int64_t n4) {
+  __shared__ float red[16];
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 df = Vec4<T>::load(pred + i * 4) - Vec4<T>::load(target + i * 4);
+    acc += dot4(df, df);
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void l2_scale_kernel(const T* __restrict__ pred, const T* __restrict__ target, const float* __restrict__ part,
+                                                       int nparts, float* __restrict__ loss, T* __restrict__ dpred, int64_t n4, float inv_b) {
+  __shared__ float ps[IMT_L2_DIST_PARTS];
+  if ((int)threadIdx.x < nparts) ps[threadIdx.x] = part[threadIdx.x];
+  __syncthreads();
+  float ss = 0.f;
+  for (int k = 0; k < nparts; ++k) ss += ps[k];
+  const float r = sqrtf(ss);
+  const float coef = ss > 0.f ? inv_b / r : 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) loss[0] = r * inv_b;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
+    Vec4<T>::store(dpred + i * 4, (Vec4<T>::load(pred + i * 4) - Vec4<T>::load(target + i * 4)) * coef);
+}
+
 // ------------------------------------------------------------------------------------------- contrastive loss
 // Workgroup i: C_ij = img_i . txt_j for every j, row loss log(sum_j exp C_ij + 1e-4) - (C_ii + 1e-4) (:260-262),
 // dC_ij = (exp C_ij / (sum_j exp C_ij + 1e-4) - [i == j]) / B, d_img_i = sum_j dC_ij txt_j.
@@ -362,6 +544,95 @@ extern "C" int imt_contrastive(const float* img, const float* txt, float* loss, 
   hipLaunchKernelGGL(contrastive_rows_kernel, dim3(B), dim3(POOL_THREADS), 0, st, img, txt, row_loss, dc, d_img, B, N, d);
   IMT_CHECK_LAUNCH();
   hipLaunchKernelGGL(contrastive_cols_kernel, dim3(N), dim3(POOL_THREADS), 0, st, img, dc, row_loss, d_txt, loss, B, N, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+namespace {
+int sent_pool_validate(const char* what, int dtype, int64_t rows, int S, int d, float dropout_p) {
+  const int rc = pool_validate(what, dtype, rows, S, d);
+  if (rc != IMT_OK) return rc;
+  IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p outside [0, 1)", what);
+  return IMT_OK;
+}
+}  // namespace
+
+extern "C" int imt_sent_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, void* v, float* probs,
+                                 int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed, void* stream) {
+  const int rc = sent_pool_validate("sent_pool_fwd", dtype, rows, S, d, dropout_p);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && b && v && probs, "sent_pool_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
+  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
+  const uint32_t th = dropout_thresh(dropout_p);
+  const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
+  ImtProfScope prof("sent_pool_fwd", 2.0 * rows * S * d * 2, (keep ? 1.0 : 2.0) * xb, st);
+  if (dtype == IMT_F32)
+    hipLaunchKernelGGL(sent_pool_fwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w,
+                       (const float*)b, mask, (float*)v, probs, S, d, keep, th, ik, dropout_seed);
+  else
+    hipLaunchKernelGGL(sent_pool_fwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       (const bf16_t*)b, mask, (bf16_t*)v, probs, S, d, keep, th, ik, dropout_seed);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_sent_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* probs, const void* dv, void* dx,
+                                 float* dw, float* db, float* ws, int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed,
+                                 void* stream) {
+  const int rc = sent_pool_validate("sent_pool_bwd", dtype, rows, S, d, dropout_p);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && probs && dv && dx && dw && db && ws, "sent_pool_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
+  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
+  const uint32_t th = dropout_thresh(dropout_p);
+  const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+  float* dw_part = ws;
+  float* db_part = ws + rows * d;
+  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
+  ImtProfScope prof("sent_pool_bwd", 2.0 * rows * S * d * 3, (keep ? 2.0 : 3.0) * xb, st);
+  if (dtype == IMT_F32)
+    hipLaunchKernelGGL(sent_pool_bwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w, mask,
+                       probs, (const float*)dv, (float*)dx, dw_part, db_part, S, d, keep, th, ik, dropout_seed);
+  else
+    hipLaunchKernelGGL(sent_pool_bwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       mask, probs, (const bf16_t*)dv, (bf16_t*)dx, dw_part, db_part, S, d, keep, th, ik, dropout_seed);
+  IMT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_pool_fold_kernel, dim3(imt_cdiv(d + 1, 256)), dim3(256), 0, st, dw_part, db_part, dw, db, rows, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_l2_dist(int dtype, const void* pred, const void* target, float* loss, void* dpred, float* ws, int B, int64_t n,
+                           void* stream) {
+  IMT_CHECK_ARG(ok_dtype(dtype), "l2_dist: bad dtype");
+  IMT_CHECK_ARG(B >= 1, "l2_dist: B must be at least 1");
+  IMT_CHECK_ARG(n >= 4 && n % 4 == 0, "l2_dist: n must be a positive multiple of 4");
+  IMT_CHECK_ARG(n <= ((int64_t)1 << 40) / B, "l2_dist: more than 2^40 elements are not taken");
+  IMT_CHECK_ARG(pred && target && loss && dpred && ws, "l2_dist: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n4 = (int64_t)B * n / 4;
+  const int64_t wgs = (n4 + 255) / 256;
+  const int nparts = (int)(wgs < IMT_L2_DIST_PARTS ? wgs : IMT_L2_DIST_PARTS);
+  const int grid2 = (int)(wgs < 2048 ? wgs : 2048);
+  const float inv_b = 1.0f / (float)B;
+  ImtProfScope prof("l2_dist", 3.0 * B * n, (double)B * n * (dtype == IMT_BF16 ? 2 : 4) * 5, st);
+  if (dtype == IMT_F32) {
+    hipLaunchKernelGGL(l2_partial_kernel<float>, dim3(nparts), dim3(256), 0, st, (const float*)pred, (const float*)target, ws, n4);
+    IMT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(l2_scale_kernel<float>, dim3(grid2), dim3(256), 0, st, (const float*)pred, (const float*)target, ws, nparts, loss,
+                       (float*)dpred, n4, inv_b);
+  } else {
+    hipLaunchKernelGGL(l2_partial_kernel<bf16_t>, dim3(nparts), dim3(256), 0, st, (const bf16_t*)pred, (const bf16_t*)target, ws, n4);
+    IMT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(l2_scale_kernel<bf16_t>, dim3(grid2), dim3(256), 0, st, (const bf16_t*)pred, (const bf16_t*)target, ws, nparts, loss,
+                       (bf16_t*)dpred, n4, inv_b);
+  }
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }

@@ -632,6 +632,56 @@ def contrastive(img, txt):
     return loss, d_img, d_txt
 
 
+# ------------------------------------------------------------------------------------------- Caption2Image tail
+L2_DIST_PARTS = 256  # include/imt_hip.h: IMT_L2_DIST_PARTS
+
+
+def sent_pool_fwd(x, w, b, mask=None, dropout_p=0.0, dropout_seed=0):
+    """(v [rows, d] in x's dtype, probs [rows, S] fp32) of the sentence pooling of dropout(x), x [rows, S, d]
+    (imt_sent_pool_fwd); w [d] and b [1] in x's dtype, mask [rows, S] bool / uint8 or None.  The dropout keeps what
+    ``add_rows_dropout`` keeps of the flattened [rows * S, d] tensor under the same seed."""
+    _req_cuda(x, w, b, mask)
+    rows, S, d = x.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and b.dtype == x.dtype and w.numel() == d and b.numel() == 1
+    mask = _pool_mask(mask, rows, S)
+    v = torch.empty((rows, d), device=x.device, dtype=x.dtype)
+    probs = torch.empty((rows, S), device=x.device, dtype=torch.float32)
+    L.check(L.load().imt_sent_pool_fwd(dt(x), _p(x), _p(w), _p(b), _p(mask), _p(v), _p(probs), rows, S, d, float(dropout_p),
+                                       int(dropout_seed), _stream()), "imt_sent_pool_fwd")
+    return v, probs
+
+
+def sent_pool_bwd(x, w, mask, probs, dv, dw, db, dropout_p=0.0, dropout_seed=0):
+    """dx [rows, S, d] in x's dtype; dw (fp32 [d]) and db (fp32 [1]) += the parameter gradients (imt_sent_pool_bwd,
+    deterministic); dv [rows, d] in x's dtype, the dropout mask is regenerated from the seed."""
+    _req_cuda(x, w, mask, probs, dv, dw, db)
+    rows, S, d = x.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and w.numel() == d
+    assert dv.dtype == x.dtype and dv.is_contiguous() and tuple(dv.shape) == (rows, d)
+    mask = _pool_mask(mask, rows, S)
+    for t, shape in ((probs, (rows, S)), (dw, (d,)), (db, (1,))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+    dx = torch.empty_like(x)
+    ws = torch.empty((rows * d + rows,), device=x.device, dtype=torch.float32)
+    L.check(L.load().imt_sent_pool_bwd(dt(x), _p(x), _p(w), _p(mask), _p(probs), _p(dv), _p(dx), _p(dw), _p(db), _p(ws), rows, S, d,
+                                       float(dropout_p), int(dropout_seed), _stream()), "imt_sent_pool_bwd")
+    return dx
+
+
+def l2_dist(pred, target):
+    """(loss [1] fp32, dpred like pred): |pred - target|_2 / B over [B, n] tensors of one dtype and its gradient with respect
+    to pred, from one call (imt_l2_dist); the gradient is all zeros where the distance is 0."""
+    _req_cuda(pred, target)
+    assert pred.dim() == 2 and pred.shape == target.shape and pred.dtype == target.dtype
+    assert pred.is_contiguous() and target.is_contiguous()
+    B, n = pred.shape
+    loss = torch.empty((1,), device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred)
+    ws = torch.empty((L2_DIST_PARTS,), device=pred.device, dtype=torch.float32)
+    L.check(L.load().imt_l2_dist(dt(pred), _p(pred), _p(target), _p(loss), _p(dpred), _p(ws), B, n, _stream()), "imt_l2_dist")
+    return loss, dpred
+
+
 def add_rows_dropout(x, add=None, out_dtype=None, dropout_p=0.0, dropout_seed=0):
     """out[r, :] = dropout(x[r, :] + add[r % add.shape[0], :]) for a 2-D x (imt_add_rows_dropout); add may be None."""
     _req_cuda(x, add)

@@ -1,6 +1,6 @@
 """Image branch of the path -- drop-in for the on-path parts of the reference's ``src/image_model.py``:
-``ImageMassSeq2Seq`` (text branch ``:157-183``, gated text + image branch ``:185-230``, contrastive branch ``:231-264``) and
-``ImageCaptioning`` (``:267-377``).
+``ImageMassSeq2Seq`` (text branch ``:157-183``, gated text + image branch ``:185-230``, contrastive branch ``:231-264``),
+``ImageCaptioning`` (``:267-377``) and ``Caption2Image`` (``:380-464``).
 
 The CNN trunk (torchvision ResNet / Faster-RCNN, ``:14-124``) is OUT of scope (frozen
 feature extractor whose pretrained weights need a network fetch); region features ``[B, 49, C]`` enter at the
@@ -9,15 +9,23 @@ The detector's output (box features, boxes, labels) enters pre-extracted as ``ba
 then runs its object stream (object rows ``:58-78``, ``obj_decoder`` and ``multistream_attention_gate`` ``:357-366``).
 ``ImageMassSeq2Seq`` with ``batch=`` runs its decoder over the text states and over the image regions and mixes the two with
 ``multimodal_attention_gate``, or, with negative samples, the contrastive loss on the fused pooling kernels (csrc/pool.hip).
+``Caption2Image`` maps a sentence to the 49 x d region embedding of its image: encoder stack, sentence pooling
+(``imt_sent_pool_fwd``, dropout included), one linear layer; its loss is the L2 distance to a captioner's embedding (``imt_l2_dist``).
 """
+import json
+import os
+import pickle
+import weakref
+
 import torch
 import torch.nn as nn
 
 from . import hip_ops as O
-from .bert_seq2seq import BertDecoderModel, _Pretrained, dropout_seed
+from . import lm_config
+from .bert_seq2seq import BertConfig, BertDecoderModel, BertEncoderModel, _LinearFn, _Pretrained, dropout_seed
 from .mass_seq2seq import MassSeq2Seq
 from .param_store import store_of
-from .seq2seq import future_mask  # noqa: F401
+from .seq2seq import FlatStoreModel, future_mask  # noqa: F401
 
 
 class _ImageHeadFn(torch.autograd.Function):
@@ -501,3 +509,151 @@ class ImageCaptioning(ImageMassSeq2Seq):
     def score(self, *args, **kwargs):
         raise NotImplementedError("ImageCaptioning.score: image-conditioned scoring is not implemented (score text pairs "
                                   "with Seq2Seq / ImageMassSeq2Seq)")
+
+
+class _SentPoolFn(torch.autograd.Function):
+    """dropout -> one-vector attention -> weighted sum (src/image_model.py:430-436) as one node: ``imt_sent_pool_fwd``; the
+    backward (``imt_sent_pool_bwd``) regenerates the dropout mask from the seed, returns the gradient the encoder stack
+    receives and accumulates d(input_attention) into the flat gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, states, mask, model, p, seed):
+        store = store_of(model).ensure()
+        w, b = store.views(states.dtype, model.input_attention.weight, model.input_attention.bias)
+        w = w.view(-1)  # nn.Linear(d, 1) weight is [1, d]
+        x = states.contiguous()
+        v, probs = O.sent_pool_fwd(x, w, b, mask, dropout_p=p, dropout_seed=seed)
+        ctx.store, ctx.model, ctx.layout_version = store, model, store.layout_version
+        ctx.mask, ctx.p, ctx.seed = mask, p, seed
+        ctx.save_for_backward(x, w, probs)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        x, w, probs = ctx.saved_tensors
+        store, att = ctx.store, ctx.model.input_attention
+        store.check_layout(ctx.layout_version, "sentence pooling")
+        dx = O.sent_pool_bwd(x, w, ctx.mask, probs, dv.to(x.dtype).contiguous(), store.grad_view(att.weight).view(-1),
+                             store.grad_view(att.bias), dropout_p=ctx.p, dropout_seed=ctx.seed)
+        store.attach_grad_views()
+        return None, dx, None, None, None, None
+
+
+class _L2DistFn(torch.autograd.Function):
+    """torch.dist(pred, target, 2) / B (src/train_txt2image.py:67): ``imt_l2_dist`` gives the loss and d loss / d pred in one
+    call; an upstream gradient multiplies the saved gradient on the device (it is never read on the host; a factor of 1, what
+    ``loss.backward()`` passes, leaves a bf16 gradient bit for bit, any other factor rounds it a second time)."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        loss, dpred = O.l2_dist(pred.contiguous(), target)
+        ctx.save_for_backward(dpred)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g.detach().to(torch.float32).reshape(()), None  # a 0-d fp32 factor: dpred's dtype is kept
+
+
+class Caption2Image(FlatStoreModel):
+    REGIONS = 49
+
+    def __init__(self, text_processor, enc_layer: int = 6, embed_dim: int = 768, intermediate_dim: int = 3072, *,
+                 num_attention_heads: int = 12):
+        super(Caption2Image, self).__init__()
+        self.text_processor = text_processor
+        self.config = lm_config.get_config(vocab_size=text_processor.tokenizer.get_vocab_size(),
+                                           pad_token_id=text_processor.pad_token_id(),
+                                           bos_token_id=text_processor.bos_token_id(),
+                                           eos_token_id=text_processor.sep_token_id(),
+                                           enc_layer=enc_layer, embed_dim=embed_dim, intermediate_dim=intermediate_dim,
+                                           num_attention_heads=num_attention_heads)
+        self.enc_layer = enc_layer
+        self.embed_dim = embed_dim
+        self.intermediate_dim = intermediate_dim
+        self.config["type_vocab_size"] = len(text_processor.languages)
+        self.config = BertConfig(**self.config)
+        self.encoder = BertEncoderModel(self.config)
+        self.encoder.init_weights()
+        self.input_attention = nn.Linear(self.config.hidden_size, 1)
+        self.decoder = nn.Linear(self.config.hidden_size, self.REGIONS * self.config.hidden_size)
+        self._imt_compute_dtype = torch.float32
+        self._link_stacks()
+
+    def _link_stacks(self):
+        self.encoder.__dict__["_imt_owner"] = weakref.ref(self)
+
+    def flat_param_order(self):
+        """The order in which the gradients become final: the linear layer, the pooling vector, the encoder from the top."""
+        ps = [self.decoder.weight, self.decoder.bias, self.input_attention.weight, self.input_attention.bias]
+        for lyr in reversed(list(self.encoder.encoder.layer)):
+            ps += lyr.ordered_params()
+        e = self.encoder.embeddings
+        return ps + [e.LayerNorm.weight, e.LayerNorm.bias, e.position_embeddings.weight, e.token_type_embeddings.weight,
+                     e.word_embeddings.weight]
+
+    @property
+    def _device(self):
+        return self.encoder.embeddings.word_embeddings.weight.device
+
+    def encode(self, src_inputs, src_mask, src_langs):
+        device = self._device
+        if src_inputs.device != device:
+            src_inputs = src_inputs.to(device)
+            src_mask = src_mask.to(device)
+            src_langs = src_langs.to(device)
+        encoder_states = self.encoder(src_inputs, attention_mask=src_mask, token_type_ids=src_langs)
+        return (encoder_states, None)
+
+    def forward(self, src_inputs, src_mask, src_langs):
+        """[B, 49 * d] in the compute dtype: encoder stack -> dropout (training) + attention pooling, one kernel -> linear."""
+        un = ImageMassSeq2Seq._un
+        src_inputs, src_mask, src_langs = un(src_inputs), un(src_mask), un(src_langs)
+        device = self._device
+        src_langs = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1)).to(device)
+        src_inputs, src_mask = src_inputs.to(device), src_mask.to(device)
+        encoder_states = self.encode(src_inputs, src_mask, src_langs)[0]
+        p = float(self.config.hidden_dropout_prob) if self.training else 0.0
+        seed = dropout_seed(self, p > 0)
+        anchor = store_of(self).ensure().anchor_if_grad()
+        sentence_embeddings = _SentPoolFn.apply(anchor, encoder_states, src_mask, self, p, seed)
+        return _LinearFn.apply(sentence_embeddings, self.decoder.weight, self.decoder.bias, self)
+
+    def loss_fused(self, src_inputs, src_mask, src_langs, image_encoding):
+        """(loss, number of images): |forward(...) - image_encoding|_2 / B (src/train_txt2image.py:62-67).  ``image_encoding``
+        ([B, 49, d] or [B, 49 * d], e.g. ``ImageCaptioning(batch=..., encode_only=True)``) is a constant."""
+        pred = self(src_inputs, src_mask, src_langs)
+        target = ImageMassSeq2Seq._un(image_encoding).detach()
+        if target.size(0) != pred.size(0) or target.numel() != pred.numel():
+            raise ValueError("Caption2Image: image_encoding %s does not match the %d x %d predictions" % (tuple(target.shape), pred.size(0), pred.size(1)))
+        target = target.reshape(pred.shape).to(device=pred.device, dtype=pred.dtype).contiguous()
+        return _L2DistFn.apply(pred, target), int(pred.size(0))
+
+    def save(self, out_dir: str):
+        if not os.path.exists(out_dir):
+            os.makedirs(out_dir)
+        with open(os.path.join(out_dir, "mt_config"), "wb") as fp:
+            pickle.dump((self.enc_layer, self.embed_dim, self.intermediate_dim), fp)
+        torch.save({k: v.detach().cpu() for k, v in self.state_dict().items()}, os.path.join(out_dir, "mt_model.state_dict"))
+        # build extension (the reference hard-codes 12 heads): beside the reference's files, as Seq2Seq.save does
+        with open(os.path.join(out_dir, "imt_config.json"), "w") as fp:
+            json.dump({"num_attention_heads": int(self.config.num_attention_heads)}, fp)
+
+    @staticmethod
+    def load(out_dir: str, tok_dir: str, text_processor=None):
+        if text_processor is None:
+            from .textprocessor import TextProcessor
+            text_processor = TextProcessor(tok_model_path=tok_dir)
+        from .safe_pickle import load_caption2image_config
+        enc_layer, embed_dim, intermediate_dim = load_caption2image_config(os.path.join(out_dir, "mt_config"))
+        kw = {}
+        extra = os.path.join(out_dir, "imt_config.json")
+        if os.path.exists(extra):  # absent in a directory the reference wrote: its 12 heads
+            with open(extra, "r") as fp:
+                kw["num_attention_heads"] = int(json.load(fp).get("num_attention_heads", 12))
+        mt_model = Caption2Image(text_processor=text_processor, enc_layer=enc_layer, embed_dim=embed_dim,
+                                 intermediate_dim=intermediate_dim, **kw)
+        sd = torch.load(os.path.join(out_dir, "mt_model.state_dict"), map_location="cpu", weights_only=True)
+        mt_model.load_state_dict(sd, strict=False)
+        return mt_model.to(torch.device("cuda" if torch.cuda.is_available() else "cpu"))

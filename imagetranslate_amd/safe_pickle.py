@@ -1,5 +1,5 @@
-"""Reading the reference's two pickled side files -- ``mt_config`` (a 9-tuple of bool/int, src/seq2seq.py:183-196) and
-the tokenizer directory's ``langs`` (Dict[str, int], src/textprocessor.py:42-45) -- without executing anything from the
+"""Reading the reference's pickled side files -- ``mt_config`` (a 9-tuple of bool/int, src/seq2seq.py:183-196; a 3-tuple of
+int for Caption2Image, src/image_model.py:445-446) and the tokenizer directory's ``langs`` (Dict[str, int], src/textprocessor.py:42-45) -- without executing anything from the
 file: an Unpickler whose ``find_class`` always refuses.  Builtin containers and scalars need no class lookup, so the
 reference's files load unchanged; a pickle that names any global (the vehicle of pickle code execution) is rejected.
 """
@@ -23,6 +23,15 @@ def load_mt_config(path):
         cfg = load_plain(fp)
     if not isinstance(cfg, tuple) or len(cfg) != 9 or not all(isinstance(v, (bool, int)) for v in cfg):
         raise ValueError("%s: expected the reference's 9-tuple of bool/int, got %r" % (path, type(cfg)))
+    return cfg
+
+
+def load_caption2image_config(path):
+    """(enc_layer, embed_dim, intermediate_dim) of a Caption2Image directory (src/image_model.py:445-446)"""
+    with open(path, "rb") as fp:
+        cfg = load_plain(fp)
+    if not isinstance(cfg, tuple) or len(cfg) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) for v in cfg):
+        raise ValueError("%s: expected the reference's 3-tuple of int, got %r" % (path, type(cfg)))
     return cfg
 
 

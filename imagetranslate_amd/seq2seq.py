@@ -113,7 +113,61 @@ class _FusedXentFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
-class Seq2Seq(nn.Module):
+class FlatStoreModel(nn.Module):
+    """What a top-level model whose parameters live in one flat store (param_store.py) needs besides its layers: the store is
+    invalidated by device / dtype moves and by module or parameter assignment, ``set_compute_dtype`` picks fp32 or bf16
+    compute, ``zero_grad`` / ``state_dict`` / ``load_state_dict`` order themselves against an overlapped optimizer step.
+    A subclass sets ``_imt_compute_dtype`` at the end of its constructor and provides ``_link_stacks()`` (which makes its
+    sub-modules find the model, ``param_store.store_of``)."""
+
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        self._link_stacks()
+        st = self.__dict__.get("_imt_flat_store")
+        if st is not None:
+            st.flat = None  # layout invalid after a device / dtype move; rebuilt lazily
+        return out
+
+    def __setattr__(self, name, value):
+        super().__setattr__(name, value)
+        if isinstance(value, (nn.Module, nn.Parameter)):
+            st = self.__dict__.get("_imt_flat_store")
+            if st is not None:
+                st.mark_dirty()  # the set of parameters may have changed: next use re-validates the flat store in full
+        if isinstance(value, nn.Module) and "_imt_compute_dtype" in self.__dict__:
+            self._link_stacks()  # e.g. caption_model.encoder = mt_model.encoder (train_captioning.py:218-220)
+
+    def set_compute_dtype(self, dtype):
+        if dtype in (torch.float16, "fp16", "bf16"):
+            dtype = torch.bfloat16  # the reference's --fp16 (apex amp O2) maps to bf16 MFMA on MI355X
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("compute dtype must be torch.float32 or torch.bfloat16")
+        self._imt_compute_dtype = dtype
+        return self
+
+    def zero_grad(self, set_to_none: bool = False):
+        st = self.__dict__.get("_imt_flat_store")
+        if st is not None and st.flat is not None:
+            st.zero_grad()
+            st.attach_grad_views()
+        else:
+            super().zero_grad(set_to_none=set_to_none)
+
+    def state_dict(self, *args, **kwargs):
+        st = self.__dict__.get("_imt_flat_store")
+        if st is not None:
+            st.wait_updates(0)  # an overlapped optimizer step (side stream) must have landed before parameters are read
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        st = self.__dict__.get("_imt_flat_store")
+        if st is not None:
+            st.wait_updates(0)  # copies into parameter views must not race an optimizer step on its side stream
+            st.mark_master_changed()
+        return super().load_state_dict(state_dict, *args, **kwargs)
+
+
+class Seq2Seq(FlatStoreModel):
     def __init__(self, text_processor, lang_dec: bool = True, use_proposals=False, tie_embed=False,
                  enc_layer: int = 6, dec_layer: int = 3, embed_dim: int = 768, intermediate_dim: int = 3072,
                  freeze_image: bool = False, resnet_depth: int = 1, use_obj: bool = False, *,
@@ -233,39 +287,6 @@ class Seq2Seq(nn.Module):
             ps += [lyr.crossattention.self.key.bias, lyr.crossattention.self.value.bias]
         ps += [dec.embeddings.LayerNorm.weight, dec.embeddings.LayerNorm.bias]
         return ps
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._link_stacks()
-        st = self.__dict__.get("_imt_flat_store")
-        if st is not None:
-            st.flat = None  # layout invalid after a device / dtype move; rebuilt lazily
-        return out
-
-    def __setattr__(self, name, value):
-        super().__setattr__(name, value)
-        if isinstance(value, (nn.Module, nn.Parameter)):
-            st = self.__dict__.get("_imt_flat_store")
-            if st is not None:
-                st.mark_dirty()  # the set of parameters may have changed: next use re-validates the flat store in full
-        if isinstance(value, nn.Module) and "_imt_compute_dtype" in self.__dict__:
-            self._link_stacks()  # e.g. caption_model.encoder = mt_model.encoder (train_captioning.py:218-220)
-
-    def set_compute_dtype(self, dtype):
-        if dtype in (torch.float16, "fp16", "bf16"):
-            dtype = torch.bfloat16  # the reference's --fp16 (apex amp O2) maps to bf16 MFMA on MI355X
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("compute dtype must be torch.float32 or torch.bfloat16")
-        self._imt_compute_dtype = dtype
-        return self
-
-    def zero_grad(self, set_to_none: bool = False):
-        st = self.__dict__.get("_imt_flat_store")
-        if st is not None and st.flat is not None:
-            st.zero_grad()
-            st.attach_grad_views()
-        else:
-            super().zero_grad(set_to_none=set_to_none)
 
     @property
     def _device(self):
@@ -484,19 +505,6 @@ class Seq2Seq(nn.Module):
         logprob, _, scores = O.score_rows(rows.contiguous(), weight, bias, targets.contiguous(), seg_offsets=offsets,
                                           normalize=normalize)
         return (scores, logprob, offsets) if return_token_logprobs else scores
-
-    def state_dict(self, *args, **kwargs):
-        st = self.__dict__.get("_imt_flat_store")
-        if st is not None:
-            st.wait_updates(0)  # an overlapped optimizer step (side stream) must have landed before parameters are read
-        return super().state_dict(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, *args, **kwargs):
-        st = self.__dict__.get("_imt_flat_store")
-        if st is not None:
-            st.wait_updates(0)  # copies into parameter views must not race an optimizer step on its side stream
-            st.mark_master_changed()
-        return super().load_state_dict(state_dict, *args, **kwargs)
 
     def save(self, out_dir: str):
         if not os.path.exists(out_dir):

@@ -436,6 +436,32 @@ int imt_attn_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* ma
 int imt_contrastive(const float* img, const float* txt, float* loss, float* d_img, float* d_txt, float* ws, int B, int N, int d,
                     void* stream);
 
+/* ------------------------------------------------------------------ tail of Caption2Image (src/image_model.py:430-438) and
+ * its loss (src/train_txt2image.py:67).
+ * imt_sent_pool_fwd, one workgroup per sentence of x [rows, S, d] (`dtype`, contiguous): xd = dropout(x), the keep decision of an
+ *   element being the one imt_add_rows_dropout makes for that element of the flattened [rows * S, d] tensor under the same seed
+ *   (dropout_p == 0: nothing is drawn); score_s = xd_s . w + b (w [d], b [1] in `dtype`), set to exactly -10000 where mask
+ *   ([rows, S] bytes, NULL = no mask) is 0; p = softmax_s(score); v = sum_s p_s xd_s.  No normalisation.  Outputs: v [rows, d] in
+ *   `dtype` (it feeds a GEMM) and probs [rows, S] fp32.  Reads x once or twice as imt_attn_pool_plan says; every sum is fp32 in a
+ *   fixed order.
+ * imt_sent_pool_bwd: dv [rows, d] in `dtype` and the saved probs -> dx [rows, S, d] in `dtype` (OVERWRITTEN; the dropout mask is
+ *   regenerated from the seed), and dw [d] / db [1] ACCUMULATED into fp32 through ws (rows * d + rows floats) and a second launch
+ *   that adds the per-sentence partials in sentence order: two identical calls give bit-identical results.
+ * imt_l2_dist: pred, target [B, n] in `dtype` (contiguous); loss[0] = sqrt(sum (pred - target)^2) / B in fp32 and
+ *   dpred = (pred - target) / (sqrt(sum) B) in `dtype`, all zeros when the sum is 0.  ws: IMT_L2_DIST_PARTS floats (per-workgroup
+ *   partial sums, added in index order).
+ * Refused before any launch with IMT_ERR_BAD_ARG: a NULL tensor, a dtype other than IMT_F32 / IMT_BF16, S < 1, S > IMT_POOL_MAX_S,
+ * d not a multiple of 4 or above IMT_POOL_MAX_D, dropout_p outside [0, 1), n not a positive multiple of 4, B < 1.  rows == 0
+ * returns IMT_OK without a launch. */
+#define IMT_L2_DIST_PARTS 256
+int imt_sent_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, void* v, float* probs,
+                      int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed, void* stream);
+int imt_sent_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* probs, const void* dv, void* dx,
+                      float* dw, float* db, float* ws, int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed,
+                      void* stream);
+int imt_l2_dist(int dtype, const void* pred, const void* target, float* loss, void* dpred, float* ws, int B, int64_t n,
+                void* stream);
+
 
 /* ------------------------------------------------------------------ whole encoder / decoder stacks
  * The host-side runtime that chains the kernels above for BertEncoderModel.forward (src/bert_seq2seq.py:103-144)
