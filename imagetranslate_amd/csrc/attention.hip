@@ -1156,7 +1156,7 @@ __global__ __launch_bounds__(512, 2) void attn_qkv_fwd_kernel(AttnP p, QkvP g) {
 
 int check_args(const imt_attn_args* a, bool bwd) {
   IMT_CHECK_ARG(a != nullptr, "attention: null args");
-  IMT_CHECK_ARG(a->dtype == IMT_F32 || a->dtype == IMT_BF16, "attention: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "attention: bad dtype");
   IMT_CHECK_ARG(a->head_dim == 32 || a->head_dim == 64, "attention: head_dim %d unsupported (32 or 64)", a->head_dim);
   IMT_CHECK_ARG(a->B > 0 && a->H > 0 && a->Tq > 0 && a->Tk > 0, "attention: bad dims");
   const int al = (a->dtype == IMT_BF16) ? 8 : 4;

@@ -84,16 +84,16 @@ extern "C" int imt_comm_init(const void* host_unique_id, int world_size, int ran
 
 extern "C" int imt_comm_allreduce(void* comm, void* buf, int64_t count, int dtype, void* stream) {
   IMT_CHECK_ARG(comm && (buf || count == 0) && count >= 0, "comm_allreduce: bad arguments");
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "comm_allreduce: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "comm_allreduce: bad dtype");
   if (count == 0) return IMT_OK;
   IMT_NEED_RCCL("comm_allreduce");
-  ImtProfScope prof("rccl_allreduce", 0.0, (double)count * (dtype == IMT_BF16 ? 2 : 4), (hipStream_t)stream);
+  ImtProfScope prof("rccl_allreduce", 0.0, (double)count * imt_dtype_bytes(dtype), (hipStream_t)stream);
   return rccl_check(g_rccl.all_reduce(buf, buf, (size_t)count, nccl_type(dtype), NCCL_SUM, (Comm)comm, (hipStream_t)stream), "ncclAllReduce");
 }
 
 extern "C" int imt_comm_broadcast(void* comm, void* buf, int64_t count, int dtype, int root, void* stream) {
   IMT_CHECK_ARG(comm && (buf || count == 0) && count >= 0 && root >= 0, "comm_broadcast: bad arguments");
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "comm_broadcast: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "comm_broadcast: bad dtype");
   if (count == 0) return IMT_OK;
   IMT_NEED_RCCL("comm_broadcast");
   return rccl_check(g_rccl.broadcast(buf, buf, (size_t)count, nccl_type(dtype), root, (Comm)comm, (hipStream_t)stream), "ncclBroadcast");

@@ -40,6 +40,14 @@ void imt_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int imt_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool imt_ok_dtype(int t) { return t == IMT_F32 || t == IMT_BF16; }
+static inline int imt_dtype_bytes(int t) { return t == IMT_BF16 ? 2 : 4; }
+// Host dispatch on a dtype already checked with imt_ok_dtype: returns f(tag), where `typename decltype(tag)::type` is float or
+// bf16_t -- the launch of a dtype-templated kernel is written once, in a generic lambda (two nested calls for two dtypes).
+template <typename T> struct ImtType { typedef T type; };
+template <typename F> static inline int imt_by_dtype(int dtype, F&& f) {
+  return dtype == IMT_F32 ? f(ImtType<float>()) : f(ImtType<bf16_t>());
+}
 
 bool imt_gemm_ln_ticket_enabled();  // gemm.hip: built with -DIMT_LN_TICKET=1 (imt_gemm's ln_out can normalise in-launch)
 // ---------------------------------------------------------------- optional launch profiler (core.hip)

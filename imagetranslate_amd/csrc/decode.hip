@@ -286,7 +286,7 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(imt_beam_args a) {
 
 extern "C" int imt_attention_decode(const imt_attn_decode_args* a, void* stream) {
   IMT_CHECK_ARG(a, "attention_decode: null args");
-  IMT_CHECK_ARG(a->dtype == IMT_F32 || a->dtype == IMT_BF16, "attention_decode: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "attention_decode: bad dtype");
   IMT_CHECK_ARG(a->head_dim == 32 || a->head_dim == 64, "attention_decode: head_dim %d unsupported (32 or 64)", a->head_dim);
   IMT_CHECK_ARG(a->R > 0 && a->H > 0 && a->n_keys > 0 && a->rep > 0 && a->R % a->rep == 0, "attention_decode: bad sizes");
   IMT_CHECK_ARG(a->Q && a->K && a->V && a->O, "attention_decode: null tensor");
@@ -296,7 +296,7 @@ extern "C" int imt_attention_decode(const imt_attn_decode_args* a, void* stream)
   hipStream_t st = (hipStream_t)stream;
   const int waves = a->R * a->H;
   const dim3 grid(imt_cdiv(waves, 4)), block(256);
-  const double es = a->dtype == IMT_BF16 ? 2 : 4;
+  const double es = imt_dtype_bytes(a->dtype);
   ImtProfScope prof("attn_decode", 4.0 * waves * a->n_keys * a->head_dim, 2.0 * waves * a->n_keys * a->head_dim * es, st);
   if (a->dtype == IMT_BF16) {
     if (a->head_dim == 64) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, 64>), grid, block, 0, st, *a);

@@ -1774,7 +1774,7 @@ extern "C" int imt_set_gemm_share_cus(int share_cus) {
 // Validate, pick a strategy, run it.
 extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
   IMT_CHECK_ARG(a != nullptr, "imt_gemm: null args");
-  IMT_CHECK_ARG(a->dtype == IMT_F32 || a->dtype == IMT_BF16, "imt_gemm: bad dtype %d", a->dtype);
+  IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "imt_gemm: bad dtype %d", a->dtype);
   IMT_CHECK_ARG(a->M >= 0 && a->N >= 0 && a->K >= 0, "imt_gemm: negative dims");
   if (a->M == 0 || a->N == 0) return IMT_OK;
   IMT_CHECK_ARG(a->A && a->B && a->C, "imt_gemm: null operand");
@@ -1820,7 +1820,7 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   bool ok = count <= MAX_GROUP;
   const int dtype = list[0].dtype;
-  const int bk = (dtype == IMT_BF16) ? 64 : 32, es = (dtype == IMT_BF16) ? 2 : 4, al = (dtype == IMT_BF16) ? 8 : 4;
+  const int bk = (dtype == IMT_BF16) ? 64 : 32, es = imt_dtype_bytes(dtype), al = (dtype == IMT_BF16) ? 8 : 4;
   int tiles = 0;
   for (int i = 0; i < count && ok; ++i) {
     const imt_gemm_args& a = list[i];

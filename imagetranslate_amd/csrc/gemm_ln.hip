@@ -280,18 +280,18 @@ int launch_gemm_ln(const GemmLnP& p, hipStream_t st) {
 }  // namespace
 
 extern "C" int imt_gemm_bias_residual_ln_supported(int dtype, int N, int K) {
-  const int es = dtype == IMT_BF16 ? 2 : 4;
-  return (dtype == IMT_F32 || dtype == IMT_BF16) && N >= 128 && N <= 512 && N % 128 == 0 && K > 0 && ((int64_t)K * es) % LN_RB == 0;  // whole 128-byte K tiles
+  const int es = imt_dtype_bytes(dtype);
+  return imt_ok_dtype(dtype) && N >= 128 && N <= 512 && N % 128 == 0 && K > 0 && ((int64_t)K * es) % LN_RB == 0;  // whole 128-byte K tiles
 }
 
 extern "C" int imt_gemm_bias_residual_ln(int dtype, const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias,
                                          const void* resid, int64_t ldr, const void* gamma, const void* beta, void* pre_ln,
                                          void* out, int64_t ldo, float* mean, float* rstd, int M, int N, int K, float eps,
                                          float dropout_p, uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "gemm_bias_residual_ln: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "gemm_bias_residual_ln: bad dtype");
   IMT_CHECK_ARG(imt_gemm_bias_residual_ln_supported(dtype, N, K), "gemm_bias_residual_ln: N must be 128, 256, 384 or 512 and K a whole number of 128-byte tiles (N=%d K=%d)", N, K);
   if (M <= 0) return IMT_OK;
-  const int es = dtype == IMT_BF16 ? 2 : 4, al = 16 / es;
+  const int es = imt_dtype_bytes(dtype), al = 16 / es;
   IMT_CHECK_ARG(x && w && gamma && beta && out, "gemm_bias_residual_ln: null pointer");
   IMT_CHECK_ARG(ldx % al == 0 && ldw % al == 0 && ldo % 4 == 0 && (!resid || ldr % 4 == 0), "gemm_bias_residual_ln: leading dimensions must keep rows 16-byte aligned");
   IMT_CHECK_ARG((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "gemm_bias_residual_ln: x / w must be 16-byte aligned");

@@ -239,31 +239,31 @@ extern "C" int imt_scaled_sum(const float* x, int n, float scale, float* out, vo
 
 extern "C" int imt_log_softmax_fwd(int dtype, const void* logits, int64_t ld, float* lp, int64_t ldlp, float* lse, int N,
                                    int V, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "log_softmax_fwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "log_softmax_fwd: bad dtype");
   if (N <= 0) return IMT_OK;
   IMT_CHECK_ARG(logits && lp && V > 0 && ld % 4 == 0 && ldlp % 4 == 0, "log_softmax_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
-  ImtProfScope prof("log_softmax_fwd", 0.0, (double)N * V * ((dtype == IMT_BF16 ? 2 : 4) + 4.0), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(log_softmax_fwd_kernel<float>, dim3(N), dim3(256), 0, st, (const float*)logits, ld, lp, ldlp, lse, V);
-  else
-    hipLaunchKernelGGL(log_softmax_fwd_kernel<bf16_t>, dim3(N), dim3(256), 0, st, (const bf16_t*)logits, ld, lp, ldlp, lse, V);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("log_softmax_fwd", 0.0, (double)N * V * (imt_dtype_bytes(dtype) + 4.0), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(log_softmax_fwd_kernel<T>, dim3(N), dim3(256), 0, st, (const T*)logits, ld, lp, ldlp, lse, V);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_log_softmax_bwd(const float* dlp, int64_t lddlp, const float* lp, int64_t ldlp, int out_dtype,
                                    void* dlogits, int64_t ld, int N, int V, void* stream) {
-  IMT_CHECK_ARG(out_dtype == IMT_F32 || out_dtype == IMT_BF16, "log_softmax_bwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(out_dtype), "log_softmax_bwd: bad dtype");
   if (N <= 0) return IMT_OK;
   IMT_CHECK_ARG(dlp && lp && dlogits && V > 0, "log_softmax_bwd: bad args");
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == IMT_F32)
-    hipLaunchKernelGGL(log_softmax_bwd_kernel<float>, dim3(N), dim3(256), 0, st, dlp, lddlp, lp, ldlp, (float*)dlogits, ld, V);
-  else
-    hipLaunchKernelGGL(log_softmax_bwd_kernel<bf16_t>, dim3(N), dim3(256), 0, st, dlp, lddlp, lp, ldlp, (bf16_t*)dlogits, ld, V);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return imt_by_dtype(out_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(log_softmax_bwd_kernel<T>, dim3(N), dim3(256), 0, st, dlp, lddlp, lp, ldlp, (T*)dlogits, ld, V);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_smoothed_nll_fwd(const float* lp, int64_t ldlp, const int64_t* target, float* loss, int N, int V,
@@ -286,23 +286,26 @@ extern "C" int imt_smoothed_nll_bwd(const float* dloss, const int64_t* target, f
 
 extern "C" int imt_xent_fused_fwd_bwd(int dtype, void* logits, int64_t ld, const int64_t* target, float* loss_rows, int N,
                                       int V, float epsilon, int64_t ignore_index, float grad_scale, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "xent_fused: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "xent_fused: bad dtype");
   if (N <= 0) return IMT_OK;
   IMT_CHECK_ARG(logits && target && loss_rows && V > 0 && ld % 4 == 0, "xent_fused: bad args");
   hipStream_t st = (hipStream_t)stream;
-  ImtProfScope prof("xent_fused", 0.0, 2.0 * N * V * (dtype == IMT_BF16 ? 2 : 4), st);
+  ImtProfScope prof("xent_fused", 0.0, 2.0 * N * V * imt_dtype_bytes(dtype), st);
   const int row_bytes = ((V * 2 + 15) / 16) * 16;
-  if (dtype == IMT_F32) {
-    hipLaunchKernelGGL(xent_fused_kernel<float>, dim3(N), dim3(256), 0, st, (float*)logits, ld, target, loss_rows, V, epsilon, ignore_index, grad_scale);
-  } else if (row_bytes <= 128 * 1024 && ld % 8 == 0 && !getenv("IMT_XENT_NO_LDS")) {
+  if (dtype == IMT_BF16 && row_bytes <= 128 * 1024 && ld % 8 == 0 && !getenv("IMT_XENT_NO_LDS")) {  // the bf16 row fits in LDS
     static bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xent_fused_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       attr_set = true;
     }
     hipLaunchKernelGGL(xent_fused_lds_kernel, dim3(N), dim3(256), row_bytes, st, (bf16_t*)logits, ld, target, loss_rows, V, epsilon, ignore_index, grad_scale);
-  } else
-    hipLaunchKernelGGL(xent_fused_kernel<bf16_t>, dim3(N), dim3(256), 0, st, (bf16_t*)logits, ld, target, loss_rows, V, epsilon, ignore_index, grad_scale);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  }
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(xent_fused_kernel<T>, dim3(N), dim3(256), 0, st, (T*)logits, ld, target, loss_rows, V, epsilon, ignore_index, grad_scale);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }

@@ -71,8 +71,6 @@ struct StackWs {
 
 constexpr int MAX_LAYERS = 64;
 
-int64_t esize(int dtype) { return dtype == IMT_BF16 ? 2 : 4; }
-
 // crossattention key|value weight / bias offsets of a layer (imt_layer_desc.cross_kv_*)
 int64_t kv_w_off(const imt_stack_desc* m, const imt_layer_desc& p) { return p.cross_kv_w >= 0 ? p.cross_kv_w : p.cross_attn.qkv_w + (int64_t)m->d * m->d; }
 int64_t kv_b_off(const imt_stack_desc* m, const imt_layer_desc& p) { return p.cross_kv_b >= 0 ? p.cross_kv_b : p.cross_attn.qkv_b + m->d; }
@@ -92,7 +90,7 @@ bool cross_kv_batched(const imt_stack_desc* m) {
 
 void carve(const imt_stack_desc* m, int B, int T, int Tk, void* ws, StackWs& w, LayerWs* layers) {
   Carver c(ws);
-  const int64_t N = (int64_t)B * T, Nk = (int64_t)B * Tk, d = m->d, ff = m->ff, es = esize(m->dtype);
+  const int64_t N = (int64_t)B * T, Nk = (int64_t)B * Tk, d = m->d, ff = m->ff, es = imt_dtype_bytes(m->dtype);
   w.emb_sum = c.take(N * d * es); w.emb_mean = (float*)c.take(N * 4); w.emb_rstd = (float*)c.take(N * 4);
   w.x0 = c.take(N * d * es);
   w.layers = layers;
@@ -380,7 +378,7 @@ int ffn_bwd(const Ctx& c, const imt_layer_desc& p, LayerWs& w, StackWs& sw, Defe
 
 int validate(const imt_stack_desc* m, const imt_stack_io* io, const void* ws, int64_t ws_bytes, StackWs& w, LayerWs* layers) {
   IMT_CHECK_ARG(m && io, "stack: null descriptor");
-  IMT_CHECK_ARG(m->dtype == IMT_F32 || m->dtype == IMT_BF16, "stack: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(m->dtype), "stack: bad dtype");
   IMT_CHECK_ARG(m->n_layers >= 0 && m->n_layers <= MAX_LAYERS && (m->n_layers == 0 || m->layers), "stack: bad layer table");
   IMT_CHECK_ARG(m->d > 0 && m->heads > 0 && m->d % m->heads == 0, "stack: hidden size %d not a multiple of heads %d", m->d, m->heads);
   const int dh = m->d / m->heads;
@@ -408,7 +406,7 @@ extern "C" int64_t imt_stack_workspace_bytes(const imt_stack_desc* m, int B, int
 extern "C" int imt_stack_forward(const imt_stack_desc* m, const imt_stack_io* io, void* ws, int64_t ws_bytes, void* stream) {
   StackWs w; LayerWs layers[MAX_LAYERS];
   RC(validate(m, io, ws, ws_bytes, w, layers));
-  Ctx c{m, (hipStream_t)stream, m->dtype, esize(m->dtype)};
+  Ctx c{m, (hipStream_t)stream, m->dtype, imt_dtype_bytes(m->dtype)};
   c.splitk = w.splitk; c.splitk_bytes = w.splitk_bytes;
   const int B = io->B, T = io->T, N = B * T, d = m->d;
   const bool training = io->training != 0;
@@ -461,7 +459,7 @@ extern "C" int imt_stack_backward(const imt_stack_desc* m, const imt_stack_io* i
   RC(validate(m, io, ws, ws_bytes, w, layers));
   IMT_CHECK_ARG(m->grads && io->d_out, "stack_backward: grads / d_out missing");
   IMT_CHECK_ARG(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= m->n_layers, "stack_backward: bad layer range");
-  Ctx c{m, (hipStream_t)stream, m->dtype, esize(m->dtype)};
+  Ctx c{m, (hipStream_t)stream, m->dtype, imt_dtype_bytes(m->dtype)};
   c.splitk = w.splitk; c.splitk_bytes = w.splitk_bytes;
   const int B = io->B, T = io->T, N = B * T, d = m->d;
   const bool training = io->training != 0;
@@ -573,7 +571,7 @@ bool fused_decode_shape(const imt_stack_desc* m) {
 
 void carve_decode(const imt_stack_desc* m, int r_max, void* ws, DecodeWs& w) {
   Carver c(ws);
-  const int64_t R = r_max, d = m->d, ff = m->ff, es = esize(m->dtype);
+  const int64_t R = r_max, d = m->d, ff = m->ff, es = imt_dtype_bytes(m->dtype);
   w.emb_sum = c.take(R * d * es); w.x = c.take(R * d * es); w.ctx = c.take(R * d * es); w.pre_ln = c.take(R * d * es);
   w.a = c.take(R * d * es); w.q = c.take(R * d * es); w.b = c.take(R * d * es);
   w.h = c.take(R * ff * es); w.z = c.take(R * ff * es);
@@ -591,7 +589,7 @@ void carve_decode(const imt_stack_desc* m, int r_max, void* ws, DecodeWs& w) {
 
 int validate_decoder(const imt_stack_desc* m) {
   IMT_CHECK_ARG(m, "decode: null descriptor");
-  IMT_CHECK_ARG(m->dtype == IMT_F32 || m->dtype == IMT_BF16, "decode: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(m->dtype), "decode: bad dtype");
   IMT_CHECK_ARG(m->is_decoder, "decode: stack is not a decoder");
   IMT_CHECK_ARG(m->n_layers > 0 && m->n_layers <= MAX_LAYERS && m->layers, "decode: bad layer table");
   IMT_CHECK_ARG(m->d > 0 && m->heads > 0 && m->d % m->heads == 0, "decode: hidden size %d not a multiple of heads %d", m->d, m->heads);
@@ -614,17 +612,17 @@ extern "C" int64_t imt_decode_workspace_bytes(const imt_stack_desc* m, int r_max
 }
 extern "C" int64_t imt_decode_self_cache_bytes(const imt_stack_desc* m, int r_max, int t_max) {
   if (!m || r_max <= 0 || t_max <= 0) return -1;
-  return (int64_t)m->n_layers * r_max * t_max * 3 * m->d * esize(m->dtype);
+  return (int64_t)m->n_layers * r_max * t_max * 3 * m->d * imt_dtype_bytes(m->dtype);
 }
 extern "C" int64_t imt_decode_cross_bytes(const imt_stack_desc* m, int B, int Tk) {
   if (!m || B <= 0 || Tk <= 0) return -1;
-  return (int64_t)m->n_layers * B * Tk * 2 * m->d * esize(m->dtype);
+  return (int64_t)m->n_layers * B * Tk * 2 * m->d * imt_dtype_bytes(m->dtype);
 }
 
 extern "C" int imt_decode_begin(const imt_stack_desc* m, const void* enc_states, int B, int Tk, void* cross_kv, void* stream) {
   RC(validate_decoder(m));
   IMT_CHECK_ARG(enc_states && cross_kv && B > 0 && Tk > 0, "decode_begin: bad arguments");
-  Ctx c{m, (hipStream_t)stream, m->dtype, esize(m->dtype)};
+  Ctx c{m, (hipStream_t)stream, m->dtype, imt_dtype_bytes(m->dtype)};
   const int d = m->d;
   const int64_t per_layer = (int64_t)B * Tk * 2 * d;
   for (int l = 0; l < m->n_layers; ++l) {
@@ -664,7 +662,7 @@ extern "C" int imt_decode_step(const imt_stack_desc* m, const imt_decode_io* io,
   carve_decode(m, io->r_max, ws, w);
   IMT_CHECK_ARG(ws && ws_bytes >= w.bytes, "decode_step: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)w.bytes);
   IMT_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decode_step: workspace must be 256-B aligned");
-  Ctx c{m, (hipStream_t)stream, m->dtype, esize(m->dtype)};
+  Ctx c{m, (hipStream_t)stream, m->dtype, imt_dtype_bytes(m->dtype)};
   c.splitk = w.splitk; c.splitk_bytes = w.splitk_bytes;
   const int R = io->R, d = m->d, ff = m->ff, H = m->heads, dh = d / H;
   const int64_t row3 = (int64_t)io->t_max * 3 * d;                       // one cache row (all positions)

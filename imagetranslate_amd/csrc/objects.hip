@@ -197,14 +197,12 @@ __global__ __launch_bounds__(256) void gated_mix_bwd_fold_kernel(const float* __
   dgate[c] += s;
 }
 
-inline bool ok_dtype(int t) { return t == IMT_F32 || t == IMT_BF16; }
-
 }  // namespace
 
 extern "C" int imt_obj_rows(int feat_dtype, int dtype, const int64_t* labels, const void* feats, const float* boxes,
                             const void* emb, const void* w, void* x_out, void* w_out, int64_t R, int d, int Kp, int* status,
                             void* stream) {
-  IMT_CHECK_ARG(ok_dtype(feat_dtype) && ok_dtype(dtype), "obj_rows: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(feat_dtype) && imt_ok_dtype(dtype), "obj_rows: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0 && d <= 4096, "obj_rows: d must be a positive multiple of 4 (at most 4096)");
   IMT_CHECK_ARG(Kp >= d + IMT_OBJ_FEAT_DIM + 7 && Kp % 8 == 0, "obj_rows: Kp must be >= d + 1031 and a multiple of 8");
   IMT_CHECK_ARG(R >= 0, "obj_rows: negative row count");
@@ -214,23 +212,24 @@ extern "C" int imt_obj_rows(int feat_dtype, int dtype, const int64_t* labels, co
   hipStream_t st = (hipStream_t)stream;
   const int row_blocks = imt_cdiv(R, ROWS_PER_BLOCK);
   const int w_blocks = w_out ? imt_cdiv(d, ROWS_PER_BLOCK) : 0;
-  const int T_bytes = dtype == IMT_BF16 ? 2 : 4;
-  ImtProfScope prof("obj_rows", 0.0, (double)R * Kp * T_bytes + (double)R * IMT_OBJ_FEAT_DIM * (feat_dtype == IMT_BF16 ? 2 : 4) +
+  const int T_bytes = imt_dtype_bytes(dtype);
+  ImtProfScope prof("obj_rows", 0.0, (double)R * Kp * T_bytes + (double)R * IMT_OBJ_FEAT_DIM * imt_dtype_bytes(feat_dtype) +
                                       (w_out ? 2.0 * d * Kp * T_bytes : 0.0), st);
   const dim3 grid(row_blocks + w_blocks);
-#define IMT_OR(TF, T) hipLaunchKernelGGL((obj_rows_kernel<TF, T>), grid, dim3(256), 0, st, labels, (const TF*)feats, boxes, (const T*)emb, \
-                                         (const T*)w, (T*)x_out, (T*)w_out, R, d, Kp, row_blocks, status)
-  if (feat_dtype == IMT_F32 && dtype == IMT_F32) IMT_OR(float, float);
-  else if (feat_dtype == IMT_F32) IMT_OR(float, bf16_t);
-  else if (dtype == IMT_F32) IMT_OR(bf16_t, float);
-  else IMT_OR(bf16_t, bf16_t);
-#undef IMT_OR
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return imt_by_dtype(feat_dtype, [&](auto feat_tag) {
+    return imt_by_dtype(dtype, [&](auto tag) {
+      using TF = typename decltype(feat_tag)::type;
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((obj_rows_kernel<TF, T>), grid, dim3(256), 0, st, labels, (const TF*)feats, boxes, (const T*)emb, (const T*)w,
+                         (T*)x_out, (T*)w_out, R, d, Kp, row_blocks, status);
+      IMT_CHECK_LAUNCH();
+      return IMT_OK;
+    });
+  });
 }
 
 extern "C" int imt_relu_dropout(int dtype, void* y, int64_t rows, int d, float dropout_p, uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "relu_dropout: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "relu_dropout: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "relu_dropout: d must be a multiple of 4");
   IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "relu_dropout: dropout_p outside [0, 1)");
   if (rows <= 0) return IMT_OK;
@@ -239,16 +238,18 @@ extern "C" int imt_relu_dropout(int dtype, void* y, int64_t rows, int d, float d
   const dim3 grid(imt_cdiv(rows, ROWS_PER_BLOCK));
   const uint32_t th = dropout_thresh(dropout_p);
   const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  ImtProfScope prof("relu_dropout", 0.0, 2.0 * rows * d * (dtype == IMT_BF16 ? 2 : 4), st);
-  if (dtype == IMT_F32) hipLaunchKernelGGL(relu_dropout_kernel<float>, grid, dim3(256), 0, st, (float*)y, rows, d, th, ik, dropout_seed);
-  else hipLaunchKernelGGL(relu_dropout_kernel<bf16_t>, grid, dim3(256), 0, st, (bf16_t*)y, rows, d, th, ik, dropout_seed);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("relu_dropout", 0.0, 2.0 * rows * d * imt_dtype_bytes(dtype), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_dropout_kernel<T>, grid, dim3(256), 0, st, (T*)y, rows, d, th, ik, dropout_seed);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_relu_dropout_bwd(int dtype, const void* dy, const void* y, void* dz, int64_t rows, int d, float dropout_p,
                                     uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "relu_dropout_bwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "relu_dropout_bwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "relu_dropout_bwd: d must be a multiple of 4");
   IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "relu_dropout_bwd: dropout_p outside [0, 1)");
   if (rows <= 0) return IMT_OK;
@@ -257,13 +258,13 @@ extern "C" int imt_relu_dropout_bwd(int dtype, const void* dy, const void* y, vo
   const dim3 grid(imt_cdiv(rows, ROWS_PER_BLOCK));
   const uint32_t th = dropout_thresh(dropout_p);
   const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  ImtProfScope prof("relu_dropout_bwd", 0.0, 3.0 * rows * d * (dtype == IMT_BF16 ? 2 : 4), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(relu_dropout_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)dy, (const float*)y, (float*)dz, rows, d, th, ik, dropout_seed);
-  else
-    hipLaunchKernelGGL(relu_dropout_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dz, rows, d, th, ik, dropout_seed);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("relu_dropout_bwd", 0.0, 3.0 * rows * d * imt_dtype_bytes(dtype), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_dropout_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)dy, (const T*)y, (T*)dz, rows, d, th, ik, dropout_seed);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_obj_fold_w(const float* dw_pad, float* grad, int d, int Kp, void* stream) {
@@ -280,39 +281,40 @@ extern "C" int imt_obj_fold_w(const float* dw_pad, float* grad, int d, int Kp, v
 
 extern "C" int imt_obj_embed_grad(int dtype, const int64_t* labels, const void* dx, int64_t ldx, float* grad, int64_t R, int d,
                                   void* stream) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "obj_embed_grad: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "obj_embed_grad: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0 && d <= 4096, "obj_embed_grad: d must be a positive multiple of 4 (at most 4096)");
   IMT_CHECK_ARG(ldx >= d && ldx % 4 == 0, "obj_embed_grad: ldx must be >= d and a multiple of 4");
   if (R <= 0) return IMT_OK;
   IMT_CHECK_ARG(labels && dx && grad, "obj_embed_grad: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  ImtProfScope prof("obj_embed_grad", 0.0, 8.0 * R * (IMT_OBJ_LABELS - 1) + (double)R * d * (dtype == IMT_BF16 ? 2 : 4), st);
+  ImtProfScope prof("obj_embed_grad", 0.0, 8.0 * R * (IMT_OBJ_LABELS - 1) + (double)R * d * imt_dtype_bytes(dtype), st);
   const dim3 grid(IMT_OBJ_LABELS - 1);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(obj_embed_grad_kernel<float>, grid, dim3(256), 0, st, labels, (const float*)dx, ldx, grad, R, d);
-  else
-    hipLaunchKernelGGL(obj_embed_grad_kernel<bf16_t>, grid, dim3(256), 0, st, labels, (const bf16_t*)dx, ldx, grad, R, d);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(obj_embed_grad_kernel<T>, grid, dim3(256), 0, st, labels, (const T*)dx, ldx, grad, R, d);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_gated_mix_bwd(int dtype, const void* dy, const void* a, const void* b, const void* gate, void* da, void* db,
                                  float* dgate, float* partial_ws, int64_t rows, int d, void* stream) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "gated_mix_bwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "gated_mix_bwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "gated_mix_bwd: d must be a multiple of 4");
   if (rows <= 0) return IMT_OK;
   IMT_CHECK_ARG(dy && a && b && gate && da && db && dgate && partial_ws, "gated_mix_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int64_t rpp = (rows + IMT_GATED_MIX_BWD_PARTS - 1) / IMT_GATED_MIX_BWD_PARTS;
-  ImtProfScope prof("gated_mix_bwd", 0.0, 5.0 * rows * d * (dtype == IMT_BF16 ? 2 : 4), st);
+  ImtProfScope prof("gated_mix_bwd", 0.0, 5.0 * rows * d * imt_dtype_bytes(dtype), st);
   // parts past the last row write zero partial sums (their row range is empty)
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(gated_mix_bwd_kernel<float>, dim3(IMT_GATED_MIX_BWD_PARTS), dim3(256), 0, st, (const float*)dy, (const float*)a,
-                       (const float*)b, (const float*)gate, (float*)da, (float*)db, partial_ws, rows, d, rpp);
-  else
-    hipLaunchKernelGGL(gated_mix_bwd_kernel<bf16_t>, dim3(IMT_GATED_MIX_BWD_PARTS), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)a,
-                       (const bf16_t*)b, (const bf16_t*)gate, (bf16_t*)da, (bf16_t*)db, partial_ws, rows, d, rpp);
-  IMT_CHECK_LAUNCH();
+  const int rc = imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gated_mix_bwd_kernel<T>, dim3(IMT_GATED_MIX_BWD_PARTS), dim3(256), 0, st, (const T*)dy, (const T*)a, (const T*)b,
+                       (const T*)gate, (T*)da, (T*)db, partial_ws, rows, d, rpp);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
+  if (rc != IMT_OK) return rc;
   hipLaunchKernelGGL(gated_mix_bwd_fold_kernel, dim3(imt_cdiv(d, 256)), dim3(256), 0, st, partial_ws, dgate, d);
   IMT_CHECK_LAUNCH();
   return IMT_OK;

@@ -10,6 +10,12 @@
 // pass that writes dx and accumulates dw the second.  All statistics and sums are fp32 and every reduction has a fixed order
 // (wave butterflies, then partial sums added in index order; dw / db as per-sentence partials folded in sentence order by a
 // second launch): the same call on the same data gives the same bits.
+//
+// Sentence pooling of Caption2Image (src/image_model.py:430-436) is the same four phases -- row scores, masked softmax, weighted
+// sum, store -- on xd = dropout(x) (training), without the normalisation, and v is written in the compute dtype (it feeds the
+// decoder GEMM).  One kernel pair serves both, templated on the kind; LDS keeps the RAW sentence either way, the dropout factor
+// of an element is recomputed from its index wherever the element is used.
+#include <type_traits>
 #include "common.hpp"
 #include <math.h>
 
@@ -17,12 +23,13 @@ namespace {
 
 constexpr int POOL_THREADS = 256;
 constexpr int POOL_PART_FLOATS = 1024;  // column-group partial sums: (256 / (d / 4)) groups x d floats <= 1024
+enum PoolKind { POOL_UNIT, POOL_SENT };  // unit vectors u = v / (|v| + 1e-4) in fp32 | v of dropout(x) in the compute dtype
+template <typename T, int KIND> using pool_out_t = typename std::conditional<KIND == POOL_UNIT, float, T>::type;  // of u / du | v / dv
 
-inline bool ok_dtype(int t) { return t == IMT_F32 || t == IMT_BF16; }
 inline int round4(int s) { return (s + 3) & ~3; }
 // LDS besides x: reduction scratch, two per-position arrays (scores / probabilities), the partial sums, one d-vector
 inline int64_t pool_small_bytes(int S, int d) { return 64 + 2 * (int64_t)round4(S) * 4 + POOL_PART_FLOATS * 4 + (int64_t)d * 4; }
-inline int64_t pool_x_bytes(int dtype, int S, int d) { return (int64_t)S * d * (dtype == IMT_BF16 ? 2 : 4); }
+inline int64_t pool_x_bytes(int dtype, int S, int d) { return (int64_t)S * d * imt_dtype_bytes(dtype); }
 
 struct PoolLds {
   float* red; float* sc; float* pr; float* part; float* vec; unsigned char* xs;
@@ -104,9 +111,7 @@ IMT_DEVICE void row_dots(const T* __restrict__ xr, const TV* __restrict__ vec, T
   }
 }
 
-// l.sc[s]: x_s . w  ->  p_s = softmax over s of (x_s . w + bias, or exactly -10000 where mask is 0); also written to probs.  The
-// statements of attn_pool_fwd_kernel's softmax, for the sentence pooling below (that kernel keeps its own copy: as a call the
-// compiler schedules it differently, and its machine code is kept as it was).
+// l.sc[s]: x_s . w  ->  p_s = softmax over s of (x_s . w + bias, or exactly -10000 where mask is 0); also written to probs
 IMT_DEVICE void pool_softmax(const PoolLds& l, const uint8_t* __restrict__ mask, float* __restrict__ probs, float bias, int64_t row,
                              int S) {
   const int t = threadIdx.x;
@@ -133,96 +138,99 @@ IMT_DEVICE void pool_softmax(const PoolLds& l, const uint8_t* __restrict__ mask,
   __syncthreads();
 }
 
-template <typename T>
-__global__ __launch_bounds__(POOL_THREADS) void attn_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
-                                                                     const uint8_t* __restrict__ mask, float* __restrict__ u,
-                                                                     float* __restrict__ probs, float* __restrict__ norm, int S, int d,
-                                                                     int keep_x) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const PoolLds l = pool_lds(smem, S, d);
-  T* xs = reinterpret_cast<T*>(l.xs);
-  const int64_t row = blockIdx.x;
-  const T* xr = x + row * S * d;
-  const int t = threadIdx.x;
-  // scores (first read of x)
-  row_dots<T, T>(xr, w, xs, l.sc, S, d, keep_x != 0);
-  __syncthreads();
-  const float bias = to_f32<T>(b[0]);
-  float m = -INFINITY;
-  for (int s = t; s < S; s += POOL_THREADS) {
-    const float v = (mask && !mask[row * S + s]) ? -10000.0f : l.sc[s] + bias;
-    l.sc[s] = v;
-    m = fmaxf(m, v);
-  }
-  m = block_max(m, l.red);
-  float sum = 0.f;
-  for (int s = t; s < S; s += POOL_THREADS) {
-    const float e = expf(l.sc[s] - m);
-    l.sc[s] = e;
-    sum += e;
-  }
-  sum = block_sum(sum, l.red);
-  const float inv = 1.0f / sum;
-  for (int s = t; s < S; s += POOL_THREADS) {
-    const float p = l.sc[s] * inv;
-    l.sc[s] = p;
-    probs[row * S + s] = p;
-  }
-  __syncthreads();
-  // weighted sum: thread (g, cg) adds positions g, g + G, ... of column group cg; the G partial vectors are added in order
-  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
+// The sums over s (v in the forward, dw in the backward) use a column-group layout: thread t = (g, cg), cg = t % (d/4),
+// g = t / (d/4) < G = 256 / (d/4), adds positions g, g + G, ... of columns cg * 4 .. cg * 4 + 3 into its acc.  This adds the G
+// partial vectors of every column group in the order g = 0, 1, ...: threads t < d / 4 return the total of column group t, the
+// others zeros; every thread must call.
+IMT_DEVICE f32x4 colgroup_fold(const PoolLds& l, int d, f32x4 acc) {
+  const int t = threadIdx.x, ncol4 = d >> 2, G = POOL_THREADS / ncol4;
   const int cg = t % ncol4, g = t / ncol4;
-  if (g < G) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int s = g; s < S; s += G) {
-      const f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
-      acc += xv * l.sc[s];
-    }
-    Vec4<float>::store(l.part + g * d + cg * 4, acc);
-  }
+  if (g < G) Vec4<float>::store(l.part + g * d + cg * 4, acc);
   __syncthreads();
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if (t < ncol4)
     for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
-  const float ss = block_sum(dot4(v, v), l.red);
-  const float r = sqrtf(ss);
-  if (t < ncol4) Vec4<float>::store(u + row * d + t * 4, v * (1.0f / (r + 1e-4f)));
-  if (t == 0) norm[row] = r;
+  return v;
 }
 
-// dx, and this sentence's partial dw [d] / db.  u = v / (r + eps), r = |v|:  dv = du / (r + eps) - u (du . u) / r;
-// dp_s = dv . x_s;  dscore_s = p_s (dp_s - sum_t p_t dp_t), 0 at a masked position (its score is a constant);
-// dx_s = p_s dv + dscore_s w;  dw = sum_s dscore_s x_s;  db = sum_s dscore_s.
-template <typename T>
-__global__ __launch_bounds__(POOL_THREADS) void attn_pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const uint8_t* __restrict__ mask,
-                                                                     const float* __restrict__ u, const float* __restrict__ probs,
-                                                                     const float* __restrict__ norm, const float* __restrict__ du,
-                                                                     const float* __restrict__ du_scale, T* __restrict__ dx,
-                                                                     float* __restrict__ dw_part, float* __restrict__ db_part, int S, int d,
-                                                                     int keep_x) {
+template <typename T, int KIND>
+__global__ __launch_bounds__(POOL_THREADS) void pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
+                                                                const uint8_t* __restrict__ mask, pool_out_t<T, KIND>* __restrict__ out,
+                                                                float* __restrict__ probs, float* __restrict__ norm, int S, int d,
+                                                                int keep_x, uint32_t thresh, float inv_keep, uint64_t seed) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const PoolLds l = pool_lds(smem, S, d);
   T* xs = reinterpret_cast<T*>(l.xs);
   const int64_t row = blockIdx.x;
   const T* xr = x + row * S * d;
-  const int t = threadIdx.x;
-  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
-  // dv
-  f32x4 uv = {0.f, 0.f, 0.f, 0.f}, gv = {0.f, 0.f, 0.f, 0.f};
-  if (t < ncol4) {
-    uv = Vec4<float>::load(u + row * d + t * 4);
-    gv = Vec4<float>::load(du + row * d + t * 4);
-    if (du_scale) gv *= du_scale[0];
+  const int t = threadIdx.x, ncol4 = d >> 2;
+  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
+  // scores (first read of x)
+  row_dots<T, T, KIND == POOL_SENT>(xr, w, xs, l.sc, S, d, keep_x != 0, dr);
+  __syncthreads();
+  pool_softmax(l, mask, probs, to_f32<T>(b[0]), row, S);
+  // weighted sum (second read of x, or LDS)
+  const int G = POOL_THREADS / ncol4, cg = t % ncol4, g = t / ncol4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (g < G) {
+#pragma unroll 4
+    for (int s = g; s < S; s += G) {
+      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      if constexpr (KIND == POOL_SENT) {
+        if (thresh) xv *= drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
+      }
+      acc += xv * l.sc[s];
+    }
   }
-  const float gu = block_sum(dot4(gv, uv), l.red);
-  const float r = norm[row];
-  const float coef = r > 0.f ? gu / r : 0.f;
-  if (t < ncol4) Vec4<float>::store(l.vec + t * 4, gv * (1.0f / (r + 1e-4f)) - uv * coef);
+  const f32x4 v = colgroup_fold(l, d, acc);
+  if constexpr (KIND == POOL_UNIT) {
+    const float ss = block_sum(dot4(v, v), l.red);
+    const float r = sqrtf(ss);
+    if (t < ncol4) Vec4<float>::store(out + row * d + t * 4, v * (1.0f / (r + 1e-4f)));
+    if (t == 0) norm[row] = r;
+  } else {
+    if (t < ncol4) Vec4<T>::store(out + row * d + t * 4, v);
+  }
+}
+
+// dx, and this sentence's partial dw [d] / db (folded by attn_pool_fold_kernel).  Unit vectors, u = v / (r + eps), r = |v|:
+// dv = du / (r + eps) - u (du . u) / r; sentence pooling: dv as given.  With xd = x, or dropout(x) for the sentence pooling:
+// dp_s = dv . xd_s;  dscore_s = p_s (dp_s - sum_t p_t dp_t), 0 at a masked position (its score is a constant);
+// d(xd_s) = p_s dv + dscore_s w, and dx = the dropout's backward of that (same mask, same scale);  dw = sum_s dscore_s xd_s;
+// db = sum_s dscore_s.
+template <typename T, int KIND>
+__global__ __launch_bounds__(POOL_THREADS) void pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const uint8_t* __restrict__ mask,
+                                                                const float* __restrict__ probs, const pool_out_t<T, KIND>* __restrict__ dout,
+                                                                const float* __restrict__ u, const float* __restrict__ norm,
+                                                                const float* __restrict__ du_scale, T* __restrict__ dx,
+                                                                float* __restrict__ dw_part, float* __restrict__ db_part, int S, int d,
+                                                                int keep_x, uint32_t thresh, float inv_keep, uint64_t seed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PoolLds l = pool_lds(smem, S, d);
+  T* xs = reinterpret_cast<T*>(l.xs);
+  const int64_t row = blockIdx.x;
+  const T* xr = x + row * S * d;
+  const int t = threadIdx.x, ncol4 = d >> 2;
+  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
+  // dv
+  if constexpr (KIND == POOL_UNIT) {
+    f32x4 uv = {0.f, 0.f, 0.f, 0.f}, gv = {0.f, 0.f, 0.f, 0.f};
+    if (t < ncol4) {
+      uv = Vec4<float>::load(u + row * d + t * 4);
+      gv = Vec4<float>::load(dout + row * d + t * 4);
+      if (du_scale) gv *= du_scale[0];
+    }
+    const float gu = block_sum(dot4(gv, uv), l.red);
+    const float r = norm[row];
+    const float coef = r > 0.f ? gu / r : 0.f;
+    if (t < ncol4) Vec4<float>::store(l.vec + t * 4, gv * (1.0f / (r + 1e-4f)) - uv * coef);
+  } else {
+    if (t < ncol4) Vec4<float>::store(l.vec + t * 4, Vec4<T>::load(dout + row * d + t * 4));
+  }
   for (int s = t; s < S; s += POOL_THREADS) l.pr[s] = probs[row * S + s];
   __syncthreads();
   // dp (first read of x)
-  row_dots<T, float>(xr, l.vec, xs, l.sc, S, d, keep_x != 0);
+  row_dots<T, float, KIND == POOL_SENT>(xr, l.vec, xs, l.sc, S, d, keep_x != 0, dr);
   __syncthreads();
   float c0 = 0.f;
   for (int s = t; s < S; s += POOL_THREADS) c0 += l.pr[s] * l.sc[s];
@@ -235,25 +243,28 @@ __global__ __launch_bounds__(POOL_THREADS) void attn_pool_bwd_kernel(const T* __
   }
   dbl = block_sum(dbl, l.red);
   // dx and dw (second read of x, or LDS)
-  const int cg = t % ncol4, g = t / ncol4;
+  const int G = POOL_THREADS / ncol4, cg = t % ncol4, g = t / ncol4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (g < G) {
     const f32x4 wv = Vec4<T>::load(w + cg * 4), dv = Vec4<float>::load(l.vec + cg * 4);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int s = g; s < S; s += G) {
-      const f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
+      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
       const float ds = l.sc[s];
-      Vec4<T>::store(dx + (row * S + s) * d + cg * 4, dv * l.pr[s] + wv * ds);
+      f32x4 gx = dv * l.pr[s] + wv * ds;
+      if constexpr (KIND == POOL_SENT) {
+        if (thresh) {
+          const f32x4 sc = drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
+          xv *= sc;
+          gx *= sc;
+        }
+      }
+      Vec4<T>::store(dx + (row * S + s) * d + cg * 4, gx);
       acc += xv * ds;
     }
-    Vec4<float>::store(l.part + g * d + cg * 4, acc);
   }
-  __syncthreads();
-  if (t < ncol4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
-    Vec4<float>::store(dw_part + row * d + t * 4, v);
-  }
+  const f32x4 dwv = colgroup_fold(l, d, acc);
+  if (t < ncol4) Vec4<float>::store(dw_part + row * d + t * 4, dwv);
   if (t == 0) db_part[row] = dbl;
 }
 
@@ -270,107 +281,6 @@ __global__ __launch_bounds__(256) void attn_pool_fold_kernel(const float* __rest
     for (int64_t r = 0; r < rows; ++r) s += db_part[r];
     db[0] += s;
   }
-}
-
-// ------------------------------------------------------------------------------------------- sentence pooling (Caption2Image)
-// src/image_model.py:430-436: xd = dropout(x) (training), score_s = xd_s . w + b, masked_fill(-10000), p = softmax(score),
-// v = sum_s p_s xd_s -- no normalisation; v is written in the compute dtype (it feeds the decoder GEMM).  Same plan as above:
-// LDS keeps the RAW sentence, the dropout factor of an element is recomputed from its index wherever the element is used.
-template <typename T>
-__global__ __launch_bounds__(POOL_THREADS) void sent_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ b,
-                                                                     const uint8_t* __restrict__ mask, T* __restrict__ v_out,
-                                                                     float* __restrict__ probs, int S, int d, int keep_x, uint32_t thresh,
-                                                                     float inv_keep, uint64_t seed) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const PoolLds l = pool_lds(smem, S, d);
-  T* xs = reinterpret_cast<T*>(l.xs);
-  const int64_t row = blockIdx.x;
-  const T* xr = x + row * S * d;
-  const int t = threadIdx.x;
-  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
-  row_dots<T, T, true>(xr, w, xs, l.sc, S, d, keep_x != 0, dr);
-  __syncthreads();
-  pool_softmax(l, mask, probs, to_f32<T>(b[0]), row, S);
-  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
-  const int cg = t % ncol4, g = t / ncol4;
-  if (g < G) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int s = g; s < S; s += G) {
-      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
-      if (thresh) xv *= drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
-      acc += xv * l.sc[s];
-    }
-    Vec4<float>::store(l.part + g * d + cg * 4, acc);
-  }
-  __syncthreads();
-  if (t < ncol4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
-    Vec4<T>::store(v_out + row * d + t * 4, v);
-  }
-}
-
-// dp_s = dv . xd_s;  dscore_s = p_s (dp_s - sum_t p_t dp_t), 0 at a masked position;  d(xd_s) = p_s dv + dscore_s w, and
-// dx = the dropout's backward of that (same mask, same scale);  dw = sum_s dscore_s xd_s;  db = sum_s dscore_s (per-sentence
-// partials, folded by attn_pool_fold_kernel).
-template <typename T>
-__global__ __launch_bounds__(POOL_THREADS) void sent_pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const uint8_t* __restrict__ mask,
-                                                                     const float* __restrict__ probs, const T* __restrict__ dv_in,
-                                                                     T* __restrict__ dx, float* __restrict__ dw_part,
-                                                                     float* __restrict__ db_part, int S, int d, int keep_x, uint32_t thresh,
-                                                                     float inv_keep, uint64_t seed) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const PoolLds l = pool_lds(smem, S, d);
-  T* xs = reinterpret_cast<T*>(l.xs);
-  const int64_t row = blockIdx.x;
-  const T* xr = x + row * S * d;
-  const int t = threadIdx.x;
-  const int ncol4 = d >> 2, G = POOL_THREADS / ncol4;
-  const PoolDrop dr = {thresh, inv_keep, seed, (uint64_t)row * (uint64_t)S * (uint64_t)d};
-  if (t < ncol4) Vec4<float>::store(l.vec + t * 4, Vec4<T>::load(dv_in + row * d + t * 4));
-  for (int s = t; s < S; s += POOL_THREADS) l.pr[s] = probs[row * S + s];
-  __syncthreads();
-  // dp (first read of x)
-  row_dots<T, float, true>(xr, l.vec, xs, l.sc, S, d, keep_x != 0, dr);
-  __syncthreads();
-  float c0 = 0.f;
-  for (int s = t; s < S; s += POOL_THREADS) c0 += l.pr[s] * l.sc[s];
-  c0 = block_sum(c0, l.red);
-  float dbl = 0.f;
-  for (int s = t; s < S; s += POOL_THREADS) {
-    const float ds = (mask && !mask[row * S + s]) ? 0.f : l.pr[s] * (l.sc[s] - c0);
-    l.sc[s] = ds;
-    dbl += ds;
-  }
-  dbl = block_sum(dbl, l.red);
-  // dx and dw (second read of x, or LDS)
-  const int cg = t % ncol4, g = t / ncol4;
-  if (g < G) {
-    const f32x4 wv = Vec4<T>::load(w + cg * 4), dv = Vec4<float>::load(l.vec + cg * 4);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int s = g; s < S; s += G) {
-      f32x4 xv = keep_x ? Vec4<T>::load(xs + (int64_t)s * d + cg * 4) : Vec4<T>::load(xr + (int64_t)s * d + cg * 4);
-      const float ds = l.sc[s];
-      f32x4 gx = dv * l.pr[s] + wv * ds;
-      if (thresh) {
-        const f32x4 sc = drop_scale4(dr, dr.base + (uint64_t)s * d + cg * 4);
-        xv *= sc;
-        gx *= sc;
-      }
-      Vec4<T>::store(dx + (row * S + s) * d + cg * 4, gx);
-      acc += xv * ds;
-    }
-    Vec4<float>::store(l.part + g * d + cg * 4, acc);
-  }
-  __syncthreads();
-  if (t < ncol4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < G; ++k) v += Vec4<float>::load(l.part + k * d + t * 4);
-    Vec4<float>::store(dw_part + row * d + t * 4, v);
-  }
-  if (t == 0) db_part[row] = dbl;
 }
 
 // ------------------------------------------------------------------------------------------- L2 distance (Caption2Image loss)
@@ -463,70 +373,102 @@ __global__ __launch_bounds__(POOL_THREADS) void contrastive_cols_kernel(const fl
   }
 }
 
-// validate: everything that can be refused without touching the device
-int pool_validate(const char* what, int dtype, int64_t rows, int S, int d) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "%s: bad dtype", what);
+// Everything the four pooling entry points share and that can be settled without touching the device: the shape is refused or
+// taken (in the order dtype, rows, S, d, dropout_p), then the LDS plan, the dropout constants and the profiler's bytes of x.
+struct PoolPlan { int keep; size_t lds; uint32_t thresh; float inv_keep; double x_bytes; };
+int pool_validate(const char* what, int dtype, int64_t rows, int S, int d, float dropout_p, PoolPlan* p) {
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "%s: bad dtype", what);
   IMT_CHECK_ARG(rows >= 0 && rows <= 0x7fffffff, "%s: row count outside [0, 2^31)", what);
   IMT_CHECK_ARG(S >= 1, "%s: S must be at least 1", what);
   IMT_CHECK_ARG(S <= IMT_POOL_MAX_S, "%s: S above %d is not taken", what, IMT_POOL_MAX_S);
   IMT_CHECK_ARG(d >= 4 && d % 4 == 0, "%s: d must be a positive multiple of 4", what);
   IMT_CHECK_ARG(d <= IMT_POOL_MAX_D, "%s: d above %d is not taken", what, IMT_POOL_MAX_D);
+  IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p outside [0, 1)", what);
+  p->keep = pool_small_bytes(S, d) + pool_x_bytes(dtype, S, d) <= IMT_POOL_LDS_BYTES;
+  p->lds = (size_t)(pool_small_bytes(S, d) + (p->keep ? pool_x_bytes(dtype, S, d) : 0));
+  p->thresh = dropout_thresh(dropout_p);
+  p->inv_keep = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+  p->x_bytes = (double)rows * pool_x_bytes(dtype, S, d);
+  return IMT_OK;
+}
+
+template <int KIND>
+int pool_fwd(const char* what, int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, void* out, float* probs,
+             float* norm, int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed, void* stream) {
+  PoolPlan p;
+  const int rc = pool_validate(what, dtype, rows, S, d, dropout_p, &p);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && b && out && probs && (norm || KIND != POOL_UNIT), "%s: null pointer", what);
+  hipStream_t st = (hipStream_t)stream;
+  ImtProfScope prof(what, 2.0 * rows * S * d * 2, (p.keep ? 1.0 : 2.0) * p.x_bytes, st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((pool_fwd_kernel<T, KIND>), dim3((unsigned)rows), dim3(POOL_THREADS), p.lds, st, (const T*)x, (const T*)w, (const T*)b,
+                       mask, (pool_out_t<T, KIND>*)out, probs, norm, S, d, p.keep, p.thresh, p.inv_keep, dropout_seed);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
+}
+
+// dout: du (fp32) | dv (compute dtype); u, norm, du_scale: unit vectors only.  ws: dw_part [rows, d] | db_part [rows]
+template <int KIND>
+int pool_bwd(const char* what, int dtype, const void* x, const void* w, const uint8_t* mask, const float* probs, const void* dout,
+             const float* u, const float* norm, const float* du_scale, void* dx, float* dw, float* db, float* ws, int64_t rows, int S,
+             int d, float dropout_p, uint64_t dropout_seed, void* stream) {
+  PoolPlan p;
+  const int rc = pool_validate(what, dtype, rows, S, d, dropout_p, &p);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(x && w && probs && dout && dx && dw && db && ws && ((u && norm) || KIND != POOL_UNIT), "%s: null pointer", what);
+  hipStream_t st = (hipStream_t)stream;
+  float* dw_part = ws;
+  float* db_part = ws + rows * d;
+  ImtProfScope prof(what, 2.0 * rows * S * d * 3, (p.keep ? 2.0 : 3.0) * p.x_bytes, st);
+  const int rc2 = imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((pool_bwd_kernel<T, KIND>), dim3((unsigned)rows), dim3(POOL_THREADS), p.lds, st, (const T*)x, (const T*)w, mask, probs,
+                       (const pool_out_t<T, KIND>*)dout, u, norm, du_scale, (T*)dx, dw_part, db_part, S, d, p.keep, p.thresh, p.inv_keep,
+                       dropout_seed);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
+  if (rc2 != IMT_OK) return rc2;
+  hipLaunchKernelGGL(attn_pool_fold_kernel, dim3(imt_cdiv(d + 1, 256)), dim3(256), 0, st, dw_part, db_part, dw, db, rows, d);
+  IMT_CHECK_LAUNCH();
   return IMT_OK;
 }
 
 }  // namespace
 
 extern "C" int imt_attn_pool_plan(int dtype, int S, int d) {
-  const int rc = pool_validate("attn_pool_plan", dtype, 0, S, d);
+  PoolPlan p;
+  const int rc = pool_validate("attn_pool_plan", dtype, 0, S, d, 0.f, &p);
   if (rc != IMT_OK) return rc;
-  return pool_small_bytes(S, d) + pool_x_bytes(dtype, S, d) <= IMT_POOL_LDS_BYTES ? 1 : 2;
+  return p.keep ? 1 : 2;
 }
 
 extern "C" int imt_attn_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, float* u, float* probs,
                                  float* norm, int64_t rows, int S, int d, void* stream) {
-  const int rc = pool_validate("attn_pool_fwd", dtype, rows, S, d);
-  if (rc != IMT_OK) return rc;
-  if (rows == 0) return IMT_OK;
-  IMT_CHECK_ARG(x && w && b && u && probs && norm, "attn_pool_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
-  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
-  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
-  ImtProfScope prof("attn_pool_fwd", 2.0 * rows * S * d * 2, (keep ? 1.0 : 2.0) * xb, st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(attn_pool_fwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w,
-                       (const float*)b, mask, u, probs, norm, S, d, keep);
-  else
-    hipLaunchKernelGGL(attn_pool_fwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       (const bf16_t*)b, mask, u, probs, norm, S, d, keep);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return pool_fwd<POOL_UNIT>("attn_pool_fwd", dtype, x, w, b, mask, u, probs, norm, rows, S, d, 0.f, 0, stream);
 }
 
 extern "C" int imt_attn_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* u, const float* probs,
                                  const float* norm, const float* du, const float* du_scale, void* dx, float* dw, float* db, float* ws,
                                  int64_t rows, int S, int d, void* stream) {
-  const int rc = pool_validate("attn_pool_bwd", dtype, rows, S, d);
-  if (rc != IMT_OK) return rc;
-  if (rows == 0) return IMT_OK;
-  IMT_CHECK_ARG(x && w && u && probs && norm && du && dx && dw && db && ws, "attn_pool_bwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
-  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
-  float* dw_part = ws;
-  float* db_part = ws + rows * d;
-  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
-  ImtProfScope prof("attn_pool_bwd", 2.0 * rows * S * d * 3, (keep ? 2.0 : 3.0) * xb, st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(attn_pool_bwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w, mask,
-                       u, probs, norm, du, du_scale, (float*)dx, dw_part, db_part, S, d, keep);
-  else
-    hipLaunchKernelGGL(attn_pool_bwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       mask, u, probs, norm, du, du_scale, (bf16_t*)dx, dw_part, db_part, S, d, keep);
-  IMT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_pool_fold_kernel, dim3(imt_cdiv(d + 1, 256)), dim3(256), 0, st, dw_part, db_part, dw, db, rows, d);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return pool_bwd<POOL_UNIT>("attn_pool_bwd", dtype, x, w, mask, probs, du, u, norm, du_scale, dx, dw, db, ws, rows, S, d, 0.f, 0, stream);
+}
+
+extern "C" int imt_sent_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, void* v, float* probs,
+                                 int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed, void* stream) {
+  return pool_fwd<POOL_SENT>("sent_pool_fwd", dtype, x, w, b, mask, v, probs, nullptr, rows, S, d, dropout_p, dropout_seed, stream);
+}
+
+extern "C" int imt_sent_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* probs, const void* dv, void* dx,
+                                 float* dw, float* db, float* ws, int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed,
+                                 void* stream) {
+  return pool_bwd<POOL_SENT>("sent_pool_bwd", dtype, x, w, mask, probs, dv, nullptr, nullptr, nullptr, dx, dw, db, ws, rows, S, d, dropout_p,
+                             dropout_seed, stream);
 }
 
 extern "C" int imt_contrastive(const float* img, const float* txt, float* loss, float* d_img, float* d_txt, float* ws, int B, int N,
@@ -548,69 +490,9 @@ extern "C" int imt_contrastive(const float* img, const float* txt, float* loss, 
   return IMT_OK;
 }
 
-namespace {
-int sent_pool_validate(const char* what, int dtype, int64_t rows, int S, int d, float dropout_p) {
-  const int rc = pool_validate(what, dtype, rows, S, d);
-  if (rc != IMT_OK) return rc;
-  IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p outside [0, 1)", what);
-  return IMT_OK;
-}
-}  // namespace
-
-extern "C" int imt_sent_pool_fwd(int dtype, const void* x, const void* w, const void* b, const uint8_t* mask, void* v, float* probs,
-                                 int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed, void* stream) {
-  const int rc = sent_pool_validate("sent_pool_fwd", dtype, rows, S, d, dropout_p);
-  if (rc != IMT_OK) return rc;
-  if (rows == 0) return IMT_OK;
-  IMT_CHECK_ARG(x && w && b && v && probs, "sent_pool_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
-  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
-  const uint32_t th = dropout_thresh(dropout_p);
-  const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
-  ImtProfScope prof("sent_pool_fwd", 2.0 * rows * S * d * 2, (keep ? 1.0 : 2.0) * xb, st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(sent_pool_fwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w,
-                       (const float*)b, mask, (float*)v, probs, S, d, keep, th, ik, dropout_seed);
-  else
-    hipLaunchKernelGGL(sent_pool_fwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       (const bf16_t*)b, mask, (bf16_t*)v, probs, S, d, keep, th, ik, dropout_seed);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
-}
-
-extern "C" int imt_sent_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* mask, const float* probs, const void* dv, void* dx,
-                                 float* dw, float* db, float* ws, int64_t rows, int S, int d, float dropout_p, uint64_t dropout_seed,
-                                 void* stream) {
-  const int rc = sent_pool_validate("sent_pool_bwd", dtype, rows, S, d, dropout_p);
-  if (rc != IMT_OK) return rc;
-  if (rows == 0) return IMT_OK;
-  IMT_CHECK_ARG(x && w && probs && dv && dx && dw && db && ws, "sent_pool_bwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int keep = imt_attn_pool_plan(dtype, S, d) == 1;
-  const size_t lds = (size_t)(pool_small_bytes(S, d) + (keep ? pool_x_bytes(dtype, S, d) : 0));
-  const uint32_t th = dropout_thresh(dropout_p);
-  const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  float* dw_part = ws;
-  float* db_part = ws + rows * d;
-  const double xb = (double)rows * S * d * (dtype == IMT_BF16 ? 2 : 4);
-  ImtProfScope prof("sent_pool_bwd", 2.0 * rows * S * d * 3, (keep ? 2.0 : 3.0) * xb, st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(sent_pool_bwd_kernel<float>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const float*)x, (const float*)w, mask,
-                       probs, (const float*)dv, (float*)dx, dw_part, db_part, S, d, keep, th, ik, dropout_seed);
-  else
-    hipLaunchKernelGGL(sent_pool_bwd_kernel<bf16_t>, dim3((unsigned)rows), dim3(POOL_THREADS), lds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       mask, probs, (const bf16_t*)dv, (bf16_t*)dx, dw_part, db_part, S, d, keep, th, ik, dropout_seed);
-  IMT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_pool_fold_kernel, dim3(imt_cdiv(d + 1, 256)), dim3(256), 0, st, dw_part, db_part, dw, db, rows, d);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
-}
-
 extern "C" int imt_l2_dist(int dtype, const void* pred, const void* target, float* loss, void* dpred, float* ws, int B, int64_t n,
                            void* stream) {
-  IMT_CHECK_ARG(ok_dtype(dtype), "l2_dist: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "l2_dist: bad dtype");
   IMT_CHECK_ARG(B >= 1, "l2_dist: B must be at least 1");
   IMT_CHECK_ARG(n >= 4 && n % 4 == 0, "l2_dist: n must be a positive multiple of 4");
   IMT_CHECK_ARG(n <= ((int64_t)1 << 40) / B, "l2_dist: more than 2^40 elements are not taken");
@@ -621,18 +503,14 @@ extern "C" int imt_l2_dist(int dtype, const void* pred, const void* target, floa
   const int nparts = (int)(wgs < IMT_L2_DIST_PARTS ? wgs : IMT_L2_DIST_PARTS);
   const int grid2 = (int)(wgs < 2048 ? wgs : 2048);
   const float inv_b = 1.0f / (float)B;
-  ImtProfScope prof("l2_dist", 3.0 * B * n, (double)B * n * (dtype == IMT_BF16 ? 2 : 4) * 5, st);
-  if (dtype == IMT_F32) {
-    hipLaunchKernelGGL(l2_partial_kernel<float>, dim3(nparts), dim3(256), 0, st, (const float*)pred, (const float*)target, ws, n4);
+  ImtProfScope prof("l2_dist", 3.0 * B * n, (double)B * n * imt_dtype_bytes(dtype) * 5, st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(l2_partial_kernel<T>, dim3(nparts), dim3(256), 0, st, (const T*)pred, (const T*)target, ws, n4);
     IMT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(l2_scale_kernel<float>, dim3(grid2), dim3(256), 0, st, (const float*)pred, (const float*)target, ws, nparts, loss,
-                       (float*)dpred, n4, inv_b);
-  } else {
-    hipLaunchKernelGGL(l2_partial_kernel<bf16_t>, dim3(nparts), dim3(256), 0, st, (const bf16_t*)pred, (const bf16_t*)target, ws, n4);
+    hipLaunchKernelGGL(l2_scale_kernel<T>, dim3(grid2), dim3(256), 0, st, (const T*)pred, (const T*)target, ws, nparts, loss, (T*)dpred, n4,
+                       inv_b);
     IMT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(l2_scale_kernel<bf16_t>, dim3(grid2), dim3(256), 0, st, (const bf16_t*)pred, (const bf16_t*)target, ws, nparts, loss,
-                       (bf16_t*)dpred, n4, inv_b);
-  }
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+    return IMT_OK;
+  });
 }

@@ -476,49 +476,48 @@ int ln_fwd_dispatch(int mode, const LnSrc<T>& src, const void* gamma, const void
 extern "C" int imt_layernorm_fwd(int dtype, const void* x, const void* gamma, const void* beta, void* y, float* mean,
                                  float* rstd, int rows, int d, float eps, float dropout_p, uint64_t dropout_seed,
                                  void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "layernorm_fwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "layernorm_fwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "layernorm_fwd: d must be a positive multiple of 4");
   if (rows <= 0) return IMT_OK;
   IMT_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == IMT_F32) { LnSrc<float> s{}; s.x = (const float*)x; return ln_fwd_dispatch<float>(0, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st); }
-  LnSrc<bf16_t> s{}; s.x = (const bf16_t*)x;
-  return ln_fwd_dispatch<bf16_t>(0, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    LnSrc<T> s{}; s.x = (const T*)x;
+    return ln_fwd_dispatch<T>(0, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st);
+  });
 }
 
 extern "C" int imt_add_layernorm_fwd(int dtype, const void* x, const void* resid, const void* gamma, const void* beta, void* sum_out,
                                      void* y, float* mean, float* rstd, int rows, int d, float eps, float dropout_p,
                                      uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "add_layernorm_fwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "add_layernorm_fwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "add_layernorm_fwd: d must be a positive multiple of 4");
   if (rows <= 0) return IMT_OK;
   IMT_CHECK_ARG(x && resid && gamma && beta && sum_out && y && mean && rstd, "add_layernorm_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == IMT_F32) {
-    LnSrc<float> s{}; s.x = (const float*)x; s.resid = (const float*)resid; s.sum_out = (float*)sum_out;
-    return ln_fwd_dispatch<float>(1, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st);
-  }
-  LnSrc<bf16_t> s{}; s.x = (const bf16_t*)x; s.resid = (const bf16_t*)resid; s.sum_out = (bf16_t*)sum_out;
-  return ln_fwd_dispatch<bf16_t>(1, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    LnSrc<T> s{}; s.x = (const T*)x; s.resid = (const T*)resid; s.sum_out = (T*)sum_out;
+    return ln_fwd_dispatch<T>(1, s, gamma, beta, y, mean, rstd, rows, d, eps, dropout_p, dropout_seed, st);
+  });
 }
 
 extern "C" int imt_embed_ln_fwd(int dtype, const int64_t* ids, const int64_t* pos_ids, const int64_t* type_ids, const void* word,
                                 const void* pos, const void* type, const void* gamma, const void* beta, void* sum_out, void* y,
                                 float* mean, float* rstd, int n_tokens, int seq_len, int d, int vocab, int max_pos, int n_types,
                                 float eps, float dropout_p, uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "embed_ln_fwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "embed_ln_fwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0 && seq_len > 0, "embed_ln_fwd: bad dims");
   if (n_tokens <= 0) return IMT_OK;
   IMT_CHECK_ARG(ids && word && pos && type && gamma && beta && sum_out && y && mean && rstd, "embed_ln_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == IMT_F32) {
-    LnSrc<float> s{}; s.ids = ids; s.pos_ids = pos_ids; s.type_ids = type_ids; s.word = (const float*)word; s.pos = (const float*)pos;
-    s.type = (const float*)type; s.sum_out = (float*)sum_out; s.seq_len = seq_len; s.vocab = vocab; s.max_pos = max_pos; s.n_types = n_types;
-    return ln_fwd_dispatch<float>(2, s, gamma, beta, y, mean, rstd, n_tokens, d, eps, dropout_p, dropout_seed, st);
-  }
-  LnSrc<bf16_t> s{}; s.ids = ids; s.pos_ids = pos_ids; s.type_ids = type_ids; s.word = (const bf16_t*)word; s.pos = (const bf16_t*)pos;
-  s.type = (const bf16_t*)type; s.sum_out = (bf16_t*)sum_out; s.seq_len = seq_len; s.vocab = vocab; s.max_pos = max_pos; s.n_types = n_types;
-  return ln_fwd_dispatch<bf16_t>(2, s, gamma, beta, y, mean, rstd, n_tokens, d, eps, dropout_p, dropout_seed, st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    LnSrc<T> s{}; s.ids = ids; s.pos_ids = pos_ids; s.type_ids = type_ids; s.word = (const T*)word; s.pos = (const T*)pos;
+    s.type = (const T*)type; s.sum_out = (T*)sum_out; s.seq_len = seq_len; s.vocab = vocab; s.max_pos = max_pos; s.n_types = n_types;
+    return ln_fwd_dispatch<T>(2, s, gamma, beta, y, mean, rstd, n_tokens, d, eps, dropout_p, dropout_seed, st);
+  });
 }
 
 // grads[g_off[i] + c] += sum_k partials[i][k][0][c], grads[b_off[i] + c] += sum_k partials[i][k][1][c]   (k over the copies)
@@ -556,42 +555,41 @@ extern "C" int imt_layernorm_bwd(int dtype, const void* dy, const void* x, const
                                  const float* rstd, void* dx, float* dgamma, float* dbeta, int rows, int d,
                                  float y_dropout_p, uint64_t y_dropout_seed, void* dx_drop, float dx_dropout_p,
                                  uint64_t dx_dropout_seed, float* partial_ws, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "layernorm_bwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "layernorm_bwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "layernorm_bwd: d must be a positive multiple of 4");
   if (rows <= 0) return IMT_OK;
   IMT_CHECK_ARG(dy && x && gamma && mean && rstd && dx && dgamma && dbeta, "layernorm_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == IMT_F32)
-    IMT_DISPATCH_NCH(ln_bwd_launch, float, d, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, d, y_dropout_p,
+  return imt_by_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    IMT_DISPATCH_NCH(ln_bwd_launch, T, d, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, d, y_dropout_p,
                      y_dropout_seed, dx_drop, dx_dropout_p, dx_dropout_seed, partial_ws, st);
-  IMT_DISPATCH_NCH(ln_bwd_launch, bf16_t, d, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, d, y_dropout_p,
-                   y_dropout_seed, dx_drop, dx_dropout_p, dx_dropout_seed, partial_ws, st);
+  });
 }
 
 extern "C" int imt_embed_fwd(int dtype, const int64_t* ids, const int64_t* pos_ids, const int64_t* type_ids,
                              const void* word, const void* pos, const void* type, void* out, int n_tokens, int seq_len,
                              int d, int vocab, int max_pos, int n_types, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "embed_fwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "embed_fwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0 && seq_len > 0, "embed_fwd: bad dims");
   if (n_tokens <= 0) return IMT_OK;
   IMT_CHECK_ARG(ids && word && pos && type && out, "embed_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(imt_cdiv(n_tokens, ROWS_PER_BLOCK));
-  ImtProfScope prof("embed_fwd", 0.0, 4.0 * n_tokens * d * (dtype == IMT_BF16 ? 2 : 4), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(embed_fwd_kernel<float>, grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const float*)word,
-                       (const float*)pos, (const float*)type, (float*)out, n_tokens, seq_len, d, vocab, max_pos, n_types);
-  else
-    hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const bf16_t*)word,
-                       (const bf16_t*)pos, (const bf16_t*)type, (bf16_t*)out, n_tokens, seq_len, d, vocab, max_pos, n_types);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("embed_fwd", 0.0, 4.0 * n_tokens * d * imt_dtype_bytes(dtype), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(embed_fwd_kernel<T>, grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const T*)word, (const T*)pos,
+                       (const T*)type, (T*)out, n_tokens, seq_len, d, vocab, max_pos, n_types);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_embed_bwd(int dtype, const int64_t* ids, const int64_t* pos_ids, const int64_t* type_ids,
                              const void* dsum, float* dword, float* dpos, float* dtype_tab, int n_tokens, int seq_len,
                              int d, int64_t pad_id, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "embed_bwd: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "embed_bwd: bad dtype");
   IMT_CHECK_ARG(d > 0 && seq_len > 0, "embed_bwd: bad dims");
   if (n_tokens <= 0) return IMT_OK;
   IMT_CHECK_ARG(ids && dsum && dword && dpos && dtype_tab, "embed_bwd: null pointer");
@@ -600,49 +598,48 @@ extern "C" int imt_embed_bwd(int dtype, const int64_t* ids, const int64_t* pos_i
   const int tokb = tokb_env > 0 ? tokb_env : 16;
   const bool posmajor = (pos_ids == nullptr) && (n_tokens % seq_len == 0);  // must match the kernel's own test
   dim3 grid(posmajor ? seq_len * imt_cdiv(n_tokens / seq_len, tokb) : imt_cdiv(n_tokens, tokb));
-  ImtProfScope prof("embed_bwd", 0.0, (double)n_tokens * d * ((dtype == IMT_BF16 ? 2 : 4) + 16.0), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL((embed_bwd_kernel<float, 4>), grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const float*)dsum,
-                       dword, dpos, dtype_tab, n_tokens, seq_len, d, pad_id, tokb);
-  else
-    hipLaunchKernelGGL((embed_bwd_kernel<bf16_t, 4>), grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const bf16_t*)dsum,
-                       dword, dpos, dtype_tab, n_tokens, seq_len, d, pad_id, tokb);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("embed_bwd", 0.0, (double)n_tokens * d * (imt_dtype_bytes(dtype) + 16.0), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((embed_bwd_kernel<T, 4>), grid, dim3(256), 0, st, ids, pos_ids, type_ids, (const T*)dsum, dword, dpos,
+                       dtype_tab, n_tokens, seq_len, d, pad_id, tokb);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_colsum(int dtype, const void* X, int64_t ldx, int M, int N, float* out, const float* scale_dev,
                           void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "colsum: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "colsum: bad dtype");
   if (M <= 0 || N <= 0) return IMT_OK;
   IMT_CHECK_ARG(X && out && ldx % 4 == 0, "colsum: bad args");
   hipStream_t st = (hipStream_t)stream;
   const int rpb = 64;
   dim3 grid(imt_cdiv(N, 256), imt_cdiv(M, rpb));
-  ImtProfScope prof("colsum", 0.0, (double)M * N * (dtype == IMT_BF16 ? 2 : 4), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)X, ldx, M, N, out, rpb, scale_dev);
-  else
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, M, N, out, rpb, scale_dev);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("colsum", 0.0, (double)M * N * imt_dtype_bytes(dtype), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, (const T*)X, ldx, M, N, out, rpb, scale_dev);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 static int gather_scatter(int dtype, const void* x, int64_t ldx, const int32_t* idx, void* out, int64_t ldo, int n_sel,
                           int d, int scatter, void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "gather_rows: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "gather_rows: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0, "gather_rows: d/ld must be multiples of 4");
   if (n_sel <= 0) return IMT_OK;
   IMT_CHECK_ARG(x && idx && out, "gather_rows: null pointer");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(imt_cdiv(n_sel, ROWS_PER_BLOCK));
-  ImtProfScope prof(scatter ? "scatter_rows" : "gather_rows", 0.0, 2.0 * n_sel * d * (dtype == IMT_BF16 ? 2 : 4), st);
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(gather_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)x, ldx, idx, (float*)out, ldo, n_sel, d, scatter);
-  else
-    hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, ldx, idx, (bf16_t*)out, ldo, n_sel, d, scatter);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof(scatter ? "scatter_rows" : "gather_rows", 0.0, 2.0 * n_sel * d * imt_dtype_bytes(dtype), st);
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gather_rows_kernel<T>, grid, dim3(256), 0, st, (const T*)x, ldx, idx, (T*)out, ldo, n_sel, d, scatter);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }
 
 extern "C" int imt_gather_rows(int dtype, const void* x, int64_t ldx, const int32_t* idx, void* out, int64_t ldo,
@@ -667,7 +664,7 @@ extern "C" int imt_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void
 
 extern "C" int imt_add_rows_dropout(int in_dtype, const void* x, int out_dtype, void* out, const void* add, int64_t rows,
                                     int d, int period, float dropout_p, uint64_t dropout_seed, void* stream) {
-  IMT_CHECK_ARG((in_dtype == IMT_F32 || in_dtype == IMT_BF16) && (out_dtype == IMT_F32 || out_dtype == IMT_BF16), "add_rows_dropout: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(in_dtype) && imt_ok_dtype(out_dtype), "add_rows_dropout: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "add_rows_dropout: d must be a multiple of 4");
   IMT_CHECK_ARG(!add || period > 0, "add_rows_dropout: period must be positive");
   IMT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "add_rows_dropout: dropout_p outside [0, 1)");
@@ -677,28 +674,30 @@ extern "C" int imt_add_rows_dropout(int in_dtype, const void* x, int out_dtype, 
   dim3 grid(imt_cdiv(rows, ROWS_PER_BLOCK));
   const uint32_t th = dropout_thresh(dropout_p);
   const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  ImtProfScope prof("add_rows_dropout", 0.0, (double)rows * d * ((in_dtype == IMT_BF16 ? 2 : 4) + (out_dtype == IMT_BF16 ? 2 : 4)), st);
-#define IMT_ARD(TI, TO) hipLaunchKernelGGL((add_rows_dropout_kernel<TI, TO>), grid, dim3(256), 0, st, (const TI*)x, (TO*)out, (const TO*)add, rows, d, period, th, ik, dropout_seed)
-  if (in_dtype == IMT_F32 && out_dtype == IMT_F32) IMT_ARD(float, float);
-  else if (in_dtype == IMT_F32) IMT_ARD(float, bf16_t);
-  else if (out_dtype == IMT_F32) IMT_ARD(bf16_t, float);
-  else IMT_ARD(bf16_t, bf16_t);
-#undef IMT_ARD
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  ImtProfScope prof("add_rows_dropout", 0.0, (double)rows * d * (imt_dtype_bytes(in_dtype) + imt_dtype_bytes(out_dtype)), st);
+  return imt_by_dtype(in_dtype, [&](auto in_tag) {
+    return imt_by_dtype(out_dtype, [&](auto out_tag) {
+      using TI = typename decltype(in_tag)::type;
+      using TO = typename decltype(out_tag)::type;
+      hipLaunchKernelGGL((add_rows_dropout_kernel<TI, TO>), grid, dim3(256), 0, st, (const TI*)x, (TO*)out, (const TO*)add, rows, d,
+                         period, th, ik, dropout_seed);
+      IMT_CHECK_LAUNCH();
+      return IMT_OK;
+    });
+  });
 }
 
 extern "C" int imt_gated_mix(int dtype, const void* a, const void* b, const void* gate, void* out, int64_t rows, int d,
                              void* stream) {
-  IMT_CHECK_ARG(dtype == IMT_F32 || dtype == IMT_BF16, "gated_mix: bad dtype");
+  IMT_CHECK_ARG(imt_ok_dtype(dtype), "gated_mix: bad dtype");
   IMT_CHECK_ARG(d > 0 && d % 4 == 0, "gated_mix: d must be a multiple of 4");
   if (rows <= 0) return IMT_OK;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(imt_cdiv(rows, ROWS_PER_BLOCK));
-  if (dtype == IMT_F32)
-    hipLaunchKernelGGL(gated_mix_kernel<float>, grid, dim3(256), 0, st, (const float*)a, (const float*)b, (const float*)gate, (float*)out, rows, d);
-  else
-    hipLaunchKernelGGL(gated_mix_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)gate, (bf16_t*)out, rows, d);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return imt_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gated_mix_kernel<T>, grid, dim3(256), 0, st, (const T*)a, (const T*)b, (const T*)gate, (T*)out, rows, d);
+    IMT_CHECK_LAUNCH();
+    return IMT_OK;
+  });
 }

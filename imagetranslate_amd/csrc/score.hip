@@ -256,8 +256,8 @@ extern "C" int64_t imt_score_ws_bytes(int N, int V) {
 }
 
 extern "C" int imt_score_supported(int dtype, int V, int K) {
-  if ((dtype != IMT_F32 && dtype != IMT_BF16) || V <= 0 || K <= 0) return 0;
-  const int es = dtype == IMT_BF16 ? 2 : 4;
+  if (!imt_ok_dtype(dtype) || V <= 0 || K <= 0) return 0;
+  const int es = imt_dtype_bytes(dtype);
   if (K % (128 / es) != 0) return 0;                              // whole K tiles (128 bytes of K)
   if ((int64_t)(V + 256) * K * es >= ((int64_t)1 << 31)) return 0;  // 32-bit DMA offsets over the weight, ragged tile included
   return 1;
@@ -265,7 +265,7 @@ extern "C" int imt_score_supported(int dtype, int V, int K) {
 
 extern "C" int imt_score_rows(const imt_score_args* a, void* stream) {
   IMT_CHECK_ARG(a != nullptr, "score_rows: null args");
-  IMT_CHECK_ARG(a->dtype == IMT_F32 || a->dtype == IMT_BF16, "score_rows: bad dtype %d", a->dtype);
+  IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "score_rows: bad dtype %d", a->dtype);
   IMT_CHECK_ARG(a->x != nullptr, "score_rows: x is null");
   IMT_CHECK_ARG(a->w != nullptr, "score_rows: w is null");
   IMT_CHECK_ARG(a->target != nullptr, "score_rows: target is null");
@@ -277,7 +277,7 @@ extern "C" int imt_score_rows(const imt_score_args* a, void* stream) {
                 (long long)(a->ws ? a->ws_bytes : 0), (long long)imt_score_ws_bytes(a->N, a->V));
   IMT_CHECK_ARG(imt_score_supported(a->dtype, a->V, a->K), "score_rows: (dtype %d, V %d, K %d) is not taken by the fused kernel (K must be a whole "
                 "number of 128-byte K tiles)", a->dtype, a->V, a->K);
-  const int es = a->dtype == IMT_BF16 ? 2 : 4, epv = 16 / es;
+  const int es = imt_dtype_bytes(a->dtype), epv = 16 / es;
   IMT_CHECK_ARG(a->ldx >= a->K && a->ldx % epv == 0 && (uintptr_t)a->x % 16 == 0, "score_rows: ldx / x must keep rows 16-byte aligned");
   IMT_CHECK_ARG(a->ldw >= a->K && a->ldw % epv == 0 && (uintptr_t)a->w % 16 == 0, "score_rows: ldw / w must keep rows 16-byte aligned");
   IMT_CHECK_ARG(((int64_t)(a->N + 256) * a->ldx) * es < ((int64_t)1 << 31) && ((int64_t)(a->V + 256) * a->ldw) * es < ((int64_t)1 << 31),

@@ -25,6 +25,10 @@ POOL_CASES = [
     ("rows5_S37_d128_ragged", 5, 37, 128, [37, 1, 0, 20, 9], 1),
     ("rows3_S200_d512_two_reads", 3, 200, 512, None, 2),
     ("rows2_S1_d1024", 2, 1, 1024, None, 1),
+    # S > 256: the per-position loops take their second and third strides; d / 4 not dividing 256: idle threads in the column groups
+    ("rows4_S300_d32_strided", 4, 300, 32, [300, 257, 0, 1], 1),
+    ("rows3_S520_d64_strided_two_reads", 3, 520, 64, [520, 1, 0], 2),
+    ("rows2_S9_d12_idle_threads", 2, 9, 12, None, 1),
 ]
 
 
