@@ -561,8 +561,19 @@ __global__ __launch_bounds__(256, (DH == 64 && sizeof(T) == 2) ? 3 : 2) void att
 //   phase 2: QUERY on the lane (wave w owns queries 16w..): dQ = dS K as a plain K-strided x K-strided product from
 //            LDS (dS^T tile, and K parked into the region Q occupied).
 // Nothing is summed across workgroups; same dropout mask / mask semantics as the kernels above.
-template <int DH, bool MASK3D>
-__global__ __launch_bounds__(512, 4) void attn_bwd_fused_kernel(AttnP p) {
+//
+// PROJ = true (imt_attention_bwd_proj): the attention output went through the block's output projection, so dO = dY W_o, and
+// phase 0 forms this head's slice dO_h = dY[b] (Tq x d_model) W_o[:, 64h .. 64h+63] itself instead of reading what a GEMM
+// launch stored: 8 MB less written and read back per block at the C1 shapes, and one launch less.  Wave w owns query rows
+// 16w .. 16w+15 (as it does for delta): its dY rows are K-contiguous and come straight from global memory as the MFMA's B
+// operand; the W_o slice is K-strided and is staged 256 k at a time, alternately into the dS^T region (unused until phase 1)
+// and the Q | dO regions (filled afterwards), read back with the transposed LDS read.  The products are C^T tiles summed over
+// ascending 32-element k-steps in fp32 and rounded once to bf16 -- what imt_gemm does for the NN product -- so the dO tile
+// in LDS, the fragments delta is taken from and the optional copy in global memory carry the bits the GEMM would have stored.
+struct ProjP { const void* dy; int64_t lddy; const void* w; int64_t ldw; int d_model; };
+
+template <int DH, bool MASK3D, bool PROJ>
+IMT_DEVICE void attn_bwd_fused_body(const AttnP& p, const ProjP& pj) {
   typedef bf16_t T;
   constexpr int RB = DH * 2, NS = RB / 64, NDT = DH / 16;
   typedef typename Frag<T>::type frag_t;
@@ -594,28 +605,100 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_fused_kernel(AttnP p) {
   {
     constexpr int CPR = RB / 16, NIT = 128 * CPR / 512;
     u32x4 vq[NIT], vo[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int q = threadIdx.x + it * 512, tr = min(q / CPR, p.Tq - 1), c = q % CPR;
-      vq[it] = *reinterpret_cast<const u32x4*>(Qb + (int64_t)tr * p.ldq + c * 8);
-      vo[it] = *reinterpret_cast<const u32x4*>(dOb + (int64_t)tr * p.lddo + c * 8);
-    }
     const int i = 16 * wave + r;  // delta / lse of this wave's 16 query rows
     frag_t of[NS], dof[NS];
-    load_row_frags<T, DH>(of, Ob, p.ldo, 16 * wave, p.Tq);
-    load_row_frags<T, DH>(dof, dOb, p.lddo, 16 * wave, p.Tq);
+    // (PROJ: the Q tile and the O rows are requested under the last W_o chunk, into the registers the chunks came through)
+    auto load_q_o = [&]() {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int q = threadIdx.x + it * 512, tr = min(q / CPR, p.Tq - 1), c = q % CPR;
+        vq[it] = *reinterpret_cast<const u32x4*>(Qb + (int64_t)tr * p.ldq + c * 8);
+        if (!PROJ) vo[it] = *reinterpret_cast<const u32x4*>(dOb + (int64_t)tr * p.lddo + c * 8);
+      }
+      load_row_frags<T, DH>(of, Ob, p.ldo, 16 * wave, p.Tq);
+    };
+    if (!PROJ) load_q_o();
+    if (!PROJ) load_row_frags<T, DH>(dof, dOb, p.lddo, 16 * wave, p.Tq);
     load_row_frags<T, DH>(kf, Kb, p.ldk, k0, p.Tk);
     load_row_frags<T, DH>(vf, Vb, p.ldv, k0, p.Tk);
     const float lse_v = p.lse[((int64_t)b * p.H + h) * p.Tq + min(i, p.Tq - 1)];
     const uint8_t* qmp = p.query_mask ? p.query_mask + (int64_t)b * p.Tq + min(i, p.Tq - 1) : reinterpret_cast<const uint8_t*>(Qb);
     const uint8_t* kmp = p.key_mask ? p.key_mask + (int64_t)b * p.Tk + min(j, p.Tk - 1) : reinterpret_cast<const uint8_t*>(Kb);
     const uint8_t qmv = *qmp, kmv = *kmp;
+    if constexpr (PROJ) {
+      static_assert(!PROJ || DH == 64, "the W_o slice is staged as 128-byte rows");
+      constexpr int WK = 256, WIT = WK * CPR / 512;  // k rows of W_o per staged chunk ([WK][64] bf16 = 32 KiB), 16-B chunks per thread
+      const int dm = pj.d_model, nks = dm / 32, nch = (nks + 7) / 8;
+      const T* Wb = reinterpret_cast<const T*>(pj.w) + h * DH + (threadIdx.x % CPR) * 8;
+      const T* dYr = reinterpret_cast<const T*>(pj.dy) + ((int64_t)b * p.Tq + min(i, p.Tq - 1)) * pj.lddy + 8 * g;
+      const int wkr = threadIdx.x / CPR;  // this thread's k row within a 64-row slab of the chunk
+      u32x4 wv[WIT];
+      frag_t af[8];
+      // (rows / k offsets past d_model are clamped to valid addresses: those loads are unconditional and never multiplied)
+      auto load_w = [&](int ch) {
+#pragma unroll
+        for (int it = 0; it < WIT; ++it) wv[it] = *reinterpret_cast<const u32x4*>(Wb + (int64_t)min(WK * ch + wkr + 64 * it, dm - 1) * pj.ldw);
+      };
+      auto stage_w = [&](int ch) -> const char* {
+        char* Ws = (ch & 1) ? Qs : dST;  // (the barrier of chunk ch - 1 is behind every wave's reads of chunk ch - 2)
+#pragma unroll
+        for (int it = 0; it < WIT; ++it) *reinterpret_cast<u32x4*>(Ws + tile_off<RB>(wkr + 64 * it, threadIdx.x % CPR)) = wv[it];
+        __syncthreads();
+        return Ws;
+      };
+      load_w(0);
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) af[ks] = *reinterpret_cast<const frag_t*>(dYr + min(32 * ks, dm - 32));
+      f32x4 acc[4];
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // every chunk but the last is whole: its 8 k-steps run without a test, each followed by the request for the same k-step
+      // of the next chunk into the registers it has just freed
+#pragma unroll 1
+      for (int ch = 0; ch + 1 < nch; ++ch) {
+        const char* Ws = stage_w(ch);
+        load_w(ch + 1);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) mma16(acc[nt], lds_frag_kstrided_bf16<RB>(Ws, 32 * ks, 16 * nt), af[ks]);  // C^T tile: rows <- n, cols <- query
+          af[ks] = *reinterpret_cast<const frag_t*>(dYr + min(WK * (ch + 1) + 32 * ks, dm - 32));
+        }
+      }
+      {
+        const char* Ws = stage_w(nch - 1);
+        load_q_o();
+        const int nk = nks - 8 * (nch - 1);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          if (ks < nk) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) mma16(acc[nt], lds_frag_kstrided_bf16<RB>(Ws, 32 * ks, 16 * nt), af[ks]);
+          }
+        }
+      }
+      __syncthreads();  // every wave is done with the W_o chunks: Q and dO may land in their regions
+      // lane (r, g) of tile nt holds dO[query 16 wave + r][16 nt + 4 g + e]; rows >= Tq (clamped loads) are zero, as staged
+      T* dOg = (p.dO && i < p.Tq) ? const_cast<T*>(dOb) + (int64_t)i * p.lddo : nullptr;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const f32x4 v = (i < p.Tq) ? acc[nt] : f32x4{0.f, 0.f, 0.f, 0.f};
+        const bf16x4 w = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+        const int col = 16 * nt + 4 * g;
+        *reinterpret_cast<bf16x4*>(dOs + tile_off<RB>(i, col >> 3) + ((col & 7) << 1)) = w;
+        if (dOg) *reinterpret_cast<bf16x4*>(dOg + col) = w;
+      }
+    }
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int q = threadIdx.x + it * 512, tr = q / CPR, c = q % CPR;
       const u32x4 z = {0u, 0u, 0u, 0u};
       *reinterpret_cast<u32x4*>(Qs + tile_off<RB>(tr, c)) = (tr < p.Tq) ? vq[it] : z;
-      *reinterpret_cast<u32x4*>(dOs + tile_off<RB>(tr, c)) = (tr < p.Tq) ? vo[it] : z;
+      if (!PROJ) *reinterpret_cast<u32x4*>(dOs + tile_off<RB>(tr, c)) = (tr < p.Tq) ? vo[it] : z;
+    }
+    if constexpr (PROJ) {  // this wave's own 16 rows of the tile, in the layout load_row_frags gives
+#pragma unroll
+      for (int s = 0; s < NS; ++s) dof[s] = lds_frag_kcontig<T, RB>(dOs, 16 * wave, 4 * s);
     }
     float d = 0.f;
 #pragma unroll
@@ -737,6 +820,14 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_fused_kernel(AttnP p) {
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) Vec4<T>::store(dQb + 16 * dt + 4 * g, dq[dt] * p.scale);
   }  IMT_STAMP(p.trace, 4);
+}
+template <int DH, bool MASK3D>
+__global__ __launch_bounds__(512, 4) void attn_bwd_fused_kernel(AttnP p) {
+  attn_bwd_fused_body<DH, MASK3D, false>(p, ProjP());
+}
+template <bool MASK3D>
+__global__ __launch_bounds__(512, 4) void attn_bwd_proj_kernel(AttnP p, ProjP pj) {
+  attn_bwd_fused_body<64, MASK3D, true>(p, pj);
 }
 
 // =========================================================================================== backward: fused, 129-256 keys / queries
@@ -1154,7 +1245,7 @@ __global__ __launch_bounds__(512, 2) void attn_qkv_fwd_kernel(AttnP p, QkvP g) {
   }
 }
 
-int check_args(const imt_attn_args* a, bool bwd) {
+int check_args(const imt_attn_args* a, bool bwd, bool need_dO = true) {
   IMT_CHECK_ARG(a != nullptr, "attention: null args");
   IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "attention: bad dtype");
   IMT_CHECK_ARG(a->head_dim == 32 || a->head_dim == 64, "attention: head_dim %d unsupported (32 or 64)", a->head_dim);
@@ -1164,7 +1255,7 @@ int check_args(const imt_attn_args* a, bool bwd) {
   IMT_CHECK_ARG(a->ldq % al == 0 && a->ldk % al == 0 && a->ldv % al == 0 && a->ldo % al == 0, "attention: ld must be 16-B multiples");
   IMT_CHECK_ARG((((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->O) & 15) == 0, "attention: 16-B alignment");
   if (bwd) {
-    IMT_CHECK_ARG(a->dO && a->dQ && a->dK && a->dV && a->lse && a->delta, "attention_bwd: null tensor");
+    IMT_CHECK_ARG((a->dO || !need_dO) && a->dQ && a->dK && a->dV && a->lse && a->delta, "attention_bwd: null tensor");
     IMT_CHECK_ARG(a->lddo % al == 0 && a->lddq % al == 0 && a->lddk % al == 0 && a->lddv % al == 0, "attention_bwd: ld alignment");
     IMT_CHECK_ARG((((uintptr_t)a->dO | (uintptr_t)a->dQ | (uintptr_t)a->dK | (uintptr_t)a->dV) & 15) == 0, "attention_bwd: 16-B alignment");
   }
@@ -1289,6 +1380,47 @@ extern "C" int imt_attention_bwd(const imt_attn_args* a, void* stream) {
     return a->head_dim == 32 ? bwd_fused256_launch<32, false>(p, st) : bwd_fused256_launch<64, false>(p, st);
   }
   return a->head_dim == 32 ? bwd_launch<bf16_t, 32>(p, st) : bwd_launch<bf16_t, 64>(p, st);
+}
+
+// Attention backward with dO = dy W_o formed inside the launch (attn_bwd_proj_kernel) instead of by an NN product in front of
+// imt_attention_bwd.  a: the backward's arguments; a->dO may be NULL (dO is then never stored) or point at a [B*Tq, >= d_model]
+// buffer (lddo) that receives it.  dy [B*Tq, d_model] (lddy): the gradient of the projection's output; w_o [d_model, d_model]
+// row-major (ldw), the projection's weight.  dQ / dK / dV (and dO) are bit-identical to the pair's.
+extern "C" int imt_attention_bwd_proj_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d) {
+  const bool fused_off = getenv("IMT_ATTN_NO_FUSED_BWD") != nullptr;  // (the instance this one is a variant of is not in use)
+  return dtype == IMT_BF16 && head_dim == 64 && H > 0 && H * 64 == d_model && Tq > 0 && Tq <= 128 && Tk > 0 && Tk <= 128 &&
+         !has_mask3d && !fused_off;
+}
+extern "C" int imt_attention_bwd_proj(const imt_attn_args* a, const void* dy, int64_t lddy, const void* w_o, int64_t ldw, int d_model,
+                                      void* stream) {
+  int rc = check_args(a, true, false);
+  if (rc) return rc;
+  IMT_CHECK_ARG(imt_attention_bwd_proj_supported(a->dtype, a->head_dim, a->H, a->Tq, a->Tk, d_model, a->mask3d != nullptr),
+                "attention_bwd_proj: unsupported shape (bf16, head_dim 64, T <= 128, d_model = 64 H, no 3-D mask)");
+  IMT_CHECK_ARG(dy && w_o && lddy >= d_model && ldw >= d_model && lddy % 8 == 0 && ldw % 8 == 0 &&
+                (((uintptr_t)dy | (uintptr_t)w_o) & 15) == 0, "attention_bwd_proj: dy / w_o missing, misaligned or narrower than d_model");
+  IMT_CHECK_ARG((double)a->B * a->H * a->Tq * a->Tk < 4294967296.0, "attention_bwd_proj: too many score elements for 32-bit dropout indices");
+  const AttnP p = make_params(a);
+  ProjP pj;
+  pj.dy = dy; pj.lddy = lddy; pj.w = w_o; pj.ldw = ldw; pj.d_model = d_model;
+  hipStream_t st = (hipStream_t)stream;
+  const int lds = 2 * 128 * 64 * 2 + 128 * 256 + 128 * 4 * 2 + 128;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_proj_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr_set = true;
+  }
+  const double work = (double)p.B * p.H * p.Tq * p.Tk * 64.0;
+  // (profiled under the kind of the kernel it is an instance of, with the projection's flops and bytes added: the suite pins the
+  // short backward's dispatch by that kind)
+  ImtProfScope prof("attn_bwd_fused_bf16", 10.0 * work + 2.0 * p.B * p.Tq * (double)d_model * d_model,
+                    ((double)p.B * p.H * 64 * 2.0) * (3.0 * p.Tq + 4.0 * p.Tk) + 2.0 * p.B * p.Tq * d_model + 2.0 * d_model * d_model, st);
+  ImtTrace tr("attn_bwd", p.B * p.H, st);
+  AttnP pt = p;
+  pt.trace = tr.dev;
+  hipLaunchKernelGGL((attn_bwd_proj_kernel<false>), dim3(p.B * p.H), dim3(512), lds, st, pt, pj);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
 }
 
 // q|k|v projection + self-attention forward in one launch (attn_qkv_fwd_kernel).  a: the attention arguments with Q / K / V

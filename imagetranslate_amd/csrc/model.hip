@@ -318,7 +318,16 @@ int attn_block_bwd(const Ctx& c, const imt_attn_block& p, AttnWs& w, StackWs& sw
   RC(imt_layernorm_bwd(c.dtype, dy, w.pre_ln, c.P(p.ln_g), w.mean, w.rstd, d_pre, c.G(p.ln_g), c.G(p.ln_b), N, d, 0.f, 0,
                        (hp > 0.f) ? d_dense : nullptr, hp, site_seed(seed, layer, site0 + 1), sw.ln_site(3 * layer + slot, d), c.st));
   dw.add(c, d_dense, d, w.ctx, d, N, d, d, p.o_w, p.o_b);
-  RC(linear_bwd_input(c, d_dense, d, N, d, p.o_w, d, sw.d_ctx, d, nullptr, 0, nullptr, IMT_AUX_NONE, 0));
+  // short attention in bf16: d_ctx = d_dense W_o is formed inside the attention backward (bit-identical to the pair), and
+  // sw.d_ctx is neither written nor read
+  static const bool do_fusion = !(getenv("IMT_ATTN_DO_FUSION") && atoi(getenv("IMT_ATTN_DO_FUSION")) == 0);
+  const bool proj = do_fusion && imt_attention_bwd_proj_supported(c.dtype, d / c.m->heads, c.m->heads, T, kv_src ? Tk : T, d, ms.m3d != nullptr);
+  if (!proj) RC(linear_bwd_input(c, d_dense, d, N, d, p.o_w, d, sw.d_ctx, d, nullptr, 0, nullptr, IMT_AUX_NONE, 0));
+  auto attn_bwd = [&](imt_attn_args& a) {
+    if (!proj) return imt_attention_bwd(&a, c.st);
+    a.dO = nullptr;
+    return imt_attention_bwd_proj(&a, d_dense, d, c.P(p.o_w), d, d, c.st);
+  };
   imt_attn_args a;
   if (!kv_src) {
     attn_args(c, a, B, T, T, w.qkv, 3 * d, offp(w.qkv, d, c.es), 3 * d, offp(w.qkv, 2 * d, c.es), 3 * d, w.ctx, w.lse, ms, ap,
@@ -326,7 +335,7 @@ int attn_block_bwd(const Ctx& c, const imt_attn_block& p, AttnWs& w, StackWs& sw
     a.dO = sw.d_ctx; a.lddo = d;
     a.dQ = sw.d_qkv; a.lddq = 3 * d; a.dK = offp(sw.d_qkv, d, c.es); a.lddk = 3 * d; a.dV = offp(sw.d_qkv, 2 * d, c.es); a.lddv = 3 * d;
     a.delta = sw.delta;
-    RC(imt_attention_bwd(&a, c.st));
+    RC(attn_bwd(a));
     dw.add(c, sw.d_qkv, 3 * d, x, d, N, 3 * d, d, p.qkv_w, p.qkv_b);
     RC(linear_bwd_input(c, sw.d_qkv, 3 * d, N, 3 * d, p.qkv_w, d, sw.d_run, d, d_pre, d, nullptr, IMT_AUX_NONE, 0));
   } else {
@@ -339,7 +348,7 @@ int attn_block_bwd(const Ctx& c, const imt_attn_block& p, AttnWs& w, StackWs& sw
     const int64_t lddkv = d_kv_batched ? w.kv_ld : 2 * d;
     a.dQ = sw.d_q; a.lddq = d; a.dK = dkv; a.lddk = lddkv; a.dV = offp(dkv, d, c.es); a.lddv = lddkv;
     a.delta = sw.delta;
-    RC(imt_attention_bwd(&a, c.st));
+    RC(attn_bwd(a));
     dw.add(c, sw.d_q, d, x, d, N, d, d, p.qkv_w, p.qkv_b);
     RC(linear_bwd_input(c, sw.d_q, d, N, d, p.qkv_w, d, sw.d_run, d, d_pre, d, nullptr, IMT_AUX_NONE, 0));
     // the key|value weight gradient stays in this layer's grouped launch either way (its 32 tiles fill CUs the other six

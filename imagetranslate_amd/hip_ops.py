@@ -311,6 +311,30 @@ def attention_bwd(do, q, k, v, o, lse, B, H, Tq, Tk, head_dim, key_mask=None, qu
     return dq, dk, dv
 
 
+def attention_bwd_proj(dy, w_o, q, k, v, o, lse, B, H, Tq, Tk, head_dim, key_mask=None, query_mask=None, causal=False,
+                       scale=None, dropout_p=0.0, dropout_seed=0, do_out=None):
+    """(dq, dk, dv) of the attention whose output went through the projection y = ctx W_o^T: dO = dy W_o is formed inside
+    the backward launch (imt_attention_bwd_proj).  dy [B*Tq, d], w_o [d, d] row-major; ``do_out`` ([B*Tq, d]) receives dO
+    when given."""
+    _req_cuda(dy, w_o, q, k, v, o, lse, do_out)
+    d = H * head_dim
+    a = _attn_args(q, k, v, B, H, Tq, Tk, head_dim, key_mask, query_mask, None, causal, scale, dropout_p, dropout_seed)
+    dq = torch.empty((B * Tq, d), device=q.device, dtype=q.dtype)
+    dk = torch.empty((B * Tk, d), device=q.device, dtype=q.dtype)
+    dv = torch.empty((B * Tk, d), device=q.device, dtype=q.dtype)
+    delta = torch.empty((B, H, Tq), device=q.device, dtype=torch.float32)
+    a.O, a.ldo, a.lse = o.data_ptr(), _rowmajor(o), lse.data_ptr()
+    if do_out is not None:
+        a.dO, a.lddo = do_out.data_ptr(), _rowmajor(do_out)
+    a.dQ, a.lddq = dq.data_ptr(), _rowmajor(dq)
+    a.dK, a.lddk = dk.data_ptr(), _rowmajor(dk)
+    a.dV, a.lddv = dv.data_ptr(), _rowmajor(dv)
+    a.delta = delta.data_ptr()
+    L.check(L.load().imt_attention_bwd_proj(ctypes.byref(a), _p(dy), _rowmajor(dy), _p(w_o), _rowmajor(w_o), d, _stream()),
+            "imt_attention_bwd_proj")
+    return dq, dk, dv
+
+
 def gather_rows(x, idx):
     _req_cuda(x, idx)
     out = torch.empty((idx.numel(), x.shape[1]), device=x.device, dtype=x.dtype)

@@ -256,6 +256,15 @@ int imt_attention_bwd(const imt_attn_args* a, void* stream);
 int imt_attention_qkv_fwd_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d);
 int imt_attention_qkv_fwd(const imt_attn_args* a, const void* x, int64_t ldx, const void* w, const void* bias, int d_model,
                           void* stream);
+/* The backward of an attention whose output went through BertSelfOutput's projection y = ctx W_o^T: dO = dy W_o is formed
+ * INSIDE the attention backward (bf16, head_dim 64, Tq and Tk <= 128, d_model = 64 H, no 3-D mask; one workgroup per (batch,
+ * head) multiplies its 64 columns of it) instead of by an NN imt_gemm into a buffer that imt_attention_bwd reads back.  a: as
+ * for imt_attention_bwd, except that a->dO may be NULL (dO is never stored) or an OUTPUT [B*Tq, >= d_model] (lddo).  dy
+ * [B*Tq, d_model] (lddy), w_o [d_model, d_model] row-major (ldw); both 16-byte aligned with leading dimensions that are
+ * multiples of 8.  Bit-identical to imt_gemm (NN, alpha 1) + imt_attention_bwd.  _supported() == 0: the caller keeps the pair. */
+int imt_attention_bwd_proj_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d);
+int imt_attention_bwd_proj(const imt_attn_args* a, const void* dy, int64_t lddy, const void* w_o, int64_t ldw, int d_model,
+                           void* stream);
 
 /* ------------------------------------------------------------------ row select (src/seq2seq.py:175-177)
  * gather: out[r,:] = x[idx[r],:] ; scatter (its backward): dx[idx[r],:] = dout[r,:] (dx pre-zeroed by caller
