@@ -373,6 +373,147 @@ __global__ __launch_bounds__(POOL_THREADS) void contrastive_cols_kernel(const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------- two-sided contrastive loss (SenSim)
+// src/sen_sim.py:94-103.  scat = [source negatives; sources], tcat = [target negatives; targets]; pair i is src_i = scat[Ns - B + i],
+// tgt_i = tcat[Nt - B + i].  Workgroup i: A_ij = src_i . tcat_j, M_ij = tgt_i . scat_j, D_i = sum_j exp A_ij + sum_j exp M_ij + 1e-4,
+// row loss log D_i - (src_i . tgt_i + 1e-4) (the dot product is A's column Nt - B + i), dA_ij = exp A_ij / (D_i B),
+// dM_ij = exp M_ij / (D_i B), and the part of the pair's own gradients that is a sum over its row:
+// row_s_i = sum_j dA_ij tcat_j - tgt_i / B (into d src_i), row_t_i = sum_j dM_ij scat_j - src_i / B (into d tgt_i).
+// d src_i holds tgt_i three times -- dA_i,own from this row sum, dM_i,own from the column sum, and - 1 / B -- and the three nearly
+// cancel when the pair dominates its denominator (few negatives).  They are added as one coefficient, formed without the
+// cancellation: with R_i = D_i - exp A_i,own - exp M_i,own (summed on its own, the pair's two terms left out),
+// dA_i,own + dM_i,own - 1 / B = -R_i / (D_i B).  The row sums here and the column sums below leave the pair's own term out.
+__global__ __launch_bounds__(POOL_THREADS) void sensim_rows_kernel(const float* __restrict__ scat, const float* __restrict__ tcat,
+                                                                   float* __restrict__ row_loss, float* __restrict__ da, float* __restrict__ dm,
+                                                                   float* __restrict__ row_s, float* __restrict__ row_t, int B, int Ns, int Nt,
+                                                                   int d) {
+  __shared__ float red[16];
+  __shared__ float a[IMT_CONTRASTIVE_MAX_N];
+  __shared__ float m[IMT_CONTRASTIVE_MAX_N];
+  __shared__ __attribute__((aligned(16))) float sv[IMT_POOL_MAX_D];
+  __shared__ __attribute__((aligned(16))) float tv[IMT_POOL_MAX_D];
+  const int i = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int ncol4 = d >> 2;
+  const float* src = scat + (int64_t)(Ns - B + i) * d;
+  const float* tgt = tcat + (int64_t)(Nt - B + i) * d;
+  if (t < ncol4) {
+    Vec4<float>::store(sv + t * 4, Vec4<float>::load(src + t * 4));
+    Vec4<float>::store(tv + t * 4, Vec4<float>::load(tgt + t * 4));
+  }
+  __syncthreads();
+  for (int j = wave; j < Nt; j += POOL_THREADS / 64) {
+    float acc = 0.f;
+    for (int k = lane * 4; k < d; k += 256) acc += dot4(Vec4<float>::load(sv + k), Vec4<float>::load(tcat + (int64_t)j * d + k));
+    acc = wave_sum(acc);
+    if (lane == 0) a[j] = acc;
+  }
+  for (int j = wave; j < Ns; j += POOL_THREADS / 64) {
+    float acc = 0.f;
+    for (int k = lane * 4; k < d; k += 256) acc += dot4(Vec4<float>::load(tv + k), Vec4<float>::load(scat + (int64_t)j * d + k));
+    acc = wave_sum(acc);
+    if (lane == 0) m[j] = acc;
+  }
+  __syncthreads();
+  const int own_a = Nt - B + i, own_m = Ns - B + i;
+  float sa = 0.f, sm = 0.f;
+  for (int j = t; j < Nt; j += POOL_THREADS) sa += j == own_a ? 0.f : expf(a[j]);
+  for (int j = t; j < Ns; j += POOL_THREADS) sm += j == own_m ? 0.f : expf(m[j]);
+  sa = block_sum(sa, red);
+  sm = block_sum(sm, red);
+  const float rest = (sa + sm) + 1e-4f;
+  const float den = rest + (expf(a[own_a]) + expf(m[own_m]));
+  if (t == 0) row_loss[i] = logf(den) - (a[own_a] + 1e-4f);
+  __syncthreads();
+  const float inv_b = 1.0f / (float)B;
+  const float own_coef = -(rest / den) * inv_b;
+  for (int j = t; j < Nt; j += POOL_THREADS) {
+    const float g = expf(a[j]) / den * inv_b;
+    a[j] = g;
+    da[(int64_t)i * Nt + j] = g;
+  }
+  for (int j = t; j < Ns; j += POOL_THREADS) {
+    const float g = expf(m[j]) / den * inv_b;
+    m[j] = g;
+    dm[(int64_t)i * Ns + j] = g;
+  }
+  __syncthreads();
+  if (t == 0) a[own_a] = m[own_m] = 0.f;  // the pair's own term is in own_coef
+  __syncthreads();
+  if (t < ncol4) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int j = 0; j < Nt; ++j) acc += Vec4<float>::load(tcat + (int64_t)j * d + t * 4) * a[j];
+    Vec4<float>::store(row_s + (int64_t)i * d + t * 4, acc + Vec4<float>::load(tv + t * 4) * own_coef);
+    f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int j = 0; j < Ns; ++j) acc2 += Vec4<float>::load(scat + (int64_t)j * d + t * 4) * m[j];
+    Vec4<float>::store(row_t + (int64_t)i * d + t * 4, acc2 + Vec4<float>::load(sv + t * 4) * own_coef);
+  }
+}
+
+// Workgroup c < Ns: d_scat_c = sum_i dM_ic tgt_i (in order); when c is one of the last B rows its own pair is left out of the sum
+// and row_s of that pair (which holds the pair's own term) is added.  Workgroup Ns + c: d_tcat_c = sum_i dA_ic src_i, plus row_t,
+// likewise.  Every output row has this one writer.  Workgroup 0 also adds the row losses.
+__global__ __launch_bounds__(POOL_THREADS) void sensim_cols_kernel(const float* __restrict__ scat, const float* __restrict__ tcat,
+                                                                   const float* __restrict__ da, const float* __restrict__ dm,
+                                                                   const float* __restrict__ row_s, const float* __restrict__ row_t,
+                                                                   const float* __restrict__ row_loss, float* __restrict__ d_scat,
+                                                                   float* __restrict__ d_tcat, float* __restrict__ loss, int B, int Ns, int Nt,
+                                                                   int d) {
+  const int t = threadIdx.x;
+  const bool src_side = (int)blockIdx.x < Ns;
+  const int c = src_side ? (int)blockIdx.x : (int)blockIdx.x - Ns;
+  const int n = src_side ? Ns : Nt;
+  const float* dc = src_side ? dm : da;                                            // [B, n]
+  const float* other = src_side ? tcat + (int64_t)(Nt - B) * d : scat + (int64_t)(Ns - B) * d;  // the B vectors of the other side
+  const float* row = src_side ? row_s : row_t;
+  float* out = src_side ? d_scat : d_tcat;
+  const int own = c - (n - B);  // the pair this row belongs to; negative for a negative sample
+  if (t < (d >> 2)) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int i = 0; i < B; ++i) acc += Vec4<float>::load(other + (int64_t)i * d + t * 4) * (i == own ? 0.f : dc[(int64_t)i * n + c]);
+    if (own >= 0) acc += Vec4<float>::load(row + (int64_t)own * d + t * 4);
+    Vec4<float>::store(out + (int64_t)c * d + t * 4, acc);
+  }
+  if (blockIdx.x == 0 && t == 0) {
+    float s = 0.f;
+    for (int i = 0; i < B; ++i) s += row_loss[i];
+    loss[0] = s / (float)B;
+  }
+}
+
+// ------------------------------------------------------------------------------------------- pair dot products (SenSim similarity)
+// out_r = a_r . b_r (src/sen_sim.py:112), one wave per row: lane sums of 4-element groups, then the wave butterfly.
+__global__ __launch_bounds__(POOL_THREADS) void pair_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out,
+                                                                int64_t rows, int d) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (POOL_THREADS / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;  // whole waves leave: no barrier follows
+  float acc = 0.f;
+  for (int k = lane * 4; k < d; k += 256) acc += dot4(Vec4<float>::load(a + r * d + k), Vec4<float>::load(b + r * d + k));
+  acc = wave_sum(acc);
+  if (lane == 0) out[r] = acc;
+}
+
+// da_r = g_r b_r, db_r = g_r a_r; one thread per 4-element group, grid-stride
+__global__ __launch_bounds__(256) void pair_dot_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ g,
+                                                           float* __restrict__ da, float* __restrict__ db, int64_t n4, int ncol4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float gr = g[i / ncol4];
+    const f32x4 av = Vec4<float>::load(a + i * 4), bv = Vec4<float>::load(b + i * 4);
+    Vec4<float>::store(da + i * 4, bv * gr);
+    Vec4<float>::store(db + i * 4, av * gr);
+  }
+}
+
+int pair_dot_validate(const char* what, int64_t rows, int d) {
+  IMT_CHECK_ARG(rows >= 0 && rows <= 0x7fffffff, "%s: row count outside [0, 2^31)", what);
+  IMT_CHECK_ARG(d >= 4 && d % 4 == 0, "%s: d must be a positive multiple of 4", what);
+  IMT_CHECK_ARG(d <= IMT_POOL_MAX_D, "%s: d above %d is not taken", what, IMT_POOL_MAX_D);
+  return IMT_OK;
+}
+
 // Everything the four pooling entry points share and that can be settled without touching the device: the shape is refused or
 // taken (in the order dtype, rows, S, d, dropout_p), then the LDS plan, the dropout constants and the profiler's bytes of x.
 struct PoolPlan { int keep; size_t lds; uint32_t thresh; float inv_keep; double x_bytes; };
@@ -486,6 +627,56 @@ extern "C" int imt_contrastive(const float* img, const float* txt, float* loss, 
   hipLaunchKernelGGL(contrastive_rows_kernel, dim3(B), dim3(POOL_THREADS), 0, st, img, txt, row_loss, dc, d_img, B, N, d);
   IMT_CHECK_LAUNCH();
   hipLaunchKernelGGL(contrastive_cols_kernel, dim3(N), dim3(POOL_THREADS), 0, st, img, dc, row_loss, d_txt, loss, B, N, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_sensim_loss(const float* scat, const float* tcat, float* loss, float* d_scat, float* d_tcat, float* ws, int B, int Ns,
+                               int Nt, int d, void* stream) {
+  IMT_CHECK_ARG(B >= 1, "sensim_loss: B must be at least 1");
+  IMT_CHECK_ARG(Ns >= B && Nt >= B, "sensim_loss: fewer vectors on a side than pairs (the last B of each side are the pairs)");
+  IMT_CHECK_ARG(Ns <= IMT_CONTRASTIVE_MAX_N && Nt <= IMT_CONTRASTIVE_MAX_N, "sensim_loss: more than %d vectors on a side are not taken",
+                IMT_CONTRASTIVE_MAX_N);
+  IMT_CHECK_ARG(d >= 4 && d % 4 == 0, "sensim_loss: d must be a positive multiple of 4");
+  IMT_CHECK_ARG(d <= IMT_POOL_MAX_D, "sensim_loss: d above %d is not taken", IMT_POOL_MAX_D);
+  IMT_CHECK_ARG(scat && tcat && loss && d_scat && d_tcat && ws, "sensim_loss: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  float* da = ws;                          // [B, Nt]
+  float* dm = da + (int64_t)B * Nt;        // [B, Ns]
+  float* row_s = dm + (int64_t)B * Ns;     // [B, d]
+  float* row_t = row_s + (int64_t)B * d;   // [B, d]
+  float* row_loss = row_t + (int64_t)B * d;  // [B]
+  ImtProfScope prof("sensim_loss", 6.0 * B * ((double)Ns + Nt) * d, 4.0 * ((double)Ns + Nt) * d * 3, st);
+  hipLaunchKernelGGL(sensim_rows_kernel, dim3(B), dim3(POOL_THREADS), 0, st, scat, tcat, row_loss, da, dm, row_s, row_t, B, Ns, Nt, d);
+  IMT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sensim_cols_kernel, dim3(Ns + Nt), dim3(POOL_THREADS), 0, st, scat, tcat, da, dm, row_s, row_t, row_loss, d_scat,
+                     d_tcat, loss, B, Ns, Nt, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_pair_dot(const float* a, const float* b, float* out, int64_t rows, int d, void* stream) {
+  const int rc = pair_dot_validate("pair_dot", rows, d);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(a && b && out, "pair_dot: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  ImtProfScope prof("pair_dot", 2.0 * rows * d, 8.0 * rows * d, st);
+  hipLaunchKernelGGL(pair_dot_kernel, dim3((unsigned)imt_cdiv(rows, POOL_THREADS / 64)), dim3(POOL_THREADS), 0, st, a, b, out, rows, d);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
+
+extern "C" int imt_pair_dot_bwd(const float* a, const float* b, const float* g, float* da, float* db, int64_t rows, int d, void* stream) {
+  const int rc = pair_dot_validate("pair_dot_bwd", rows, d);
+  if (rc != IMT_OK) return rc;
+  if (rows == 0) return IMT_OK;
+  IMT_CHECK_ARG(a && b && g && da && db, "pair_dot_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n4 = rows * (d >> 2);
+  const int64_t wgs = (n4 + 255) / 256;
+  ImtProfScope prof("pair_dot_bwd", 2.0 * rows * d, 16.0 * rows * d, st);
+  hipLaunchKernelGGL(pair_dot_bwd_kernel, dim3((unsigned)(wgs < 2048 ? wgs : 2048)), dim3(256), 0, st, a, b, g, da, db, n4, d >> 2);
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }

@@ -706,6 +706,44 @@ def l2_dist(pred, target):
     return loss, dpred
 
 
+# ------------------------------------------------------------------------------------------- SenSim tail
+def sensim_loss(scat, tcat, B):
+    """(loss [1], d_scat [Ns, d], d_tcat [Nt, d]) of the two-sided contrastive loss over fp32 unit vectors (imt_sensim_loss);
+    the last B rows of scat / tcat are the sentence pairs, the rows before them each side's negatives."""
+    _req_cuda(scat, tcat)
+    Ns, d = scat.shape
+    Nt = tcat.shape[0]
+    B = int(B)
+    assert scat.dtype == tcat.dtype == torch.float32 and scat.is_contiguous() and tcat.is_contiguous() and tcat.shape[1] == d
+    loss = torch.empty((1,), device=scat.device, dtype=torch.float32)
+    d_scat, d_tcat = torch.empty_like(scat), torch.empty_like(tcat)
+    ws = torch.empty((max(B, 0) * (Ns + Nt + 2 * d + 1),), device=scat.device, dtype=torch.float32)
+    L.check(L.load().imt_sensim_loss(_p(scat), _p(tcat), _p(loss), _p(d_scat), _p(d_tcat), _p(ws), B, Ns, Nt, d, _stream()),
+            "imt_sensim_loss")
+    return loss, d_scat, d_tcat
+
+
+def pair_dot(a, b):
+    """out [rows] fp32: out_r = a_r . b_r over fp32 [rows, d] tensors (imt_pair_dot)."""
+    _req_cuda(a, b)
+    assert a.dim() == 2 and a.shape == b.shape and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    rows, d = a.shape
+    out = torch.empty((rows,), device=a.device, dtype=torch.float32)
+    L.check(L.load().imt_pair_dot(_p(a), _p(b), _p(out), rows, d, _stream()), "imt_pair_dot")
+    return out
+
+
+def pair_dot_bwd(a, b, g):
+    """(da, db) = (g_r b_r, g_r a_r) for an upstream g [rows] fp32 (imt_pair_dot_bwd)."""
+    _req_cuda(a, b, g)
+    assert a.dim() == 2 and a.shape == b.shape and a.dtype == b.dtype == g.dtype == torch.float32
+    assert a.is_contiguous() and b.is_contiguous() and g.is_contiguous() and tuple(g.shape) == (a.shape[0],)
+    rows, d = a.shape
+    da, db = torch.empty_like(a), torch.empty_like(b)
+    L.check(L.load().imt_pair_dot_bwd(_p(a), _p(b), _p(g), _p(da), _p(db), rows, d, _stream()), "imt_pair_dot_bwd")
+    return da, db
+
+
 def add_rows_dropout(x, add=None, out_dtype=None, dropout_p=0.0, dropout_seed=0):
     """out[r, :] = dropout(x[r, :] + add[r % add.shape[0], :]) for a 2-D x (imt_add_rows_dropout); add may be None."""
     _req_cuda(x, add)

@@ -471,6 +471,29 @@ int imt_sent_pool_bwd(int dtype, const void* x, const void* w, const uint8_t* ma
 int imt_l2_dist(int dtype, const void* pred, const void* target, float* loss, void* dpred, float* ws, int B, int64_t n,
                 void* stream);
 
+/* ------------------------------------------------------------------ tail of SenSim (src/sen_sim.py:68-113)
+ * The sentence vectors are pooled by imt_attn_pool_fwd (the same one-vector attention and the same / (norm + 1e-4)).
+ * imt_sensim_loss (:94-103), the two-sided contrastive loss: scat [Ns, d] = the source negatives followed by the B sources,
+ *   tcat [Nt, d] = the target negatives followed by the B targets (the reference's cat([neg, pos])), fp32 unit vectors;
+ *   src_i = scat[Ns - B + i], tgt_i = tcat[Nt - B + i].  A = src tcat^T [B, Nt], M = tgt scat^T [B, Ns],
+ *   D_i = sum_j exp A_ij + sum_j exp M_ij + 1e-4, loss[0] = sum_i (log D_i - (src_i . tgt_i + 1e-4)) / B.  No max is subtracted
+ *   (unit vectors: every exponent lies in [-1, 1]).  The gradients come from the same call, d_scat [Ns, d] and d_tcat [Nt, d]
+ *   OVERWRITTEN: with dA = exp A / (D B), dM = exp M / (D B), d_scat = dM^T tgt and its last B rows += dA tcat - tgt / B,
+ *   d_tcat = dA^T src and its last B rows += dM scat - src / B.  The three multiples of tgt_i in d src_i (and of src_i in
+ *   d tgt_i) nearly cancel when a pair dominates its denominator; they are added as one coefficient -R_i / (D_i B), R_i = D_i
+ *   without the pair's own two terms, summed separately, so no accuracy is lost there.  Two launches: one workgroup per pair writes dA, dM and the two
+ *   row sums to ws, then one workgroup per row of scat and tcat forms the column sums and adds the row sum of its pair -- one
+ *   writer per output row, fixed summation order, no float atomics: two identical calls give identical bits.
+ *   ws: B * (Ns + Nt) + 2 * B * d + B floats.  Without negatives the reference's loss is one-sided (:105-108): that is
+ *   imt_contrastive with N = B.
+ * imt_pair_dot (:112): out_r = a_r . b_r over fp32 [rows, d]; imt_pair_dot_bwd: da_r = g_r b_r, db_r = g_r a_r (OVERWRITTEN).
+ * Refused before any launch with IMT_ERR_BAD_ARG: a NULL tensor, B < 1, Ns < B, Nt < B, Ns or Nt above IMT_CONTRASTIVE_MAX_N,
+ * rows outside [0, 2^31), d not a positive multiple of 4 or above IMT_POOL_MAX_D.  rows == 0 returns IMT_OK without a launch. */
+int imt_sensim_loss(const float* scat, const float* tcat, float* loss, float* d_scat, float* d_tcat, float* ws, int B, int Ns,
+                    int Nt, int d, void* stream);
+int imt_pair_dot(const float* a, const float* b, float* out, int64_t rows, int d, void* stream);
+int imt_pair_dot_bwd(const float* a, const float* b, const float* g, float* da, float* db, int64_t rows, int d, void* stream);
+
 
 /* ------------------------------------------------------------------ whole encoder / decoder stacks
  * The host-side runtime that chains the kernels above for BertEncoderModel.forward (src/bert_seq2seq.py:103-144)
