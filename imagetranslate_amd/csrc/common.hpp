@@ -49,7 +49,6 @@ template <typename F> static inline int imt_by_dtype(int dtype, F&& f) {
   return dtype == IMT_F32 ? f(ImtType<float>()) : f(ImtType<bf16_t>());
 }
 
-bool imt_gemm_ln_ticket_enabled();  // gemm.hip: built with -DIMT_LN_TICKET=1 (imt_gemm's ln_out can normalise in-launch)
 // ---------------------------------------------------------------- optional launch profiler (core.hip)
 bool imt_prof_enabled();
 const char* imt_prof_intern(const char* kind, int M, int N, int K);
@@ -157,16 +156,13 @@ template <> IMT_DEVICE float from_f32<float>(float v) { return v; }
 template <> IMT_DEVICE bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
 
 // 4-element vector of T <-> f32x4 (global/LDS, 8- or 16-byte accesses)
-#ifndef IMT_WT_STORES
-#define IMT_WT_STORES 0
-#endif
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {
   typedef f32x4 type;
   static IMT_DEVICE f32x4 load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
   static IMT_DEVICE void store(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
   // write-through (sc1) store: the bytes leave the XCD's L2 as the store completes -- for data that another workgroup of the
-  // SAME launch reads (imt_gemm's in-launch LayerNorm); two 8-byte stores (the parity mode, not the fast path)
+  // SAME launch reads (the one-launch decoder step, decode_fused.hip); two 8-byte stores (the parity mode, not the fast path)
   static IMT_DEVICE void store_wt(float* p, f32x4 v) {
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
     const f32x2_t lo = {v[0], v[1]}, hi = {v[2], v[3]};
@@ -185,12 +181,7 @@ template <> struct Vec4<bf16_t> {
   }
   static IMT_DEVICE void store(bf16_t* p, f32x4 v) {
     bf16x4 r = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-#if IMT_WT_STORES  // experiment: write-through (sc1) output stores, nothing left dirty for the end-of-kernel write-back
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, r), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-#else
     *reinterpret_cast<bf16x4*>(p) = r;
-#endif
   }
   static IMT_DEVICE void store_wt(bf16_t* p, f32x4 v) {  // global_store_dwordx2 ... sc1
     bf16x4 r = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};

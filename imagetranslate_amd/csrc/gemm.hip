@@ -30,37 +30,6 @@
 #include "mma.hpp"
 #include "gemm_xl.hpp"
 
-// ---- build-time tuning switches (tools/build_variant.sh builds a second library with other values for A/B runs)
-#ifndef IMT_WS_NST
-#define IMT_WS_NST 3
-#endif
-#ifndef IMT_LN_TICKET
-#define IMT_LN_TICKET 0  // 1: imt_gemm's ln_out normalises finished row blocks inside the persistent kernel's launch (row-block
-                         // tickets, ln_rowblock_tail).  Measured on C1: the tail costs 18 us per
-                         // launch against 8.9 us for the LayerNorm launch it replaces, and the code alone, switched off at
-                         // run time, slows every persistent launch (+0.38 ms per step) -- so it is compiled out and ln_out
-                         // takes a second launch
-#endif
-#ifndef IMT_WS_RUNAHEAD
-#define IMT_WS_RUNAHEAD 0
-#endif
-#ifndef IMT_GROUP_RUNAHEAD
-#define IMT_GROUP_RUNAHEAD 1
-#endif
-#ifndef IMT_WS_ABLATE
-#define IMT_WS_ABLATE 0
-#endif
-#ifndef IMT_WS_AHEAD
-#define IMT_WS_AHEAD true
-#endif
-#ifndef IMT_WS_ROTATE
-#define IMT_WS_ROTATE 0
-#endif
-#ifndef IMT_GROUP_NST
-#define IMT_GROUP_NST 4
-#endif
-
-
 namespace {
 
 constexpr int BM = 128, BN = 128, NTHREADS = 256;
@@ -146,9 +115,9 @@ struct EpiParams {
   unsigned long long* trace;  // tuning only (IMT_TRACE=gemm_ws | gemm_xl): per-workgroup phase time stamps
   int64_t slab_elems;         // split-K slab mode: C of K split y = C + y * slab_elems (fp32 slabs)
   int splits = 1;             // persistent kernel, split-K slab mode: K ranges per output tile (imt_gemm_args.splitk_ws)
-  // in-launch LayerNorm of finished row blocks (persistent kernel, one tile per workgroup; ln_rowblock_tail)
+  // LayerNorm of the finished rows in the split-K epilogue launch (splitk_epilogue_ln_kernel)
   const void* ln_gamma = nullptr; const void* ln_beta = nullptr; void* ln_out = nullptr; int64_t ld_ln = 0;
-  float* ln_mean = nullptr; float* ln_rstd = nullptr; int* ln_tickets = nullptr; float ln_eps = 0.f;
+  float* ln_mean = nullptr; float* ln_rstd = nullptr; float ln_eps = 0.f;
 };
 
 // ------------------------------------------------------------------------------------------------ tile product
@@ -204,7 +173,7 @@ IMT_DEVICE void mma_step_interleaved(f32x4 (&acc)[4][4], const typename Frag<T>:
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) if (!(IMT_WS_ABLATE & 1)) mma16(acc[i][j], fb[j], fa[i]);  // C^T tile: rows <- n, cols <- m
+    for (int j = 0; j < 4; ++j) mma16(acc[i][j], fb[j], fa[i]);  // C^T tile: rows <- n, cols <- m
 #pragma unroll
   for (int k = 0; k < S::NR; ++k) {
     __builtin_amdgcn_sched_group_barrier(0x008, S::PER, 0);  // MFMA
@@ -392,13 +361,8 @@ IMT_DEVICE void epilogue_fast(const f32x4 (*acc)[4], char* smem, int m0, int n0,
       if (KIND == EM_F32_ACC) v += pc[gq];
       if (live) {
         // (non-temporal stores here, to leave less dirty data for the end-of-kernel write-back: no measurable change)
-        if (IMT_LN_TICKET && ep.ln_out) {  // read by another workgroup of this launch: write-through (uniform branch)
-          if (C32) Vec4<float>::store_wt(reinterpret_cast<float*>(ep.C) + m * ep.ldc + n, v);
-          else     Vec4<T>::store_wt(reinterpret_cast<T*>(ep.C) + m * ep.ldc + n, v);
-        } else {
-          if (C32) Vec4<float>::store(reinterpret_cast<float*>(ep.C) + m * ep.ldc + n, v);
-          else     Vec4<T>::store(reinterpret_cast<T*>(ep.C) + m * ep.ldc + n, v);
-        }
+        if (C32) Vec4<float>::store(reinterpret_cast<float*>(ep.C) + m * ep.ldc + n, v);
+        else     Vec4<T>::store(reinterpret_cast<T*>(ep.C) + m * ep.ldc + n, v);
       }
     }
   }
@@ -440,11 +404,11 @@ IMT_DEVICE void epilogue_general(const f32x4 (*acc)[4], char* smem, int m0, int 
         if (ep.c_f32) {
           float* c = reinterpret_cast<float*>(ep.C) + (int64_t)m * ep.ldc + n;
           if (ep.accumulate) v += Vec4<float>::load(c);
-          if (IMT_LN_TICKET && ep.ln_out) Vec4<float>::store_wt(c, v); else Vec4<float>::store(c, v);
+          Vec4<float>::store(c, v);
         } else {
           T* c = reinterpret_cast<T*>(ep.C) + (int64_t)m * ep.ldc + n;
           if (ep.accumulate) v += Vec4<T>::load(c);
-          if (IMT_LN_TICKET && ep.ln_out) Vec4<T>::store_wt(c, v); else Vec4<T>::store(c, v);
+          Vec4<T>::store(c, v);
         }
         continue;
       }
@@ -678,110 +642,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_pipe_kernel(const T* __restrict
 }
 
 
-// ------------------------------------------------------------------------------------------------ in-launch LayerNorm
-// LayerNorm(dropout(dense(x)) + input) without a second launch (src/bert_seq2seq.py:84-90,139-143).  A row needs all N
-// columns, i.e. the nbx column tiles of its 128-row block, which different workgroups compute.  No workgroup waits for
-// another: every workgroup stores its C tile write-through (sc1), drains its stores, and one lane takes a ticket of the row
-// block with an agent-scope atomic add; the workgroup whose ticket is the last one (nbx - 1) knows that all tiles of the
-// block are in memory and normalises the block's rows, reading C around its L1 / L2 (sc1 loads: the other tiles were
-// written by other CUs).  This is the "last arriver" hand-off of MI355X_MICROARCH.md (section Workgroup dispatch ...:
-// every store of the handed-off bytes sc1 and drained by its wave before the workgroup's one atomic add; every load of them
-// an sc1 buffer load to registers issued after the add has returned and a workgroup barrier).  The ticket returns to zero
-// for the next launch.  All WS_THREADS threads of the workgroup call this (barriers inside).
-// the rows of one finished block: each wave takes 16 of the 128 rows, eight at a time with all their loads in flight
-// (a row is one dependent load -> reduce -> store chain: taken one by one, sixteen memory round trips per wave)
-template <typename T, int NCH>
-IMT_DEVICE void ln_finished_rows(const EpiParams& ep, int m0, int rows, int M, int N) {
-  constexpr int EPL = 16 / sizeof(T);  // elements per lane and chunk (one 16-byte load)
-  constexpr int CW = 64 * EPL;         // columns per chunk
-  constexpr int RB = 8;                // rows in flight per wave
-  typedef typename Frag<T>::type vec_t;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // one descriptor over the whole C view; offsets stay below 2^31 (host-checked)
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(ep.C, 0, (int)(((int64_t)(M - 1) * ep.ldc + N) * sizeof(T)), 0x00020000);
-  float g[NCH][EPL], b[NCH][EPL];
-  int col[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    col[i] = min(lane * EPL + i * CW, N - EPL);  // clamped: loads unconditional, masked at use
-    const vec_t gv = *reinterpret_cast<const vec_t*>(reinterpret_cast<const T*>(ep.ln_gamma) + col[i]);
-    const vec_t bv = *reinterpret_cast<const vec_t*>(reinterpret_cast<const T*>(ep.ln_beta) + col[i]);
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) { g[i][e] = (float)gv[e]; b[i][e] = (float)bv[e]; }
-  }
-  for (int r0 = wave * 16; r0 < rows; r0 += 16 * 8) {  // (128 rows, 8 waves: one trip)
-#pragma unroll
-    for (int h = 0; h < 16; h += RB) {
-      u32x4 raw[RB][NCH];
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const int64_t m = m0 + min(r0 + h + k, rows - 1);  // clamped row: read, not used
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-          raw[k][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, (int)((m * ep.ldc + col[i]) * sizeof(T)), 0, 16 /* sc1 */));
-      }
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const int r = r0 + h + k;
-        const int64_t m = m0 + r;
-        float v[NCH][EPL];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const vec_t x = __builtin_bit_cast(vec_t, raw[k][i]);
-          const bool live = lane * EPL + i * CW < N;
-#pragma unroll
-          for (int e = 0; e < EPL; ++e) { v[i][e] = (float)x[e]; if (live) s += v[i][e]; }
-        }
-        const float mean = wave_sum(s) / (float)N;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-          if (lane * EPL + i * CW < N) {
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) { const float t = v[i][e] - mean; q += t * t; }
-          }
-        const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)N + ep.ln_eps);
-        if (r < rows) {
-          if (lane == 0) {
-            if (ep.ln_mean) ep.ln_mean[m] = mean;
-            if (ep.ln_rstd) ep.ln_rstd[m] = rstd;
-          }
-          T* yr = reinterpret_cast<T*>(ep.ln_out) + m * ep.ld_ln;
-#pragma unroll
-          for (int i = 0; i < NCH; ++i) {
-            const int c = lane * EPL + i * CW;
-            if (c < N) {
-              vec_t o;
-#pragma unroll
-              for (int e = 0; e < EPL; ++e) o[e] = from_f32<T>((v[i][e] - mean) * rstd * g[i][e] + b[i][e]);
-              *reinterpret_cast<vec_t*>(yr + c) = o;
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// (not inlined: inlined into the persistent kernel its registers pushed the kernel past the 256 a wave gets at two waves per
-// SIMD and the main loop spilled)
-template <typename T>
-__device__ __attribute__((noinline)) void ln_rowblock_tail(const EpiParams& ep, char* lds, int m0, int row_block, int nbx, int M, int N) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's C stores have completed (written through)
-  __syncthreads();
-  int* flag = reinterpret_cast<int*>(lds);
-  if (threadIdx.x == 0) *flag = __hip_atomic_fetch_add(ep.ln_tickets + row_block, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (*flag != nbx - 1) return;  // uniform
-  if (threadIdx.x == 0) __hip_atomic_store(ep.ln_tickets + row_block, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int rows = min(BM, M - m0);
-  const int nch = (N + 1024 / (int)sizeof(T) - 1) / (1024 / (int)sizeof(T));  // 16-byte loads: 512 bf16 / 256 fp32 columns per chunk
-  if (nch <= 1)      ln_finished_rows<T, 1>(ep, m0, rows, M, N);
-  else if (nch == 2) ln_finished_rows<T, 2>(ep, m0, rows, M, N);
-  else               ln_finished_rows<T, 4>(ep, m0, rows, M, N);  // N <= 1024 (host-checked)
-}
-
 // ------------------------------------------------------------------------------------------------ persistent wave-specialised kernel
 // The main GEMM loop of the path when K is a whole number of tiles: 512 threads, waves 0-3 multiply (64x64 each),
 // waves 4-7 stream the operand tiles by LDS-DMA into a 3-stage ring and run AHEAD ACROSS OUTPUT TILES (one workgroup
@@ -789,7 +649,7 @@ __device__ __attribute__((noinline)) void ln_rowblock_tail(const EpiParams& ep, 
 // tile stalls the MFMA waves of the next one.  The epilogue restages through its own 32 KiB (ring 96 KiB + 32 KiB
 // = 128 KiB: a communication workgroup of a data-parallel job can share the CU).  Producers keep their own counted vmcnt (only DMA), consumers' epilogue loads/stores
 // have theirs; the only coupling is one raw s_barrier per K tile plus the epilogue's four.
-constexpr int WS_NST = IMT_WS_NST;   // 96 KiB ring + 32 KiB epilogue staging = 128 KiB: leaves LDS for a co-resident communication workgroup
+constexpr int WS_NST = 3;            // 96 KiB ring + 32 KiB epilogue staging = 128 KiB: leaves LDS for a co-resident communication workgroup
 constexpr int WS_THREADS = 512;
 constexpr int WS_LDS = WS_NST * STAGE_BYTES + 32768;
 
@@ -830,24 +690,16 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
     Dma<T, A_KC> da; Dma<T, B_KC> db;
     int total = 0;
     for (int i = 0; i < my_tiles; ++i) { int lt, kt0, ntl; item(i, lt, kt0, ntl); total += ntl; }
-    int iq = 0, tq = 0;  // item / k index of the NEXT step to issue
-    int rot = 0, nt_q = 0;
+    int iq = 0, tq = 0, nt_q = 0;  // item / k index of the NEXT step to issue, K tiles of that item
     auto issue_next = [&](int slot) {
       if (tq == 0) {
         int lt, kt0;
         item(iq, lt, kt0, nt_q);
         da.init(A, lda, a_bytes, (lt / nbx) * BM, kt0 * BK, wave - 4);
         db.init(B, ldb, b_bytes, (lt % nbx) * BN, kt0 * BK, wave - 4);
-        // (experiment) the workgroups that share an operand row block start at different K tiles, so a tile is
-        // fetched from the Infinity Cache by one of them and found in the XCD's L2 by the others
-        if (IMT_WS_ROTATE && sizeof(T) == 2 && S == 1) rot = ((lt % nbx) * nt_q / nbx + (lt / nbx)) % nt_q;
       }
-      int tk = tq + rot;
-      if (tk >= nt_q) tk -= nt_q;
-      if (!(IMT_WS_ABLATE & 2)) {  // (-DIMT_WS_ABLATE=2: no DMA, the consumers multiply whatever the ring holds; 3: bare loop)
-        da.issue(smem + slot * STAGE_BYTES, tk);
-        db.issue(smem + slot * STAGE_BYTES + TILE_BYTES, tk);
-      }
+      da.issue(smem + slot * STAGE_BYTES, tq);
+      db.issue(smem + slot * STAGE_BYTES + TILE_BYTES, tq);
       if (++tq == nt_q) { tq = 0; ++iq; }
     };
     int issued = 0;
@@ -861,15 +713,10 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
       else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
-    if (IMT_WS_RUNAHEAD && total > 0) {  // run-ahead protocol: barrier q publishes step q + 1; one more barrier in front publishes step 0
-      wait_newer(issued - 1);
-      asm volatile("s_barrier" ::: "memory");
-    }
     int ci = 0, nt_c = 0;  // item being consumed and its K tiles
     if (my_tiles > 0) { int lt, kt0; item(0, lt, kt0, nt_c); }
     for (int q = 0; q < total; ++q) {
-      // steps issued after the step this barrier publishes (classic: step q; run-ahead: step q + 1)
-      wait_newer(issued - 1 - q - (IMT_WS_RUNAHEAD ? 1 : 0));
+      wait_newer(issued - 1 - q);  // steps issued after step q, which this barrier publishes
       asm volatile("s_barrier" ::: "memory");
       if (issued < total) { issue_next(cur == 0 ? WS_NST - 1 : cur - 1); ++issued; }
       cur = (cur + 1 == WS_NST) ? 0 : cur + 1;
@@ -885,7 +732,6 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
           EpiParams eps = ep;
           if (S > 1) eps.C = reinterpret_cast<float*>(ep.C) + (int64_t)ks * ep.slab_elems;
           epilogue<T, 512, false>(none, epi, (lt / nbx) * BM, (lt % nbx) * BN, -1, 0, M, N, eps, alpha);
-          if (IMT_LN_TICKET && ep.ln_out) ln_rowblock_tail<T>(ep, epi, (lt / nbx) * BM, lt / nbx, nbx, M, N);  // (host: one tile per workgroup)
         } else {
           // the consumers' epilogue: 2 passes x 2 barriers
           asm volatile("s_barrier\n\ts_barrier\n\ts_barrier\n\ts_barrier" ::: "memory");
@@ -900,7 +746,6 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
     const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
     int cur = 0;
     IMT_STAMP(ep.trace, 0);
-    if (IMT_WS_RUNAHEAD && my_tiles * nt_all > 0) asm volatile("s_barrier" ::: "memory");  // step 0 landed (same condition as the producers' total > 0; run-ahead builds: no split-K)
     for (int i = 0; i < my_tiles; ++i) {
       int lt, kt0, nt;
       const int ks = item(i, lt, kt0, nt);
@@ -913,51 +758,19 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
       ColSum<T> cs;
       cs.clear();
       const bool do_colsum = colsum_kernel && n0 == 0;
-#if IMT_WS_RUNAHEAD
-      // software pipeline over k-steps (see grouped_consumer_loop): barrier q has told us that K tile q + 1 has landed, so
-      // its first fragments are read while tile q is still being multiplied.  Not across output tiles: the fragments would
-      // be live through the epilogue.
-      typename Frag<T>::type f0a[4], f0b[4], f1a[4], f1b[4];
-      {
-        const char* t0 = smem + cur * STAGE_BYTES;  // first K tile of this output tile: landed (initial barrier / the previous K tile's)
-        load_frags_in_use_order<T, LAYOUT>(f0a, f0b, t0, t0 + TILE_BYTES, wm, wn, 0);
-      }
-      for (int t = 0; t < nt; ++t) {
-        if (i == 0 && t == 0) IMT_STAMP(ep.trace, 1);
-        const char* ta = smem + cur * STAGE_BYTES;
-        load_frags_in_use_order<T, LAYOUT>(f1a, f1b, ta, ta + TILE_BYTES, wm, wn, 1);
-        mma_step_interleaved<T, LAYOUT>(acc, f0a, f0b);
-        __builtin_amdgcn_sched_barrier(0);
-        // barrier q: K tile q + 1 has landed (read below), and everyone is done with tile q - 1 (its slot is refilled).
-        // Half a tile into the iteration: the first tile of a launch does not wait for the second one to land
-        asm volatile("s_barrier" ::: "memory");
-        const int nxt = (cur + 1 == WS_NST) ? 0 : cur + 1;
-        const char* tn = smem + nxt * STAGE_BYTES;  // K tile t + 1 (past the last one: read and never used)
-        load_frags_in_use_order<T, LAYOUT>(f0a, f0b, tn, tn + TILE_BYTES, wm, wn, 0);
-        mma_step_interleaved<T, LAYOUT>(acc, f1a, f1b);
-        __builtin_amdgcn_sched_barrier(0);
-        if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(ta);
-        cur = nxt;
-      }
-#else
       for (int t = 0; t < nt; ++t) {
         asm volatile("s_barrier" ::: "memory");
         if (i == 0 && t == 0) IMT_STAMP(ep.trace, 1);
         const char* ta = smem + cur * STAGE_BYTES;
-        // (-DIMT_WS_ABLATE=1: fill only.  Compile-time: a run-time branch around the product makes the compiler copy
-        // the 64 accumulator registers at every K tile, which is what such a probe then measures)
-        if (!(IMT_WS_ABLATE & 1)) compute_tile<T, LAYOUT, IMT_WS_AHEAD>(acc, ta, ta + TILE_BYTES, wm, wn);
+        compute_tile<T, LAYOUT, true>(acc, ta, ta + TILE_BYTES, wm, wn);
         if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(ta);
         cur = (cur + 1 == WS_NST) ? 0 : cur + 1;
       }
-#endif
       if (i == 0) IMT_STAMP(ep.trace, 2);
       EpiParams eps = ep;
       if (S > 1) eps.C = reinterpret_cast<float*>(ep.C) + (int64_t)ks * ep.slab_elems;
-      if (i == my_tiles - 1) {
-        epilogue<T, 512, true>(acc, epi, m0, n0, wm, wn, M, N, eps, alpha);  // producers join in
-        if (IMT_LN_TICKET && ep.ln_out) ln_rowblock_tail<T>(ep, epi, m0, lt / nbx, nbx, M, N);
-      } else epilogue<T>(acc, epi, m0, n0, wm, wn, M, N, eps, alpha);
+      if (i == my_tiles - 1) epilogue<T, 512, true>(acc, epi, m0, n0, wm, wn, M, N, eps, alpha);  // producers join in
+      else                   epilogue<T>(acc, epi, m0, n0, wm, wn, M, N, eps, alpha);
       if (i == 0) IMT_STAMP(ep.trace, 3);
       if (i == my_tiles - 1) IMT_STAMP(ep.trace, 4);
       if (colsum_kernel) cs.flush(epi, ep.a_colsum, m0, M, alpha, do_colsum);
@@ -1140,7 +953,7 @@ struct GroupArgs { int count; int total_tiles; float alpha; int alpha_pad_order 
 // max()), done by partner waves on the same SIMDs it overlaps.  One raw s_barrier per K tile: producers first wait
 // (counted vmcnt) for THEIR pieces of tile t, the barrier publishes tile t to the consumers and tells the producers
 // that the consumers are done with the buffer the next DMA overwrites.
-constexpr int GROUP_NST = IMT_GROUP_NST;       // 4: 128 KiB ring, three tiles in flight
+constexpr int GROUP_NST = 4;                   // 128 KiB ring, three tiles in flight
 constexpr int GROUP_THREADS = 512;
 
 // Consumer side of the grouped weight-gradient kernel: software pipeline over k-steps, across tile boundaries -- the LDS
@@ -1178,7 +991,7 @@ IMT_DEVICE void grouped_consumer_loop(f32x4 (&acc)[4][4], f32x4 (&bacc)[2], cons
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) if (!(IMT_WS_ABLATE & 1)) mma16(acc[i][j], f0b[j], f0a[i]);
+      for (int j = 0; j < 4; ++j) mma16(acc[i][j], f0b[j], f0a[i]);
     if (CS) { mma16(bacc[0], ones, f0a[LO ? 0 : 2]); mma16(bacc[1], ones, f0a[LO ? 1 : 3]); }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -1192,7 +1005,7 @@ IMT_DEVICE void grouped_consumer_loop(f32x4 (&acc)[4][4], f32x4 (&bacc)[2], cons
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) if (!(IMT_WS_ABLATE & 1)) mma16(acc[i][j], f1b[j], f1a[i]);
+      for (int j = 0; j < 4; ++j) mma16(acc[i][j], f1b[j], f1a[i]);
     if (CS) { mma16(bacc[0], ones, f1a[LO ? 0 : 2]); mma16(bacc[1], ones, f1a[LO ? 1 : 3]); }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -1232,9 +1045,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  ColSum<T> cs;
-  cs.clear();
-  f32x4 bacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // bias gradient (column sums of dy), IMT_GROUP_RUNAHEAD
+  f32x4 bacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // bias gradient (column sums of dy, grouped_consumer_loop)
   const bool do_colsum = P.a_colsum && n0 == 0;
 
   if (!consumer) {
@@ -1246,7 +1057,6 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
     for (int s0 = 0; s0 < GROUP_NST - 1; ++s0)
       if (s0 < nt) { da.issue(smem + s0 * STAGE_BYTES, s0); db.issue(smem + s0 * STAGE_BYTES + TILE_BYTES, s0); }
     int cur = 0;
-#if IMT_GROUP_RUNAHEAD
     // barrier t tells the consumers that tile t + 1 has landed (they read its first fragments while still multiplying
     // tile t), and the producers that the consumers are done with tile t - 1, whose slot takes tile t + 3
     {
@@ -1263,20 +1073,6 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
       else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_barrier" ::: "memory");
-      if (t + GROUP_NST - 1 < nt && !(IMT_WS_ABLATE & 2)) {
-        const int nxt = (cur == 0) ? GROUP_NST - 1 : cur - 1;
-        da.issue(smem + nxt * STAGE_BYTES, t + GROUP_NST - 1);
-        db.issue(smem + nxt * STAGE_BYTES + TILE_BYTES, t + GROUP_NST - 1);
-      }
-      cur = (cur + 1 == GROUP_NST) ? 0 : cur + 1;
-    }
-#else
-    for (int t = 0; t < nt; ++t) {
-      const int newer = min(GROUP_NST - 2, nt - 1 - t);
-      if (newer >= 2)      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_barrier" ::: "memory");
       if (t + GROUP_NST - 1 < nt) {
         const int nxt = (cur == 0) ? GROUP_NST - 1 : cur - 1;
         da.issue(smem + nxt * STAGE_BYTES, t + GROUP_NST - 1);
@@ -1284,23 +1080,11 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
       }
       cur = (cur + 1 == GROUP_NST) ? 0 : cur + 1;
     }
-#endif
   } else {
     // ------------------------------------------------------------ consumer waves
-    int cur = 0;
-#if IMT_GROUP_RUNAHEAD
     if (!do_colsum)   grouped_consumer_loop<T, false, false>(acc, bacc, smem, nt, wm, wn);
     else if (wn == 0) grouped_consumer_loop<T, true, true>(acc, bacc, smem, nt, wm, wn);
     else              grouped_consumer_loop<T, true, false>(acc, bacc, smem, nt, wm, wn);
-#else
-    for (int t = 0; t < nt; ++t) {
-      asm volatile("s_barrier" ::: "memory");
-      const char* ta = smem + cur * STAGE_BYTES;
-      compute_tile<T, IMT_TN>(acc, ta, ta + TILE_BYTES, wm, wn);
-      if (do_colsum) cs.add_tile(ta);
-      cur = (cur + 1 == GROUP_NST) ? 0 : cur + 1;
-    }
-#endif
   }
   EpiParams ep;
   ep.C = P.C; ep.ldc = P.ldc; ep.c_f32 = 1; ep.accumulate = 1;
@@ -1310,16 +1094,12 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
   // one tile per workgroup: the epilogue is fully exposed, so all 8 waves share it (the producers have nothing left to do)
   if (consumer) epilogue<T, 512, true>(acc, smem, m0, n0, wm, wn, M, N, ep, g.alpha);
   else epilogue<T, 512, false>(acc, smem, m0, n0, wm, wn, M, N, ep, g.alpha);
-#if IMT_GROUP_RUNAHEAD
   if (do_colsum && consumer && (threadIdx.x & 63) < 16) {
     // every row of the 16 x 16 tile holds the same sums: lanes 0-15 (row group 0) publish element 0; one contributor per column
     const int mb = m0 + wm + ((wn == 0) ? 0 : 32) + (threadIdx.x & 15);
     if (mb < M)      atomicAdd(P.a_colsum + mb, bacc[0][0] * g.alpha);
     if (mb + 16 < M) atomicAdd(P.a_colsum + mb + 16, bacc[1][0] * g.alpha);
   }
-#else
-  if (do_colsum) cs.flush(smem, P.a_colsum, m0, M, g.alpha, consumer);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -1553,7 +1333,6 @@ struct GemmSwitches {
   bool no_xl;                // IMT_GEMM_NO_XL (presence): never choose the 256-tile kernel
   bool no_xl_gelu;           // IMT_GEMM_NO_XL_GELU (presence): a GELU-forward epilogue alone does not choose it
   bool no_xl_tn;             // IMT_GEMM_NO_XL_TN (presence): weight gradients do not choose it
-  bool no_ln_ticket;         // IMT_GEMM_LN_TICKET=0 (atoi): an IMT_LN_TICKET build takes the LayerNorm launch all the same
   bool no_small_splitk;      // IMT_GEMM_NO_SMALL_SPLITK (presence): imt_gemm_args.splitk_ws is never used
   int splitk_ln_min_nt;      // IMT_GEMM_SPLITK_LN_MIN_NT=<K tiles> (atoi, default 8): shortest K split when the epilogue launch normalises
   int share_cus;             // IMT_GEMM_SHARE_CUS (atoi, an empty string means 1): overrides imt_set_gemm_share_cus; -1 when unset
@@ -1564,7 +1343,7 @@ const GemmSwitches& gemm_switches() {
   static const auto has = [](const char* name) { return getenv(name) != nullptr; };
   static const auto share = [] { const char* v = getenv("IMT_GEMM_SHARE_CUS"); return !v ? -1 : (atoi(v) != 0 || v[0] == '\0') ? 1 : 0; };
   static const GemmSwitches sw = {num("IMT_GEMM_DBG", 0), has("IMT_GEMM_NO_XL"), has("IMT_GEMM_NO_XL_GELU"), has("IMT_GEMM_NO_XL_TN"),
-                                  num("IMT_GEMM_LN_TICKET", 1) == 0, has("IMT_GEMM_NO_SMALL_SPLITK"), num("IMT_GEMM_SPLITK_LN_MIN_NT", 8),
+                                  has("IMT_GEMM_NO_SMALL_SPLITK"), num("IMT_GEMM_SPLITK_LN_MIN_NT", 8),
                                   share(), has("IMT_GROUPED_PLAIN_ORDER")};  // (in the order of the fields)
   return sw;
 }
@@ -1587,9 +1366,9 @@ EpiParams slab_params(void* slabs, const imt_gemm_args* a) {
   ep.C = slabs; ep.ldc = a->N; ep.c_f32 = 1; ep.alpha = 1.0f; ep.inv_keep = 1.0f; ep.slab_elems = (int64_t)a->M * a->N;
   return ep;
 }
-void epi_set_ln(EpiParams& ep, const imt_gemm_args* a, int* tickets) {
+void epi_set_ln(EpiParams& ep, const imt_gemm_args* a) {
   ep.ln_gamma = a->ln_gamma; ep.ln_beta = a->ln_beta; ep.ln_out = a->ln_out; ep.ld_ln = a->ld_ln;
-  ep.ln_mean = a->ln_mean; ep.ln_rstd = a->ln_rstd; ep.ln_tickets = tickets; ep.ln_eps = a->ln_eps;
+  ep.ln_mean = a->ln_mean; ep.ln_rstd = a->ln_rstd; ep.ln_eps = a->ln_eps;
 }
 
 // ln_out's preconditions, checked by each strategy before its first launch (the wording differs by strategy; callers match on
@@ -1700,7 +1479,7 @@ int run_splitk_ws(const imt_gemm_args* a, const GemmFacts& f, int S, void* strea
   EpiParams ep = epi_params(a);
   const float* slabs = reinterpret_cast<const float*>(a->splitk_ws);
   if (splitk_ws_ln_fused(a)) {
-    epi_set_ln(ep, a, nullptr);
+    epi_set_ln(ep, a);
     ImtProfScope prof("gemm_splitk_epilogue_ln", 0.0, (double)a->M * a->N * (4.0 * S + 3.0 * f.es), st);
     return (a->dtype == IMT_F32) ? launch_splitk_epilogue_ln<float>(slabs, slab.slab_elems, S, a->M, a->N, ep, st)
                                  : launch_splitk_epilogue_ln<bf16_t>(slabs, slab.slab_elems, S, a->M, a->N, ep, st);
@@ -1752,20 +1531,14 @@ int run_single(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& s
   const Variant variant = choose_variant(a, f, sw, splits, sw.share_cus >= 0 ? sw.share_cus != 0 : g_share_cus != 0);
   EpiParams ep = epi_params(a);
   ep.atomic = (splits > 1); ep.dbg = a->force_general / 100 | sw.dbg;
-  // LayerNorm of the finished rows: in-launch (ln_rowblock_tail) when this is a one-tile-per-workgroup launch of the
-  // persistent kernel over whole 128-column tiles; otherwise a LayerNorm launch behind the GEMM
-  const bool ln_in_launch = a->ln_out && IMT_LN_TICKET && !sw.no_ln_ticket && variant == V_WS && f.tiles <= 256 && a->N % BN == 0 && a->N <= 1024 &&
-                            a->ln_tickets != nullptr && ((int64_t)(a->M - 1) * a->ldc + a->N) * f.es < (1ll << 31);
-  if (ln_in_launch) epi_set_ln(ep, a, a->ln_tickets);
-  int rc = check_ln_out(a, LN_SINGLE, splits, !ln_in_launch);
+  int rc = check_ln_out(a, LN_SINGLE, splits, true);  // LayerNorm of the finished rows: a launch behind the GEMM
   if (rc == IMT_OK) rc = dispatch(a, f, ep, splits, kps, variant, reinterpret_cast<hipStream_t>(stream));
-  return (rc == IMT_OK && a->ln_out && !ln_in_launch) ? layernorm_behind(a, stream) : rc;
+  return (rc == IMT_OK && a->ln_out) ? layernorm_behind(a, stream) : rc;
 }
 
 }  // namespace
 
 extern "C" int64_t imt_gemm_splitk_ws_bytes(void) { return (int64_t)256 * BM * BN * 4 + 4096; }
-bool imt_gemm_ln_ticket_enabled() { return IMT_LN_TICKET != 0; }
 extern "C" int imt_set_gemm_share_cus(int share_cus) {
   const int prev = g_share_cus;
   return g_share_cus = share_cus ? 1 : 0, prev;

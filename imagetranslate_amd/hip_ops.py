@@ -95,13 +95,13 @@ def gemm(A, B, layout, *, out=None, out_dtype=None, bias=None, resid=None, aux=N
         _req_cuda(splitk_ws)
         a.splitk_ws, a.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel() * splitk_ws.element_size()
     if ln is not None:
-        # ln = dict(gamma, beta, out, mean, rstd, tickets (int32, zero), eps): LayerNorm of the rows of `out` in the same call
-        _req_cuda(ln["gamma"], ln["beta"], ln["out"], ln["mean"], ln["rstd"], ln["tickets"])
-        assert ln["tickets"].dtype == torch.int32 and ln["tickets"].numel() >= (M + 127) // 128
+        # ln = dict(gamma, beta, out, mean, rstd, eps): LayerNorm of the rows of `out` in the same call (a "tickets" entry
+        # is accepted and ignored: imt_gemm_args.ln_tickets is reserved)
+        _req_cuda(ln["gamma"], ln["beta"], ln["out"], ln["mean"], ln["rstd"])
         a.ln_gamma, a.ln_beta = ln["gamma"].data_ptr(), ln["beta"].data_ptr()
         a.ln_out, a.ld_ln = ln["out"].data_ptr(), _rowmajor(ln["out"])
         a.ln_mean, a.ln_rstd = ln["mean"].data_ptr(), ln["rstd"].data_ptr()
-        a.ln_tickets, a.ln_eps = ln["tickets"].data_ptr(), float(ln.get("eps", 1e-12))
+        a.ln_eps = float(ln.get("eps", 1e-12))
     if not _launch:
         return a
     L.check(L.load().imt_gemm(ctypes.byref(a), _stream()), "imt_gemm")

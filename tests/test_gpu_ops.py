@@ -782,10 +782,9 @@ def test_embed_ln_and_add_ln_fused_forwards(cuda, dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("shape", [(8192, 512, 512), (8128, 512, 2048), (1000, 256, 128), (8192, 1024, 256), (300, 384, 64)])
 def test_gemm_with_layernorm_of_finished_rows(cuda, dtype, shape):
-    """imt_gemm(ln_out=...): C keeps dropout(x W^T + b) + resid, ln_out = LayerNorm(C) -- in the GEMM's own launch for
-    one-tile-per-workgroup launches of the persistent kernel (row-block tickets, write-through C, the last column tile of
-    a row block normalises it), behind it otherwise.  Against the two-launch path (same C bit for bit; LayerNorm within
-    round-off: the in-launch pass sums a row in a different lane order) and torch's LayerNorm of that C."""
+    """imt_gemm(ln_out=...): C keeps dropout(x W^T + b) + resid, ln_out = LayerNorm(C) by a LayerNorm launch behind the
+    GEMM.  Against the two calls made separately (same C bit for bit, LayerNorm within round-off) and torch's LayerNorm
+    of that C.  The `tickets` entry is the reserved imt_gemm_args.ln_tickets: ignored, so it stays zero."""
     import imagetranslate_amd.hip_ops as O
     M, N, K = shape
     g = torch.Generator().manual_seed(M + N + K)

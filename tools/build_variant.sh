@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a second copy of the library with extra compile flags, for A/B runs inside one gpurun call:
-#   tools/build_variant.sh wt -DIMT_WT_STORES=1   ->  build/libimt_hip_wt.so   (select with IMT_LIB=<path>)
+#   tools/build_variant.sh o2 -O2   ->  build/libimt_hip_o2.so   (select with IMT_LIB=<path>)
 # objects, the library and any offload-bundler debris stay under build/ (git-ignored; travels to the GPU box)
 set -e
 name=$1; shift
