@@ -226,6 +226,10 @@ SIGNATURES = {
     "imt_sensim_loss": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "imt_pair_dot": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
     "imt_pair_dot_bwd": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int, _P]),
+    "imt_proposal_attn_ws_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "imt_proposal_attn_fwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_float, _P]),
+    "imt_proposal_attn_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int,
+                                      c_int64, c_int64, _P]),
     "imt_comm_unique_id_bytes": (c_int, []),
     "imt_comm_get_unique_id": (c_int, [_P]),
     "imt_comm_init": (c_int, [_P, c_int, c_int, POINTER(c_void_p)]),

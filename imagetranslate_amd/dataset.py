@@ -32,13 +32,38 @@ def _first_pad_index(texts: torch.Tensor, pad_idx: int) -> torch.Tensor:
     return first.to(torch.long)
 
 
+def get_lex_dict(path: str) -> dict:
+    """The --dict file (src/train_image_mt.py:29-36): lines of ``id id id ...``; the first id is the key, the others its
+    proposed translations (lines with the same key add up)."""
+    lex_dict = {}
+    with open(path) as fp:
+        for line in fp:
+            ids = [int(x) for x in line.split()]
+            if ids:
+                lex_dict.setdefault(ids[0], []).extend(ids[1:])
+    return lex_dict
+
+
+def get_lex_suggestions(lex_dict, ids, pad_idx: int) -> torch.Tensor:
+    """Proposed word ids of one sentence (src/dataset.py:23-27): the union of ``lex_dict[int(w)]`` over its tokens, sorted
+    (the reference's order is a set's; the proposal attention does not depend on it), or ``[pad_idx]`` when no token has an
+    entry.  Keys are looked up as ints whether ``ids`` is a tensor or a list -- the reference looks up 0-d tensors, which hash
+    by identity and never hit."""
+    found = set()
+    for w in (ids.tolist() if torch.is_tensor(ids) else ids):
+        found.update(lex_dict.get(int(w), ()))
+    return torch.LongTensor(sorted(found)) if found else torch.LongTensor([pad_idx])
+
+
+def _pad_proposals(lex: List[torch.Tensor], pad_idx: int) -> torch.Tensor:
+    return pad_sequence(lex, batch_first=True, padding_value=pad_idx)
+
+
 class MTDataset(Dataset):
     def __init__(self, max_batch_capacity: int, max_batch: int, pad_idx: int, max_seq_len: int = 175,
                  batch_pickle_dir: Optional[str] = None, examples: Optional[List] = None, lex_dict=None,
                  keep_pad_idx: bool = True, ngpu: int = 1):
-        if lex_dict is not None:
-            raise NotImplementedError("lexical proposals (--dict) are outside the hot path (SURVEY a5)")
-        self.lex_dict = None
+        self.lex_dict = lex_dict
         self.keep_pad_idx = keep_pad_idx
         self.ngpu = ngpu
         if examples is None:
@@ -46,12 +71,13 @@ class MTDataset(Dataset):
                 examples = marshal.load(fr)
         self.batch_examples(examples, max_batch, max_batch_capacity, max_seq_len, ngpu, pad_idx)
 
-    def _emit(self, src, dst, src_langs, dst_langs, pad_idx):
+    def _emit(self, src, dst, src_langs, dst_langs, pad_idx, lex=None):
         src_batch = pad_sequence(src, batch_first=True, padding_value=pad_idx)
         dst_batch = pad_sequence(dst, batch_first=True, padding_value=pad_idx)
         entry = {"src_texts": src_batch, "src_pad_mask": src_batch != pad_idx, "dst_texts": dst_batch,
                  "dst_pad_mask": dst_batch != pad_idx, "src_langs": torch.LongTensor(src_langs),
-                 "dst_langs": torch.LongTensor(dst_langs), "proposal": torch.LongTensor([pad_idx])}
+                 "dst_langs": torch.LongTensor(dst_langs),
+                 "proposal": _pad_proposals(lex, pad_idx) if self.lex_dict is not None else torch.LongTensor([pad_idx])}
         if self.keep_pad_idx:
             entry["pad_idx"] = _first_pad_index(src_batch, pad_idx)
         self.batches.append(entry)
@@ -59,7 +85,7 @@ class MTDataset(Dataset):
     def batch_examples(self, examples, max_batch, max_batch_capacity, max_seq_len, num_gpu, pad_idx):
         self.batches = []
         budget = max_batch_capacity * 1000000
-        src, dst, sl, dl = [], [], [], []
+        src, dst, sl, dl, lex = [], [], [], [], []  # lex: one row of proposals per sentence, drawn from its source (:113-115)
         max_s = max_t = 0
         for ex in examples:
             s = torch.LongTensor(list(ex[0][:max_seq_len]))
@@ -67,13 +93,15 @@ class MTDataset(Dataset):
             new_s, new_t, n = max(max_s, s.numel()), max(max_t, t.numel()), len(src) + 1
             over = (new_s + new_t) * n > max_batch or (new_s ** 2 + new_t ** 2) * n * new_t > budget
             if over and len(src) >= num_gpu and n > 1:
-                self._emit(src, dst, sl, dl, pad_idx)
-                src, dst, sl, dl = [], [], [], []
+                self._emit(src, dst, sl, dl, pad_idx, lex)
+                src, dst, sl, dl, lex = [], [], [], [], []
                 new_s, new_t = s.numel(), t.numel()
             src.append(s); dst.append(t); sl.append(ex[2]); dl.append(ex[3])
+            if self.lex_dict is not None:
+                lex.append(get_lex_suggestions(self.lex_dict, s, pad_idx))
             max_s, max_t = new_s, new_t
         if len(src) > 0 and len(src) >= num_gpu:
-            self._emit(src, dst, sl, dl, pad_idx)
+            self._emit(src, dst, sl, dl, pad_idx, lex)
 
     def __len__(self):
         return len(self.batches)
@@ -86,9 +114,7 @@ class MassDataset(Dataset):
     def __init__(self, batch_pickle_dir: Optional[str], max_batch_capacity: int, max_batch: int, pad_idx: int,
                  max_seq_len: int = 512, keep_examples: bool = False, example_list: Optional[List] = None, lex_dict=None,
                  keep_pad_idx: bool = True, ngpu: int = 1):
-        if lex_dict is not None:
-            raise NotImplementedError("lexical proposals (--dict) are outside the hot path (SURVEY a5)")
-        self.lex_dict = None
+        self.lex_dict = lex_dict
         self.keep_pad_idx = keep_pad_idx
         self.ngpu = ngpu
         if example_list is None:
@@ -109,7 +135,7 @@ class MassDataset(Dataset):
         self.lang_ids = set()
         budget = max_batch_capacity * 1000000
         groups = []
-        cur, langs, longest = [], [], 0
+        cur, langs, lex, longest = [], [], [], 0  # lex: proposals drawn from the sentence itself (:230-232)
         for examples in self.examples_list:
             for ex in examples:
                 if len(ex[0]) > max_seq_len:
@@ -119,15 +145,18 @@ class MassDataset(Dataset):
                 new_longest, n = max(longest, len(ids)), len(cur) + 1
                 over = 2 * new_longest * n > max_batch or 2 * new_longest ** 3 * n > budget
                 if over and len(cur) >= self.ngpu and n > 1:
-                    groups.append((cur, langs))
-                    cur, langs, new_longest = [], [], len(ids)
+                    groups.append((cur, langs, lex))
+                    cur, langs, lex, new_longest = [], [], [], len(ids)
                 cur.append(ids); langs.append(ex[1])
+                if self.lex_dict is not None:
+                    lex.append(get_lex_suggestions(self.lex_dict, ids, pad_idx))
                 longest = new_longest
         if len(cur) > 0 and len(cur) >= self.ngpu:
-            groups.append((cur, langs))
-        for sents, lg in groups:
+            groups.append((cur, langs, lex))
+        for sents, lg, lx in groups:
             texts = pad_sequence([torch.LongTensor(s) for s in sents], batch_first=True, padding_value=pad_idx)
-            self.batches.append({"src_texts": texts, "langs": torch.LongTensor(lg), "proposal": torch.LongTensor([pad_idx]),
+            proposal = _pad_proposals(lx, pad_idx) if self.lex_dict is not None else torch.LongTensor([pad_idx])
+            self.batches.append({"src_texts": texts, "langs": torch.LongTensor(lg), "proposal": proposal,
                                  "pad_idx": _first_pad_index(texts, pad_idx)})
 
     def __len__(self):
@@ -211,40 +240,43 @@ class ImageCaptionDataset(Dataset):
     def __init__(self, root_img_dir: str, data_bin_file: str, max_capacity: int, text_processor, max_img_per_batch: int,
                  lex_dict=None, ngpu: int = 1, use_neg_samples: bool = False, features: Optional[RegionFeatures] = None,
                  neg_seed: int = 0):
-        if lex_dict is not None:
-            raise NotImplementedError("lexical proposals (--dict) are outside the hot path (SURVEY a5)")
+        self.lex_dict = lex_dict
         self.ngpu = ngpu
         self.use_neg_samples = bool(use_neg_samples)
         self._neg_rng = random.Random(neg_seed)
         self.pad_idx = text_processor.pad_token_id()
         self.features = features if features is not None else RegionFeatures(root_img_dir)
         self.batches, self.image_batches, self.all_captions, self.lang_ids = [], [], [], set()
+        self.proposal_batches = []  # per batch [B, Pmax] proposals drawn from the captions (:314-316), None without --dict
         budget = max_capacity * 1000000
         with open(data_bin_file, "rb") as fp:
             self.unique_images, captions = marshal.load(fp)
         tag = text_processor.id2token(captions[0][1][0])
         self.lang_ids.add(int(captions[0][1][0]))
         self.lang = text_processor.languages[tag] if tag in text_processor.languages else 0
-        cur, imgs, longest = [], [], 0
+        cur, imgs, lex, longest = [], [], [], 0
         for image_id, caption in captions:
             if str(self.unique_images[image_id]).lower().endswith(".png"):
                 continue
             cap = torch.LongTensor(list(caption))
             self.all_captions.append(cap)
             cur.append(cap); imgs.append(image_id)
+            if lex_dict is not None:
+                lex.append(get_lex_suggestions(lex_dict, cap, self.pad_idx))
             longest = max(longest, cap.numel())
             over = len(imgs) > max_img_per_batch or 2 * longest ** 3 * len(cur) > budget
             if over and len(cur) - 1 >= self.ngpu and len(cur) > 1:
-                self._emit(cur[:-1], imgs[:-1])
-                cur, imgs = [cur[-1]], [imgs[-1]]
+                self._emit(cur[:-1], imgs[:-1], lex[:-1])
+                cur, imgs, lex = [cur[-1]], [imgs[-1]], lex[-1:]  # the sentence that did not fit carries its proposals over (:328)
                 longest = cur[0].numel()
         if cur:
-            self._emit(cur, imgs)
+            self._emit(cur, imgs, lex)
 
-    def _emit(self, caps, imgs):
+    def _emit(self, caps, imgs, lex):
         texts = pad_sequence(caps, batch_first=True, padding_value=self.pad_idx)
         self.batches.append((texts, texts != self.pad_idx, _first_pad_index(texts, self.pad_idx)))
         self.image_batches.append(list(imgs))
+        self.proposal_batches.append(_pad_proposals(lex, self.pad_idx) if self.lex_dict is not None else None)
 
     def __len__(self):
         return len(self.batches)
@@ -253,7 +285,8 @@ class ImageCaptionDataset(Dataset):
         texts, mask, pad_indices = self.batches[item]
         paths = [self.unique_images[i] for i in self.image_batches[item]]
         out = {"images": self.features.get(paths), "captions": texts, "pad_idx": pad_indices,
-               "langs": torch.LongTensor([self.lang] * texts.size(0)), "caption_mask": mask, "proposal": None}
+               "langs": torch.LongTensor([self.lang] * texts.size(0)), "caption_mask": mask,
+               "proposal": self.proposal_batches[item]}
         if self.use_neg_samples:
             n = min(len(self.all_captions), max(30, int(texts.size(0))))
             out["neg"] = pad_sequence(self._neg_rng.sample(self.all_captions, n), batch_first=True, padding_value=self.pad_idx)

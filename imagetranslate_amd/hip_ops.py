@@ -656,6 +656,55 @@ def contrastive(img, txt):
     return loss, d_img, d_txt
 
 
+# ------------------------------------------------------------------------------------------- lexical proposals
+def _proposal_args(x, table, prop, gate, gamma, beta, rows_per_group):
+    _req_cuda(x, table, prop, gate, gamma, beta)
+    rows, d = x.shape
+    rows_per_group = int(rows_per_group)
+    assert x.is_contiguous() and table.is_contiguous() and table.dtype == x.dtype and table.dim() == 2 and table.shape[1] == d
+    assert prop.dtype == torch.int64 and prop.dim() == 2 and prop.is_contiguous()
+    assert rows_per_group >= 1 and prop.shape[0] * rows_per_group == rows, "one row of proposals per group of rows_per_group rows"
+    for t in (gate, gamma, beta):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == d)
+    return rows, d, int(prop.shape[1]), rows_per_group
+
+
+def proposal_attn(x, table, prop, gate, gamma, beta, rows_per_group, pad_idx, eps):
+    """(y [rows, d] in x's dtype, scores [rows, P] fp32, stats [rows, 4] fp32) of the lexical-proposal attention + gate +
+    LayerNorm (imt_proposal_attn_fwd): x [rows, d], table [V, d] in x's dtype, prop [rows / rows_per_group, P] int64,
+    gate / gamma / beta fp32 [d]."""
+    rows, d, P, rpg = _proposal_args(x, table, prop, gate, gamma, beta, rows_per_group)
+    y = torch.empty_like(x)
+    scores = torch.empty((rows, P), device=x.device, dtype=torch.float32)
+    stats = torch.empty((rows, 4), device=x.device, dtype=torch.float32)
+    L.check(L.load().imt_proposal_attn_fwd(dt(x), _p(x), _p(table), _p(prop), _p(gate), _p(gamma), _p(beta), _p(y), _p(scores),
+                                           _p(stats), rows, rpg, P, d, int(table.shape[0]), int(pad_idx), float(eps), _stream()),
+            "imt_proposal_attn_fwd")
+    return y, scores, stats
+
+
+def proposal_attn_bwd(dy, x, table, prop, gate, gamma, scores, stats, dtable, dgate, dgamma, dbeta, rows_per_group, pad_idx):
+    """dx [rows, d] in x's dtype; dtable (fp32 [V, d]), dgate, dgamma, dbeta (fp32 [d]) += the parameter gradients
+    (imt_proposal_attn_bwd, deterministic)."""
+    rows, d, P, rpg = _proposal_args(x, table, prop, gate, gamma, None, rows_per_group)
+    _req_cuda(dy, scores, stats, dtable, dgate, dgamma, dbeta)
+    assert dy.dtype == x.dtype and dy.is_contiguous() and dy.shape == x.shape
+    for t, shape in ((scores, (rows, P)), (stats, (rows, 4)), (dtable, tuple(table.shape))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+    for t in (dgate, dgamma, dbeta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == d
+    dx = torch.empty_like(x)
+    if rows == 0:
+        return dx
+    nbytes = int(L.load().imt_proposal_attn_ws_bytes(rows, rpg, P, d))
+    L.check(min(nbytes, 0), "imt_proposal_attn_ws_bytes")
+    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+    L.check(L.load().imt_proposal_attn_bwd(dt(x), _p(dy), _p(x), _p(table), _p(prop), _p(gate), _p(gamma), _p(scores), _p(stats),
+                                           _p(dx), _p(dtable), _p(dgate), _p(dgamma), _p(dbeta), _p(ws), nbytes, rows, rpg, P, d,
+                                           int(table.shape[0]), int(pad_idx), _stream()), "imt_proposal_attn_bwd")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------- Caption2Image tail
 L2_DIST_PARTS = 256  # include/imt_hip.h: IMT_L2_DIST_PARTS
 

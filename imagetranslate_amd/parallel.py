@@ -249,12 +249,14 @@ class GradSync:
 
 def _loss_of(model, batch, epsilon):
     from .mass_seq2seq import MassSeq2Seq
+    proposals = batch.get("proposal") if getattr(model, "use_proposals", False) else None  # --dict (src/train_image_mt.py:246)
     if not isinstance(model, MassSeq2Seq):  # plain Seq2Seq takes explicit masks (src/seq2seq.py:146)
         return model.loss_fused(batch["src_texts"], batch["dst_texts"], batch["src_pad_mask"], batch["dst_pad_mask"],
-                                batch["src_langs"], batch["dst_langs"], epsilon=epsilon, ntokens=batch.get("ntokens"))
+                                batch["src_langs"], batch["dst_langs"], epsilon=epsilon, proposals=proposals,
+                                ntokens=batch.get("ntokens"))
     # the trainer's model class derives the masks from the ids (src/mass_seq2seq.py:24-25)
     return model.loss_fused(src_inputs=batch["src_texts"], tgt_inputs=batch["dst_texts"], src_langs=batch["src_langs"],
-                            tgt_langs=batch["dst_langs"], epsilon=epsilon)
+                            tgt_langs=batch["dst_langs"], epsilon=epsilon, proposals=proposals)
 
 
 def clip_in_place(optimizer, store, max_norm: float, grad_scale: float = 1.0):

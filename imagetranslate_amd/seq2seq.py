@@ -113,6 +113,38 @@ class _FusedXentFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
+class _ProposalAttnFn(torch.autograd.Function):
+    """Lexical-proposal attention + gate + LayerNorm (src/seq2seq.py:110-144) over ``imt_proposal_attn_fwd`` / ``_bwd``.  The
+    word table is read in the compute dtype; gate and LayerNorm parameters are the fp32 masters.  The gradients of the table,
+    the gate and the LayerNorm go straight into the flat fp32 gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, prop, model, pad_idx, rows_per_group):
+        store = store_of(model).ensure()
+        ln = model.lexical_layer_norm
+        table = store.views(x.dtype, model.proposal_embedding.weight)[0]
+        gate, gamma, beta = store.views(torch.float32, model.lexical_gate, ln.weight, ln.bias)
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        y, scores, stats = O.proposal_attn(x2, table, prop, gate.view(-1), gamma, beta, rows_per_group, pad_idx, ln.eps)
+        ctx.store, ctx.model, ctx.layout_version = store, model, store.layout_version
+        ctx.args = (x.shape, pad_idx, rows_per_group)
+        ctx.save_for_backward(x2, table, prop, gate, gamma, scores, stats)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, table, prop, gate, gamma, scores, stats = ctx.saved_tensors
+        shape, pad_idx, rows_per_group = ctx.args
+        store, model = ctx.store, ctx.model
+        store.check_layout(ctx.layout_version, "lexical proposals")
+        ln = model.lexical_layer_norm
+        dx = O.proposal_attn_bwd(dy.to(x2.dtype).reshape(x2.shape).contiguous(), x2, table, prop, gate.view(-1), gamma, scores, stats,
+                                 store.grad_view(model.proposal_embedding.weight), store.grad_view(model.lexical_gate).view(-1),
+                                 store.grad_view(ln.weight), store.grad_view(ln.bias), rows_per_group, pad_idx)
+        store.attach_grad_views()
+        return None, dx.view(shape), None, None, None, None
+
+
 class FlatStoreModel(nn.Module):
     """What a top-level model whose parameters live in one flat store (param_store.py) needs besides its layers: the store is
     invalidated by device / dtype moves and by module or parameter assignment, ``set_compute_dtype`` picks fp32 or bf16
@@ -311,9 +343,31 @@ class Seq2Seq(FlatStoreModel):
         encoder_states = self.encoder(src_inputs, attention_mask=src_mask, token_type_ids=src_langs)
         return (encoder_states, None)
 
-    def attend_proposal(self, decoder_output, proposals, pad_idx):
-        """src/seq2seq.py:110-144 (lexical proposals, off by default): plain torch ops on the GPU, not a kernel
-        target.  Includes the reference's no-op mask fill (:132)."""
+    def attend_proposal(self, decoder_output, proposals, pad_idx, rows_per_group=None):
+        """src/seq2seq.py:110-144 (lexical proposals) as one fused kernel pair (``imt_proposal_attn_fwd`` / ``_bwd``):
+        ``decoder_output`` [B, T - 1, d] with ``proposals`` [B, P] (training: the rows of sentence b share row b), or
+        [rows, d] with ``rows_per_group`` consecutive rows sharing one row of ``proposals`` (beam search: the beam
+        repetition; default ``rows // len(proposals)``, the reference's repeat_interleave)."""
+        if proposals is None:
+            raise ValueError("this model was built with use_proposals=True: pass proposals ([B, P] word ids)")
+        proposals = proposals.to(device=self._device, dtype=torch.int64)
+        if proposals.dim() == 1:
+            proposals = proposals.unsqueeze(0)
+        proposals = proposals.contiguous()
+        if decoder_output.dim() == 3:
+            rows_per_group = decoder_output.size(1)
+        elif rows_per_group is None:
+            rows_per_group = max(1, len(decoder_output) // len(proposals))
+        if proposals.size(0) * rows_per_group != decoder_output.numel() // decoder_output.size(-1):
+            raise ValueError("attend_proposal: %d rows of proposals for %d states in groups of %d" % (
+                proposals.size(0), decoder_output.numel() // decoder_output.size(-1), rows_per_group))
+        anchor = store_of(self).ensure().anchor_if_grad()
+        return _ProposalAttnFn.apply(anchor, decoder_output, proposals, self, int(pad_idx), int(rows_per_group))
+
+    def _attend_proposal_torch(self, decoder_output, proposals, pad_idx):
+        """The same function as a composition of torch operators (it materialises the [.., P, d] products): the baseline
+        of the bf16 accuracy check and of tools/proposal_bench.py.  No product path calls it.  Includes the reference's
+        no-op mask fill (:132)."""
         device = self._device
         proposals = proposals.to(device)
         attend_mask = (proposals == pad_idx)

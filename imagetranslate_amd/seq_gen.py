@@ -235,7 +235,7 @@ class BeamDecoder(nn.Module):
                                              tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
                     states = O.gated_mix(states.contiguous(), obj_states.contiguous(), gate)
             if model.use_proposals:
-                states = model.attend_proposal(states, proposals, pad_idx)
+                states = model.attend_proposal(states.contiguous(), proposals, pad_idx, rows_per_group=rep)
             O.gemm(states.contiguous(), W, O.IMT_NT, bias=bias, out=logits[:rows])
 
             a = L.BeamArgs()

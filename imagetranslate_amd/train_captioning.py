@@ -17,7 +17,7 @@ from .option_parser import get_img_options_parser
 from .seq2seq import Seq2Seq
 from .seq_gen import BeamDecoder, get_outputs_until_eos
 from .textprocessor import TextProcessor
-from .train_image_mt import ImageMTTrainer, LossMeter, init_distributed, reject_off_path
+from .train_image_mt import ImageMTTrainer, LossMeter, init_distributed, load_lex_dict, reject_off_path, use_lex_dict
 from .utils import build_optimizer
 
 
@@ -42,7 +42,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
         if self.sync is not None:
             self.sync.begin_step()
         loss, ntokens = model.loss_fused(tgt_inputs=batch["captions"], tgt_mask=batch["caption_mask"], pad_idx=tp.pad_token_id(),
-                                         tgt_langs=batch["langs"], batch=batch)
+                                         tgt_langs=batch["langs"], batch=batch, proposals=self._proposals(batch))
         loss.backward()
         self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
@@ -55,7 +55,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
         for i in range(len(img_dev_data)):
             batch = img_dev_data[i]
             loss, n = self.model.loss_fused(tgt_inputs=batch["captions"], tgt_mask=batch["caption_mask"], pad_idx=tp.pad_token_id(),
-                                            tgt_langs=batch["langs"], batch=batch)
+                                            tgt_langs=batch["langs"], batch=batch, proposals=self._proposals(batch))
             total += float(loss) * int(n)
             count += int(n)
         self.model.train()
@@ -71,7 +71,8 @@ class ImageCaptionTrainer(ImageMTTrainer):
         for i in range(len(img_test_data) if max_batches is None else min(max_batches, len(img_test_data))):
             b = img_test_data[i]
             hyps = self.generator(images=b["images"], first_tokens=b["first_tokens"], tgt_langs=b["langs"],
-                                  pad_idx=tp.pad_token_id(), max_len=b["max_len"], objects=b.get("objects"))
+                                  pad_idx=tp.pad_token_id(), max_len=b["max_len"], objects=b.get("objects"),
+                                  proposals=self._proposals(b))
             for image_id, h in zip(b["img_ids"], hyps):
                 out[image_id] = tp.decode(h[1:].tolist()) if hasattr(tp, "decode") else h[1:].tolist()
         model.train()
@@ -136,7 +137,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
 
     @staticmethod
     def train(options):
-        reject_off_path(options, lm_supported=True)
+        reject_off_path(options, lm_supported=True, dict_supported=True)
         rank, world = init_distributed()
         random.seed(options.seed)
         torch.manual_seed(options.seed)
@@ -144,12 +145,14 @@ class ImageCaptionTrainer(ImageMTTrainer):
             os.makedirs(options.model_path, exist_ok=True)
         tp = TextProcessor(options.tokenizer_path)
         assert tp.pad_token_id() == 0
+        lex_dict = load_lex_dict(options)
         if options.pretrained_path is not None:
             caption_model = Seq2Seq.load(ImageCaptioning, options.pretrained_path, tok_dir=options.tokenizer_path,
                                          use_obj=not options.no_obj)
         else:
             caption_model = ImageCaptioning(text_processor=tp, tie_embed=options.tie_embed, resnet_depth=options.resnet_depth,
                                             lang_dec=options.lang_decoder, enc_layer=options.encoder_layer,
+                                            use_proposals=lex_dict is not None,
                                             dec_layer=options.decoder_layer, embed_dim=options.embed_dim,
                                             intermediate_dim=options.intermediate_layer_dim, use_obj=not options.no_obj,
                                             num_attention_heads=options.heads, image_feat_dim=options.feat_dim)
@@ -160,20 +163,24 @@ class ImageCaptionTrainer(ImageMTTrainer):
             caption_model.encoder = mt_model.encoder
             caption_model.decoder = mt_model.decoder
             caption_model.output_layer = mt_model.output_layer
+        use_lex_dict(caption_model, lex_dict, "train_captioning")
         caption_model.set_compute_dtype(torch.float32 if options.fp32 else torch.bfloat16)
         caption_model = caption_model.cuda().train()
         optimizer = build_optimizer(caption_model, options.learning_rate, options.warmup)
         trainer = ImageCaptionTrainer(model=caption_model, mask_prob=options.mask_prob, optimizer=optimizer, clip=options.clip,
                                       beam_width=options.beam_width, max_len_a=options.max_len_a, max_len_b=options.max_len_b,
-                                      len_penalty_ratio=options.len_penalty_ratio, rank=rank, world_size=world, seed=options.seed)
+                                      len_penalty_ratio=options.len_penalty_ratio, rank=rank, world_size=world, seed=options.seed,
+                                      lex_dict=lex_dict)
         feats = dataset.RegionFeatures(options.image_dir)
         mk_img = lambda cls, path: cls(root_img_dir=options.image_dir, data_bin_file=path, max_capacity=options.img_capacity,
-                                       text_processor=tp, max_img_per_batch=options.max_image, features=feats)
+                                       text_processor=tp, max_img_per_batch=options.max_image, features=feats,
+                                       lex_dict=lex_dict)
         img_train = mk_img(dataset.ImageCaptionDataset, options.train_path)
         img_dev = mk_img(dataset.ImageCaptionDataset, options.dev_path) if options.dev_path else None
         pad = tp.pad_token_id()
         mk_mt = lambda path: dataset.MTDataset(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad,
-                                               max_seq_len=options.max_seq_len, batch_pickle_dir=path).batches
+                                               max_seq_len=options.max_seq_len, batch_pickle_dir=path,
+                                               lex_dict=lex_dict).batches
         mt_train = sum((mk_mt(p.strip()) for p in (options.mt_train_path or "").split(",") if p.strip()), []) or None
         mt_dev = sum((mk_mt(p.strip()) for p in (options.mt_dev_path or "").split(",") if p.strip()), []) or None
         if rank == 0:

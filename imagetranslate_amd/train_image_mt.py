@@ -47,8 +47,13 @@ class ImageMTTrainer:
         self._img_rng = random.Random((seed + 2) * 104729 + rank)
         self.image_steps, self.last_image_step = 0, None  # image batches consumed; (kind, loss) of the last one
         self.generator = None  # BeamDecoder of the back-translation phase (built on first use)
+        self.lex_dict = kwargs.get("lex_dict")  # --dict: the back-translation phase looks up proposals for what it generates
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
+
+    def _proposals(self, batch):
+        """batch["proposal"] ([B, Pmax], built by the datasets from --dict) when the model attends over proposals."""
+        return batch.get("proposal") if getattr(self.model, "use_proposals", False) else None
 
     def _finish_micro_step(self, accum: int):
         """clip after EVERY backward, step every `accum` (src/train_image_mt.py:291-295)."""
@@ -72,7 +77,7 @@ class ImageMTTrainer:
             self.sync.begin_step()
         loss, ntokens = self.model.loss_fused(src_inputs=masked["src_text"], tgt_inputs=masked["to_recover"],
                                               src_langs=batch["langs"], pad_idx=tp.pad_token_id(),
-                                              tgt_positions=masked["positions"])
+                                              tgt_positions=masked["positions"], proposals=self._proposals(batch))
         loss.backward()
         self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
@@ -95,7 +100,7 @@ class ImageMTTrainer:
             loss, ntokens = self.model.loss_fused(src_inputs=masked["src_text"], tgt_inputs=masked["to_recover"],
                                                   tgt_positions=masked["positions"], src_pads=batch["caption_mask"],
                                                   pad_idx=tp.pad_token_id(), src_langs=batch["langs"], tgt_langs=batch["langs"],
-                                                  batch=batch)
+                                                  batch=batch, proposals=self._proposals(batch))
         else:  # "nothing to predict" (:274-276): the loss is back-propagated as it is and counts no tokens
             loss, ntokens = self.model.loss_fused(src_inputs=batch["captions"], src_pads=batch["caption_mask"],
                                                   neg_samples=batch["neg"], neg_mask=batch["neg_mask"],
@@ -137,13 +142,20 @@ class ImageMTTrainer:
         with torch.no_grad():
             outs = self.generator(src_inputs=src, src_sizes=batch["pad_idx"], first_tokens=target_tags, src_langs=batch["langs"],
                                   tgt_langs=dst_langs, pad_idx=pad, src_mask=src_mask, unpad_output=False,
-                                  beam_width=self.bt_kw["beam_width"])
+                                  beam_width=self.bt_kw["beam_width"], proposals=self._proposals(batch))
         model.train(was_training)
-        translations = pad_sequence([o.cpu() for o in outs], batch_first=True, padding_value=pad)
+        outs = [o.cpu() for o in outs]
+        translations = pad_sequence(outs, batch_first=True, padding_value=pad)
+        translation_proposals = None
+        if getattr(model, "use_proposals", False):  # proposals for the generated sources (:157-163)
+            if self.lex_dict is None:
+                raise ValueError("back-translation with a use_proposals model needs the dictionary (ImageMTTrainer(lex_dict=...))")
+            translation_proposals = pad_sequence([dataset.get_lex_suggestions(self.lex_dict, o, pad) for o in outs],
+                                                 batch_first=True, padding_value=pad)
         if self.sync is not None:
             self.sync.begin_step()
         loss, ntokens = model.loss_fused(src_inputs=translations, tgt_inputs=src, src_langs=dst_langs, tgt_langs=batch["langs"],
-                                         pad_idx=pad)
+                                         pad_idx=pad, proposals=translation_proposals)
         loss.backward()
         self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
@@ -154,7 +166,8 @@ class ImageMTTrainer:
         total, count = 0.0, 0
         for batch in dev_data:
             loss, n = self.model.loss_fused(src_inputs=batch["src_texts"], tgt_inputs=batch["dst_texts"],
-                                            src_langs=batch["src_langs"], tgt_langs=batch["dst_langs"])
+                                            src_langs=batch["src_langs"], tgt_langs=batch["dst_langs"],
+                                            proposals=self._proposals(batch))
             total += float(loss) * int(n)
             count += int(n)
         self.model.train()
@@ -261,19 +274,35 @@ def init_distributed():
     return rank, world
 
 
-def reject_off_path(options, lm_supported: bool = False):
+def reject_off_path(options, lm_supported: bool = False, dict_supported: bool = False):
     """Flags whose feature is not built are refused, never silently ignored: a requested pretrained initialisation or a
-    resumed optimizer that quietly trains from scratch is worse than an error."""
-    for flag, val in (("--dict", options.dict_path),):
+    resumed optimizer that quietly trains from scratch is worse than an error.  ``dict_supported``: the entry point builds a
+    model that attends over lexical proposals and feeds it from the dictionary (train_image_mt, train_captioning)."""
+    for flag, val in (("--dict", None if dict_supported else options.dict_path),):
         if val:
-            raise NotImplementedError("%s: outside the hot path (lexical proposals, DESIGN section 7)" % flag)
+            raise NotImplementedError("%s: this entry point does not train with lexical proposals (train_image_mt and "
+                                      "train_captioning do, DESIGN section 6)" % flag)
     for flag, val in (("--lm", None if lm_supported else options.lm_path), ("--cont", options.continue_train), ("--save-opt", options.save_opt)):
         if val:
             raise NotImplementedError("%s: not implemented by this trainer (masked-LM initialisation / pickled-optimizer resume, "
                                       "src/train_image_mt.py:319-321,449-462); use --pretrained to continue from saved weights" % flag)
 
 
-def load_image_data(options, tp):
+def load_lex_dict(options):
+    """--dict FILE (src/train_image_mt.py:430-432): {source word id: [proposed ids]}, or None without the flag."""
+    return dataset.get_lex_dict(options.dict_path) if getattr(options, "dict_path", None) else None
+
+
+def use_lex_dict(model, lex_dict, what: str):
+    """The dictionary the data is built with: ``lex_dict`` for a model that attends over proposals, None otherwise.  A
+    checkpoint and a --dict flag that disagree are an error, not a silent choice."""
+    if bool(getattr(model, "use_proposals", False)) != (lex_dict is not None):
+        raise ValueError("%s: the model was %s lexical proposals but --dict is %s" % (
+            what, "built with" if model.use_proposals else "built without", "given" if lex_dict is not None else "missing"))
+    return lex_dict
+
+
+def load_image_data(options, tp, lex_dict=None):
     """--image DIR with the caption file of --train (src/train_image_mt.py:468-473, :636-645): the image-caption batches, or
     None without --image.  DIR must hold a readable features.pt (dataset.RegionFeatures); negative samples are drawn unless
     every image step is a masked one."""
@@ -288,11 +317,11 @@ def load_image_data(options, tp):
     return dataset.ImageCaptionDataset(root_img_dir=options.image_dir, data_bin_file=options.train_path,
                                        max_capacity=int(options.img_capacity), text_processor=tp,
                                        max_img_per_batch=int(options.max_image), use_neg_samples=options.mm_mode != "masked",
-                                       neg_seed=options.seed)
+                                       neg_seed=options.seed, lex_dict=lex_dict)
 
 
 def train(options):
-    reject_off_path(options)
+    reject_off_path(options, dict_supported=True)
     if getattr(options, "image_dir", "") and len([l for l in (options.bt_langs or "").split(",") if l.strip()]) >= 2 \
             and options.finetune_step > 0:
         raise NotImplementedError("--image with --langs / --fstep: back-translation over image batches (src/train_image_mt.py:108-198 "
@@ -301,26 +330,30 @@ def train(options):
     random.seed(options.seed)
     torch.manual_seed(options.seed)
     tp = TextProcessor(options.tokenizer_path)
-    img_train = load_image_data(options, tp)  # before the model is built: a missing features.pt fails at once
+    lex_dict = load_lex_dict(options)  # once: every dataset and the back-translation phase share it
+    img_train = load_image_data(options, tp, lex_dict)  # before the model is built: a missing features.pt fails at once
     if img_train is not None and world > 1:
         raise NotImplementedError("--image under data parallelism is not built (ImageMTTrainer.image_step)")
     if options.pretrained_path:
         model = ImageMassSeq2Seq.load(ImageMassSeq2Seq, options.pretrained_path, tok_dir=options.tokenizer_path)
     else:
         model = ImageMassSeq2Seq(text_processor=tp, lang_dec=options.lang_decoder, tie_embed=options.tie_embed,
+                                 use_proposals=lex_dict is not None,
                                  enc_layer=options.encoder_layer, dec_layer=options.decoder_layer, embed_dim=options.embed_dim,
                                  intermediate_dim=options.intermediate_layer_dim, num_attention_heads=options.heads,
                                  resnet_depth=options.resnet_depth, image_feat_dim=options.feat_dim)
+    use_lex_dict(model, lex_dict, "train_image_mt")
     model.set_compute_dtype(torch.float32 if options.fp32 else torch.bfloat16)
     model = model.cuda().train()
     optimizer = build_optimizer(model, options.learning_rate, options.warmup)
     # (GradSync broadcasts rank 0's parameters, like the DDP constructor at src/train_image_mt.py:73)
     trainer = ImageMTTrainer(model, mask_prob=options.mask_prob, clip=options.clip, optimizer=optimizer, rank=rank, world_size=world,
                              seed=options.seed, bt_beam_width=options.bt_beam_width, max_len_a=options.max_len_a,
-                             max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio, mm_mode=options.mm_mode)
+                             max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio, mm_mode=options.mm_mode,
+                             lex_dict=lex_dict)
     pad = tp.pad_token_id()
     mk = lambda cls, path, **kw: cls(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad,
-                                     max_seq_len=options.max_seq_len, ngpu=1, **kw, **path)
+                                     max_seq_len=options.max_seq_len, ngpu=1, lex_dict=lex_dict, **kw, **path)
     mt_train, mass_train, mt_dev = [], [], None
     for pth in (options.mt_train_path or "").split(","):
         if pth.strip():

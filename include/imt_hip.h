@@ -491,6 +491,37 @@ int imt_sensim_loss(const float* scat, const float* tcat, float* loss, float* d_
 int imt_pair_dot(const float* a, const float* b, float* out, int64_t rows, int d, void* stream);
 int imt_pair_dot_bwd(const float* a, const float* b, const float* g, float* da, float* db, int64_t rows, int d, void* stream);
 
+/* ------------------------------------------------------------------ lexical proposals of Seq2Seq (src/seq2seq.py:110-144)
+ * imt_proposal_attn_fwd: x [rows, d] (`dtype`, contiguous) are decoder states, row r belonging to group g = r / rows_per_group
+ *   (a sentence: rows_per_group = T - 1 in training, the beam repetition in beam search); prop [G, P] int64 are the group's
+ *   proposed word ids, table [vocab, d] (`dtype`) the word embeddings; gate, gamma, beta [d] fp32.
+ *   e_j = table[prop[g, j]] (pad entries take part: the reference's -10000 fill is a no-op); s_j = <x_r, e_j>; p = softmax_j(s);
+ *   c = sum_j p_j e_j, or 1e-8 in every element when all of prop[g, :] == pad_idx; sg = sigmoid(gate + 1e-8);
+ *   y_r = LayerNorm(sg x_r + (1 - sg) c; gamma, beta, eps), written in `dtype`.  An id outside [0, vocab) reads row 0.
+ *   Saved for the backward: scores [rows, P] fp32 (the raw s) and stats [rows, 4] fp32 (softmax max and sum, LayerNorm mean and rstd).
+ *   All statistics and sums are fp32; no buffer of rows * P * d elements exists in either direction.
+ * imt_proposal_attn_bwd: dy [rows, d] in `dtype` -> dx [rows, d] in `dtype` (OVERWRITTEN); dgate, dgamma, dbeta [d] and
+ *   dtable [vocab, d] ACCUMULATED into fp32 (the flat gradient buffer).  A table row gets the sum over every entry of prop that
+ *   names it, duplicates within a group and across groups included, of sum over the group's rows of (p_j dc + ds_j x_r); pad_idx
+ *   (and ids outside [0, vocab)) get nothing, so an all-pad group leaves dtable alone and reaches x only through sg dz.
+ *   ws: caller-owned, 16-byte aligned, imt_proposal_attn_ws_bytes(rows, rows_per_group, P, d) bytes = p and ds [rows, P], dc
+ *   [rows, d], per-workgroup partial sums ceil(rows_per_group / 8) * G * 3 * d, the gathered gradient [G, P, d] fp32 and two
+ *   ints per entry of prop.  Partials are added in workgroup order, a group's rows in row order, the entries of one id in entry
+ *   order by a single writer: no float atomics, two identical calls give identical bits.
+ * Refused before any launch: IMT_ERR_BAD_ARG for a bad dtype, a NULL tensor, rows outside [0, 2^31) or no multiple of
+ *   rows_per_group, rows_per_group < 1, P < 1, vocab < 1, a workspace that is too small or misaligned; IMT_ERR_UNSUPPORTED for d
+ *   not a multiple of 4 in [4, IMT_PROPOSAL_MAX_D].  imt_proposal_attn_ws_bytes returns the same negative codes.  rows == 0
+ *   returns IMT_OK without a launch. */
+#define IMT_PROPOSAL_MAX_D 1024
+int64_t imt_proposal_attn_ws_bytes(int64_t rows, int rows_per_group, int P, int d);
+int imt_proposal_attn_fwd(int dtype, const void* x, const void* table, const int64_t* prop, const float* gate, const float* gamma,
+                          const float* beta, void* y, float* scores, float* stats, int64_t rows, int rows_per_group, int P, int d,
+                          int64_t vocab, int64_t pad_idx, float eps, void* stream);
+int imt_proposal_attn_bwd(int dtype, const void* dy, const void* x, const void* table, const int64_t* prop, const float* gate,
+                          const float* gamma, const float* scores, const float* stats, void* dx, float* dtable, float* dgate,
+                          float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, int64_t rows, int rows_per_group, int P, int d,
+                          int64_t vocab, int64_t pad_idx, void* stream);
+
 
 /* ------------------------------------------------------------------ whole encoder / decoder stacks
  * The host-side runtime that chains the kernels above for BertEncoderModel.forward (src/bert_seq2seq.py:103-144)
