@@ -13,6 +13,7 @@
 //               all query tiles; Q and dO tiles are staged once and read both row-wise and transposed.
 // Nothing is summed across workgroups: no atomics, bitwise reproducible.
 #include <stdlib.h>
+#include <type_traits>
 #include "mma.hpp"
 
 namespace {
@@ -572,6 +573,9 @@ __global__ __launch_bounds__(256, (DH == 64 && sizeof(T) == 2) ? 3 : 2) void att
 // in LDS, the fragments delta is taken from and the optional copy in global memory carry the bits the GEMM would have stored.
 struct ProjP { const void* dy; int64_t lddy; const void* w; int64_t ldw; int d_model; };
 
+// dynamic LDS of a launch: the Q and dO tiles, the dS^T tile, lse and delta, the query mask
+constexpr int fused_lds_bytes(int dh) { return 2 * 128 * (dh * 2) + 128 * 256 + 2 * 128 * 4 + 128; }
+
 template <int DH, bool MASK3D, bool PROJ>
 IMT_DEVICE void attn_bwd_fused_body(const AttnP& p, const ProjP& pj) {
   typedef bf16_t T;
@@ -584,6 +588,7 @@ IMT_DEVICE void attn_bwd_fused_body(const AttnP& p, const ProjP& pj) {
   float* lse_s = reinterpret_cast<float*>(dST + 128 * 256);
   float* delta_s = lse_s + 128;
   uint8_t* qmask_s = reinterpret_cast<uint8_t*>(delta_s + 128);
+  static_assert(fused_lds_bytes(DH) == 128 * RB + 128 * RB + 128 * 256 + 128 * 4 + 128 * 4 + 128, "the launches size LDS for this carve");
 
   const int lid = imt_xcd_block(blockIdx.x, gridDim.x);
   const int b = lid / p.H, h = lid % p.H;
@@ -842,6 +847,8 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_proj_kernel(AttnP p, ProjP pj
 //   phase 2: QUERY on the lane: dQ[64 x dh] = dS K from LDS (wave = 16 queries x half of dh), stored at once.
 // The [key][query] tile is 32 KiB instead of 128: 82 KiB in all.  Nothing is summed across workgroups (no atomics); same
 // masks, same dropout draws as every other attention kernel.
+constexpr int fused256_lds_bytes(int dh) { return 256 * (dh * 2) + 2 * 64 * (dh * 2) + 256 * 128 + 2 * 256 * 4 + 256; }  // K, Q | dO tiles, dS^T, lse | delta, query mask
+
 template <int DH, bool MASK3D>
 __global__ __launch_bounds__(512, 2) void attn_bwd_fused256_kernel(AttnP p) {
   typedef bf16_t T;
@@ -855,6 +862,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused256_kernel(AttnP p) {
   float* lse_s = reinterpret_cast<float*>(dST + 256 * 128);
   float* delta_s = lse_s + 256;
   uint8_t* qmask_s = reinterpret_cast<uint8_t*>(delta_s + 256);
+  static_assert(fused256_lds_bytes(DH) == 256 * RB + 64 * RB + 64 * RB + 256 * 128 + 256 * 4 + 256 * 4 + 256, "the launch sizes LDS for this carve");
 
   const int lid = imt_xcd_block(blockIdx.x, gridDim.x);
   const int b = lid / p.H, h = lid % p.H;
@@ -1042,209 +1050,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused256_kernel(AttnP p) {
   }
 }
 
-// =========================================================================================== forward: q|k|v projection + attention
-// Self-attention of a short sequence (T <= 128, head_dim 64, bf16) with the q|k|v projection of BertSelfAttention
-// (src/bert_seq2seq.py:84-90,139-143 -> HF BertSelfAttention.query / key / value) INSIDE the attention launch: one workgroup
-// (8 waves) per (batch element, PAIR of heads) computes its 128 x 384 slice of x W^T + b -- q, k and v of its two heads, the
-// 128 rows being the batch element's tokens -- with the 256-tile kernel's loop (LDS-DMA of K tiles by all waves, two 64-KiB
-// stages, one barrier per K tile), stores it (the backward reads q|k|v) and parks it in LDS as the Q / K / V tiles of
-// attn_fwd_short_kernel, whose arithmetic then runs unchanged for the two heads.  Against the projection launch + attention
-// launch it saves one launch boundary, the 24-MB re-read of q|k|v and the second cold start.  Same k order per accumulator as
-// every GEMM kernel and the same attention code: results are bit-identical to the two-launch path.
-struct QkvP { const void* x; int64_t ldx; int64_t x_bytes; const void* w; const void* bias; int d_model; };
-
-// one wave's four 1-KiB pieces of a [128 rows][64 k] K-contiguous bf16 tile (the Dma struct of gemm.hip)
-struct QkvDma {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int voff[4];
-  IMT_DEVICE void init(const bf16_t* base, int64_t ld, int64_t valid_bytes, int row0, int sub) {
-    rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, (int)valid_bytes, 0x00020000);
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = 64 * (4 * i + sub) + lane;
-      const int tr = q >> 3, pc = q & 7;
-      const int c = pc ^ swz<128>(tr);
-      voff[i] = (int)((((int64_t)(row0 + tr)) * ld + c * 8) * 2);
-    }
-  }
-  IMT_DEVICE void issue(char* tile, int sub, int t) const {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(tile + (4 * i + sub) * 1024), 16,
-                                               voff[i] + t * 128, 0, 0, 0);
-  }
-};
-
-template <bool UNUSED = false>
-__global__ __launch_bounds__(512, 2) void attn_qkv_fwd_kernel(AttnP p, QkvP g) {
-  typedef bf16_t T;
-  constexpr int DH = 64, RB = 128, NS = 2, NDT = 4;
-  typedef Frag<T>::type frag_t;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // K loop: 2 stages x (x tile | Wq | Wk | Wv tiles of 16 KiB)
-  const int hp_n = p.H >> 1;
-  const int lid = imt_xcd_block(blockIdx.x, gridDim.x);
-  const int b = lid / hp_n, hp = lid % hp_n;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 15, gq = lane >> 4;
-  const int T_ = p.Tq, d = g.d_model;
-  const int nt = d >> 6;  // K tiles of 64 (host: d % 64 == 0)
-
-  // ---- phase A: [128 tokens] x [384 = q | k | v of two heads] = x_b W_sel^T
-  QkvDma d0, d1;
-  const bf16_t* xb = reinterpret_cast<const bf16_t*>(g.x) + (int64_t)b * T_ * g.ldx;
-  const bf16_t* wq = reinterpret_cast<const bf16_t*>(g.w);
-  const int sub = wave & 3;
-  if (wave < 4) {  // waves 0-3 stream the x tile and the Wq tile, waves 4-7 the Wk and Wv tiles
-    d0.init(xb, g.ldx, g.x_bytes - (int64_t)b * T_ * g.ldx * 2, 0, sub);
-    d1.init(wq, d, (int64_t)3 * d * d * 2, hp * 128, sub);
-  } else {
-    d0.init(wq, d, (int64_t)3 * d * d * 2, d + hp * 128, sub);
-    d1.init(wq, d, (int64_t)3 * d * d * 2, 2 * d + hp * 128, sub);
-  }
-  const int t0 = wave < 4 ? 0 : 2;  // first of this wave's two sub-tiles within a stage
-  auto issue = [&](int slot, int t) {
-    d0.issue(smem + slot * 65536 + t0 * 16384, sub, t);
-    d1.issue(smem + slot * 65536 + (t0 + 1) * 16384, sub, t);
-  };
-  const int wm = (wave >> 2) * 64, c0 = (wave & 3) * 96;  // this wave's 64 rows x 96 columns
-  f32x4 acc[4][6];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  issue(0, 0);
-  for (int t = 0; t < nt; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    if (t + 1 < nt) issue((t + 1) & 1, t + 1);
-    const char* st = smem + (t & 1) * 65536;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      frag_t fa[4], fb[6];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int c = c0 + 16 * j;
-        fb[j] = lds_frag_kcontig<T, RB>(st + (1 + (c >> 7)) * 16384, c & 127, 4 * s);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = lds_frag_kcontig<T, RB>(st, wm + 16 * i, 4 * s);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) mma16(acc[i][j], fb[j], fa[i]);  // C^T tile: rows <- n, cols <- m
-    }
-  }
-  __syncthreads();  // every wave is done with the last K tile: the stages become the Q / K / V tiles
-
-  // ---- phase B: + bias, store q|k|v (the backward reads them), park them as [which][head][128 rows][64] bf16 tiles
-  char* tiles = smem;                       // tile (which, hh) at ((which * 2 + hh) * 16384)
-  uint8_t* kmask_s = reinterpret_cast<uint8_t*>(smem + 6 * 16384);
-  {
-    const bf16_t* bias = reinterpret_cast<const bf16_t*>(g.bias);
-    bf16_t* outs[3] = {reinterpret_cast<bf16_t*>(const_cast<void*>(p.Q)), reinterpret_cast<bf16_t*>(const_cast<void*>(p.K)),
-                       reinterpret_cast<bf16_t*>(const_cast<void*>(p.V))};
-    const int64_t lds_[3] = {p.ldq, p.ldk, p.ldv};
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int c = c0 + 16 * j + 4 * gq;        // column of the 384: which = c >> 7, head = (c >> 6) & 1, dim = c & 63
-      const int which = c >> 7, hh = (c >> 6) & 1, dim = c & 63;
-      const int gcol = which * d + hp * 128 + (c & 127);
-      const f32x4 bv = bias ? Vec4<T>::load(bias + gcol) : f32x4{0.f, 0.f, 0.f, 0.f};
-      bf16_t* ob = outs[which] + (int64_t)b * T_ * lds_[which] + hp * 128 + (c & 127);
-      char* tl = tiles + (which * 2 + hh) * 16384;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = wm + 16 * i + r;
-        const f32x4 v = acc[i][j] * 1.0f + bv;
-        bf16x4 w4 = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-        if (m >= T_) w4 = bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};  // rows of the next batch element / past the end
-        else *reinterpret_cast<bf16x4*>(ob + (int64_t)m * lds_[which]) = w4;
-        *reinterpret_cast<bf16x4*>(tl + tile_off<RB>(m, dim >> 3) + ((dim & 7) << 1)) = w4;
-      }
-    }
-    if (threadIdx.x < 128) {
-      const int j = threadIdx.x;
-      kmask_s[j] = (j < p.Tk) ? (p.key_mask ? p.key_mask[(int64_t)b * p.Tk + j] : (uint8_t)1) : (uint8_t)0;
-    }
-  }
-  const int q0 = wave * 16, i = q0 + r;
-  const uint8_t* qmp = p.query_mask ? p.query_mask + (int64_t)b * p.Tq + min(i, p.Tq - 1) : reinterpret_cast<const uint8_t*>(g.w);
-  const uint8_t qmv = *qmp;
-  const bool query_ok = (p.query_mask && i < p.Tq) ? (qmv != 0) : true;
-  __syncthreads();
-  if (q0 >= p.Tq) return;  // whole wave past the last query (no barrier follows)
-
-  // ---- phase C: attn_fwd_short_kernel's arithmetic for the two heads
-#pragma unroll 1
-  for (int hh = 0; hh < 2; ++hh) {
-    const int h = 2 * hp + hh;
-    const char* Qs = tiles + (0 * 2 + hh) * 16384;
-    const char* Ks = tiles + (1 * 2 + hh) * 16384;
-    const char* Vs = tiles + (2 * 2 + hh) * 16384;
-    frag_t qf[NS];
-#pragma unroll
-    for (int ks = 0; ks < NS; ++ks) qf[ks] = lds_frag_kcontig<T, RB>(Qs, q0, 4 * ks);
-    f32x4 s[8];
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int nt8 = 0; nt8 < 8; ++nt8) {
-      s[nt8] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < NS; ++ks) mma16(s[nt8], lds_frag_kcontig<T, RB>(Ks, 16 * nt8, 4 * ks), qf[ks]);
-      const uint32_t km4 = *reinterpret_cast<const uint32_t*>(kmask_s + 16 * nt8 + 4 * gq);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = 16 * nt8 + 4 * gq + e;
-        float v = s[nt8][e] * p.scale + (mask_ok<false>(p, b, i, j, ((km4 >> (8 * e)) & 0xffu) != 0, query_ok) ? 0.f : -10000.0f);
-        if (j >= p.Tk) v = -INFINITY;
-        s[nt8][e] = v;
-        tmax = fmaxf(tmax, v);
-      }
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    float psum = 0.f;
-#pragma unroll
-    for (int nt8 = 0; nt8 < 8; ++nt8)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float pv = __expf(s[nt8][e] - tmax);
-        psum += pv;
-        s[nt8][e] = pv;
-      }
-    if (p.drop_thresh) {
-      const uint32_t key = dropout_key(p.seed);
-      const uint32_t prow = (uint32_t)attn_pair_row(p, b, h, i) + (uint32_t)(2 * gq);
-#pragma unroll
-      for (int nt8 = 0; nt8 < 8; ++nt8)
-#pragma unroll
-        for (int e2 = 0; e2 < 2; ++e2) {
-          const uint32_t w = attn_drop_word(key, prow + 8 * nt8 + e2);
-          s[nt8][2 * e2] = (w & 0xffffu) >= p.drop_thresh ? s[nt8][2 * e2] * p.inv_keep : 0.f;
-          s[nt8][2 * e2 + 1] = (w >> 16) >= p.drop_thresh ? s[nt8][2 * e2 + 1] * p.inv_keep : 0.f;
-        }
-    }
-    psum += __shfl_xor(psum, 16, 64);
-    psum += __shfl_xor(psum, 32, 64);
-    f32x4 o[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const frag_t pf = acc_pair_to_frag(s[2 * u], s[2 * u + 1]);
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) mma16(o[dt], lds_frag_kperm_bf16<RB>(Vs, 32 * u, 16 * dt), pf);
-    }
-    const float inv_l = 1.0f / psum;
-    if (i < p.Tq) {
-      T* Ob = reinterpret_cast<T*>(p.O) + ((int64_t)b * p.Tq + i) * p.ldo + h * DH;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) Vec4<T>::store(Ob + 16 * dt + 4 * gq, o[dt] * inv_l);
-      if (gq == 0 && p.lse) p.lse[((int64_t)b * p.H + h) * p.Tq + i] = tmax + __logf(psum);
-    }
-  }
-}
-
 int check_args(const imt_attn_args* a, bool bwd, bool need_dO = true) {
   IMT_CHECK_ARG(a != nullptr, "attention: null args");
   IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "attention: bad dtype");
@@ -1276,63 +1081,106 @@ AttnP make_params(const imt_attn_args* a) {
   return p;
 }
 
-template <typename T, int DH> int fwd_launch(const AttnP& p, hipStream_t st) {
-  dim3 grid(imt_cdiv(p.Tq, 64) * p.H * p.B);
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * DH;
-  const double io = ((double)p.B * p.H * DH * sizeof(T)) * (2.0 * p.Tq + 2.0 * p.Tk);
-  ImtProfScope prof(sizeof(T) == 2 ? "attn_fwd_bf16" : "attn_fwd_f32", 4.0 * work, io, st);
-  if (p.mask3d) hipLaunchKernelGGL((attn_fwd_kernel<T, DH, true>), grid, dim3(256), 0, st, p);
-  else          hipLaunchKernelGGL((attn_fwd_kernel<T, DH, false>), grid, dim3(256), 0, st, p);
+// ------------------------------------------------------------------------------------------------ plan
+// The tuning switches, read once per entry-point call and not cached: the suite flips them inside one process.
+struct AttnSwitches { bool no_short_fwd, no_fused_bwd, no_fused256; };
+AttnSwitches read_switches() {
+  return {getenv("IMT_ATTN_NO_SHORT_FWD") != nullptr, getenv("IMT_ATTN_NO_FUSED_BWD") != nullptr, getenv("IMT_ATTN_NO_FUSED256") != nullptr};
+}
+
+enum FwdKernel { FWD_TILED, FWD_SHORT };
+enum BwdKernel { BWD_PAIR, BWD_FUSED, BWD_FUSED256 };
+constexpr int ONE_WG_T = 128, ONE_WG_T256 = 256;  // queries and keys one workgroup per (batch, head) holds: short / fused, fused-256
+
+// the one-workgroup kernels index dropout elements with 32 bits
+bool one_wg_fits(int B, int H, int Tq, int Tk, int limit) {
+  return Tq <= limit && Tk <= limit && (double)B * H * Tq * Tk < 4294967296.0;
+}
+// (head_dim and the mask kind pick the template instance of the planned kernel, not the kernel)
+FwdKernel plan_fwd(int dtype, int head_dim, int B, int H, int Tq, int Tk, bool has_mask3d, const AttnSwitches& sw) {
+  if (dtype == IMT_F32) return FWD_TILED;
+  return Tq > 64 && one_wg_fits(B, H, Tq, Tk, ONE_WG_T) && !sw.no_short_fwd ? FWD_SHORT : FWD_TILED;
+}
+BwdKernel plan_bwd(int dtype, int head_dim, int B, int H, int Tq, int Tk, bool has_mask3d, const AttnSwitches& sw) {
+  if (dtype == IMT_F32 || sw.no_fused_bwd) return BWD_PAIR;
+  if (one_wg_fits(B, H, Tq, Tk, ONE_WG_T)) return BWD_FUSED;
+  // 129 .. 256 keys / queries (MASS: encoder self-attention at 256 tokens, the decoder's cross-attention over them)
+  return one_wg_fits(B, H, Tq, Tk, ONE_WG_T256) && !sw.no_fused256 ? BWD_FUSED256 : BWD_PAIR;
+}
+
+// ------------------------------------------------------------------------------------------------ launch
+// Host dispatch on the head_dim (checked: 32 | 64) and on the presence of a 3-D mask: f(tag) with tag() a compile-time constant,
+// so that a launch names its template instance once (imt_by_dtype's counterparts; they nest).  The compiler emits the kernel
+// instances in the order in which launch_fwd / launch_bwd come to name them (fp32 before bf16, statements top to bottom, the outer
+// helper's cases before the inner one's); the nesting at each site keeps the code object's order, and so its bytes, as they were.
+template <typename F> int by_head_dim(int head_dim, F&& f) {
+  return head_dim == 32 ? f(std::integral_constant<int, 32>()) : f(std::integral_constant<int, 64>());
+}
+template <typename F> int by_mask3d(const AttnP& p, F&& f) { return p.mask3d ? f(std::true_type()) : f(std::false_type()); }
+// raises the dynamic-LDS limit of a kernel instance, once per instance
+template <auto KERNEL> void allow_lds(int bytes) {
+  static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)once;
+}
+template <typename K, typename... A> int launch(K kernel, int blocks, int threads, int lds, hipStream_t st, const A&... args) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, st, args...);
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }
-template <int DH, bool MASK3D> int bwd_fused_launch(const AttnP& p, hipStream_t st) {
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * DH;
-  const double io = ((double)p.B * p.H * DH * 2.0) * (4.0 * p.Tq + 4.0 * p.Tk);
-  const int lds = 2 * 128 * DH * 2 + 128 * 256 + 128 * 4 * 2 + 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<DH, MASK3D>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
+AttnP traced(AttnP p, const ImtTrace& tr) { p.trace = tr.dev; return p; }
+// for the profiler: the multiply-adds of one [Tq, Tk] x head_dim product; the bytes of rq operands of Tq rows and rk of Tk rows
+double attn_work(const AttnP& p, int dh) { return (double)p.B * p.H * p.Tq * p.Tk * dh; }
+double attn_io(const AttnP& p, int dh, size_t es, double rq, double rk) { return ((double)p.B * p.H * dh * es) * (rq * p.Tq + rk * p.Tk); }
+
+template <typename T> int launch_fwd(FwdKernel k, const AttnP& p, int head_dim, hipStream_t st) {
+  ImtProfScope prof(sizeof(T) == 2 ? "attn_fwd_bf16" : "attn_fwd_f32", 4.0 * attn_work(p, head_dim), attn_io(p, head_dim, sizeof(T), 2.0, 2.0), st);
+  if constexpr (sizeof(T) == 2) {  // (the one-workgroup kernels exist in bf16 only)
+    if (k == FWD_SHORT) {
+      ImtTrace tr("attn_fwd", p.B * p.H, st);
+      return by_head_dim(head_dim, [&](auto dh) {
+        return by_mask3d(p, [&](auto m3) { return launch(attn_fwd_short_kernel<dh(), m3()>, p.B * p.H, 512, 0, st, traced(p, tr)); });
+      });
+    }
   }
-  ImtProfScope prof("attn_bwd_fused_bf16", 10.0 * work, io, st);
-  ImtTrace tr("attn_bwd", p.B * p.H, st);
-  AttnP pt = p;
-  pt.trace = tr.dev;
-  hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, MASK3D>), dim3(p.B * p.H), dim3(512), lds, st, pt);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return by_head_dim(head_dim, [&](auto dh) {
+    return by_mask3d(p, [&](auto m3) { return launch(attn_fwd_kernel<T, dh(), m3()>, imt_cdiv(p.Tq, 64) * p.H * p.B, 256, 0, st, p); });
+  });
 }
-template <int DH, bool MASK3D> int bwd_fused256_launch(const AttnP& p, hipStream_t st) {
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * DH;
-  const double io = ((double)p.B * p.H * DH * 2.0) * (4.0 * p.Tq + 4.0 * p.Tk);
-  const int lds = 256 * DH * 2 + 2 * 64 * DH * 2 + 256 * 128 + 256 * 4 * 2 + 256;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused256_kernel<DH, MASK3D>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
+
+template <typename T> int launch_bwd(BwdKernel k, const AttnP& p, int head_dim, hipStream_t st) {
+  const double work = attn_work(p, head_dim);
+  if constexpr (sizeof(T) == 2) {  // (the one-workgroup kernels exist in bf16 only)
+    const double io = attn_io(p, head_dim, 2, 4.0, 4.0);
+    if (k == BWD_FUSED)
+      return by_mask3d(p, [&](auto m3) {
+        return by_head_dim(head_dim, [&](auto dh) {
+          constexpr auto kernel = attn_bwd_fused_kernel<dh(), m3()>;
+          allow_lds<kernel>(fused_lds_bytes(dh()));
+          ImtProfScope prof("attn_bwd_fused_bf16", 10.0 * work, io, st);
+          ImtTrace tr("attn_bwd", p.B * p.H, st);
+          return launch(kernel, p.B * p.H, 512, fused_lds_bytes(dh()), st, traced(p, tr));
+        });
+      });
+    if (k == BWD_FUSED256)
+      return by_mask3d(p, [&](auto m3) {
+        return by_head_dim(head_dim, [&](auto dh) {
+          constexpr auto kernel = attn_bwd_fused256_kernel<dh(), m3()>;
+          allow_lds<kernel>(fused256_lds_bytes(dh()));
+          ImtProfScope prof("attn_bwd_fused256_bf16", 10.0 * work, io, st);
+          return launch(kernel, p.B * p.H, 512, fused256_lds_bytes(dh()), st, p);
+        });
+      });
   }
-  ImtProfScope prof("attn_bwd_fused256_bf16", 10.0 * work, io, st);
-  hipLaunchKernelGGL((attn_bwd_fused256_kernel<DH, MASK3D>), dim3(p.B * p.H), dim3(512), lds, st, p);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
-}
-template <typename T, int DH> int bwd_launch(const AttnP& p, hipStream_t st) {
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * DH;
-  const double io = ((double)p.B * p.H * DH * sizeof(T)) * (2.0 * p.Tq + 2.0 * p.Tk);
-  {
-    ImtProfScope prof(sizeof(T) == 2 ? "attn_bwd_dq_bf16" : "attn_bwd_dq_f32", 6.0 * work, io * 1.5, st);
-    if (p.mask3d) hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DH, true>), dim3(imt_cdiv(p.Tq, 64) * p.H * p.B), dim3(256), 0, st, p);
-    else          hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DH, false>), dim3(imt_cdiv(p.Tq, 64) * p.H * p.B), dim3(256), 0, st, p);
-    IMT_CHECK_LAUNCH();
-  }
-  {
-    ImtProfScope prof(sizeof(T) == 2 ? "attn_bwd_dkdv_bf16" : "attn_bwd_dkdv_f32", 8.0 * work, io * 1.5, st);
-    if (p.mask3d) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, DH, true>), dim3(imt_cdiv(p.Tk, 64) * p.H * p.B), dim3(256), 0, st, p);
-    else          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, DH, false>), dim3(imt_cdiv(p.Tk, 64) * p.H * p.B), dim3(256), 0, st, p);
-    IMT_CHECK_LAUNCH();
-  }
-  return IMT_OK;
+  const double io = attn_io(p, head_dim, sizeof(T), 2.0, 2.0) * 1.5;
+  return by_head_dim(head_dim, [&](auto dh) {
+    {
+      ImtProfScope prof(sizeof(T) == 2 ? "attn_bwd_dq_bf16" : "attn_bwd_dq_f32", 6.0 * work, io, st);
+      const int rc = by_mask3d(p, [&](auto m3) { return launch(attn_bwd_dq_kernel<T, dh(), m3()>, imt_cdiv(p.Tq, 64) * p.H * p.B, 256, 0, st, p); });
+      if (rc) return rc;
+    }
+    ImtProfScope prof(sizeof(T) == 2 ? "attn_bwd_dkdv_bf16" : "attn_bwd_dkdv_f32", 8.0 * work, io, st);
+    return by_mask3d(p, [&](auto m3) { return launch(attn_bwd_dkdv_kernel<T, dh(), m3()>, imt_cdiv(p.Tk, 64) * p.H * p.B, 256, 0, st, p); });
+  });
 }
 
 }  // namespace
@@ -1341,118 +1189,51 @@ extern "C" int imt_attention_fwd(const imt_attn_args* a, void* stream) {
   int rc = check_args(a, false);
   if (rc) return rc;
   const AttnP p = make_params(a);
-  hipStream_t st = (hipStream_t)stream;
-  if (a->dtype == IMT_F32) return a->head_dim == 32 ? fwd_launch<float, 32>(p, st) : fwd_launch<float, 64>(p, st);
-  const bool idx32 = (double)a->B * a->H * a->Tq * a->Tk < 4294967296.0;  // 32-bit dropout element indices
-  if (a->Tq <= 128 && a->Tk <= 128 && a->Tq > 64 && idx32 && !getenv("IMT_ATTN_NO_SHORT_FWD")) {  // one workgroup per (batch, head)
-    const double work = (double)p.B * p.H * p.Tq * p.Tk * a->head_dim;
-    ImtProfScope prof("attn_fwd_bf16", 4.0 * work, ((double)p.B * p.H * a->head_dim * 2.0) * (2.0 * p.Tq + 2.0 * p.Tk), st);
-    ImtTrace tr("attn_fwd", p.B * p.H, st);
-    AttnP pt = p;
-    pt.trace = tr.dev;
-    if (a->head_dim == 32) {
-      if (p.mask3d) hipLaunchKernelGGL((attn_fwd_short_kernel<32, true>), dim3(p.B * p.H), dim3(512), 0, st, pt);
-      else          hipLaunchKernelGGL((attn_fwd_short_kernel<32, false>), dim3(p.B * p.H), dim3(512), 0, st, pt);
-    } else {
-      if (p.mask3d) hipLaunchKernelGGL((attn_fwd_short_kernel<64, true>), dim3(p.B * p.H), dim3(512), 0, st, pt);
-      else          hipLaunchKernelGGL((attn_fwd_short_kernel<64, false>), dim3(p.B * p.H), dim3(512), 0, st, pt);
-    }
-    IMT_CHECK_LAUNCH();
-    return IMT_OK;
-  }
-  return a->head_dim == 32 ? fwd_launch<bf16_t, 32>(p, st) : fwd_launch<bf16_t, 64>(p, st);
+  const FwdKernel k = plan_fwd(a->dtype, a->head_dim, a->B, a->H, a->Tq, a->Tk, a->mask3d != nullptr, read_switches());
+  return imt_by_dtype(a->dtype, [&](auto tag) { return launch_fwd<typename decltype(tag)::type>(k, p, a->head_dim, (hipStream_t)stream); });
 }
 
 extern "C" int imt_attention_bwd(const imt_attn_args* a, void* stream) {
   int rc = check_args(a, true);
   if (rc) return rc;
   const AttnP p = make_params(a);
-  hipStream_t st = (hipStream_t)stream;
-  if (a->dtype == IMT_F32) return a->head_dim == 32 ? bwd_launch<float, 32>(p, st) : bwd_launch<float, 64>(p, st);
-  const bool idx32 = (double)a->B * a->H * a->Tq * a->Tk < 4294967296.0;  // 32-bit dropout element indices
-  if (a->Tq <= 128 && a->Tk <= 128 && idx32 && !getenv("IMT_ATTN_NO_FUSED_BWD")) {  // short sequences: one fused kernel
-    if (p.mask3d) return a->head_dim == 32 ? bwd_fused_launch<32, true>(p, st) : bwd_fused_launch<64, true>(p, st);
-    return a->head_dim == 32 ? bwd_fused_launch<32, false>(p, st) : bwd_fused_launch<64, false>(p, st);
-  }
-  // 129 .. 256 keys / queries (MASS: encoder self-attention at 256 tokens, the decoder's cross-attention over them)
-  if (a->Tq <= 256 && a->Tk <= 256 && idx32 && !getenv("IMT_ATTN_NO_FUSED_BWD") && !getenv("IMT_ATTN_NO_FUSED256")) {
-    if (p.mask3d) return a->head_dim == 32 ? bwd_fused256_launch<32, true>(p, st) : bwd_fused256_launch<64, true>(p, st);
-    return a->head_dim == 32 ? bwd_fused256_launch<32, false>(p, st) : bwd_fused256_launch<64, false>(p, st);
-  }
-  return a->head_dim == 32 ? bwd_launch<bf16_t, 32>(p, st) : bwd_launch<bf16_t, 64>(p, st);
+  const BwdKernel k = plan_bwd(a->dtype, a->head_dim, a->B, a->H, a->Tq, a->Tk, a->mask3d != nullptr, read_switches());
+  return imt_by_dtype(a->dtype, [&](auto tag) { return launch_bwd<typename decltype(tag)::type>(k, p, a->head_dim, (hipStream_t)stream); });
 }
 
+// Where imt_attention_bwd_proj applies: where imt_attention_bwd runs the fused kernel (the instance this one is a variant of), at
+// head_dim 64 without a 3-D mask.  The shape query knows no batch size and plans for one batch element; the call plans for all.
+static bool bwd_proj_ok(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, bool has_mask3d, const AttnSwitches& sw) {
+  return dtype == IMT_BF16 && head_dim == 64 && H > 0 && H * 64 == d_model && Tq > 0 && Tk > 0 && !has_mask3d &&
+         plan_bwd(dtype, head_dim, 1, H, Tq, Tk, has_mask3d, sw) == BWD_FUSED;
+}
+extern "C" int imt_attention_bwd_proj_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d) {
+  return bwd_proj_ok(dtype, head_dim, H, Tq, Tk, d_model, has_mask3d != 0, read_switches());
+}
 // Attention backward with dO = dy W_o formed inside the launch (attn_bwd_proj_kernel) instead of by an NN product in front of
 // imt_attention_bwd.  a: the backward's arguments; a->dO may be NULL (dO is then never stored) or point at a [B*Tq, >= d_model]
 // buffer (lddo) that receives it.  dy [B*Tq, d_model] (lddy): the gradient of the projection's output; w_o [d_model, d_model]
 // row-major (ldw), the projection's weight.  dQ / dK / dV (and dO) are bit-identical to the pair's.
-extern "C" int imt_attention_bwd_proj_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d) {
-  const bool fused_off = getenv("IMT_ATTN_NO_FUSED_BWD") != nullptr;  // (the instance this one is a variant of is not in use)
-  return dtype == IMT_BF16 && head_dim == 64 && H > 0 && H * 64 == d_model && Tq > 0 && Tq <= 128 && Tk > 0 && Tk <= 128 &&
-         !has_mask3d && !fused_off;
-}
 extern "C" int imt_attention_bwd_proj(const imt_attn_args* a, const void* dy, int64_t lddy, const void* w_o, int64_t ldw, int d_model,
                                       void* stream) {
   int rc = check_args(a, true, false);
   if (rc) return rc;
-  IMT_CHECK_ARG(imt_attention_bwd_proj_supported(a->dtype, a->head_dim, a->H, a->Tq, a->Tk, d_model, a->mask3d != nullptr),
+  const AttnSwitches sw = read_switches();
+  IMT_CHECK_ARG(bwd_proj_ok(a->dtype, a->head_dim, a->H, a->Tq, a->Tk, d_model, a->mask3d != nullptr, sw),
                 "attention_bwd_proj: unsupported shape (bf16, head_dim 64, T <= 128, d_model = 64 H, no 3-D mask)");
   IMT_CHECK_ARG(dy && w_o && lddy >= d_model && ldw >= d_model && lddy % 8 == 0 && ldw % 8 == 0 &&
                 (((uintptr_t)dy | (uintptr_t)w_o) & 15) == 0, "attention_bwd_proj: dy / w_o missing, misaligned or narrower than d_model");
-  IMT_CHECK_ARG((double)a->B * a->H * a->Tq * a->Tk < 4294967296.0, "attention_bwd_proj: too many score elements for 32-bit dropout indices");
+  IMT_CHECK_ARG(plan_bwd(a->dtype, a->head_dim, a->B, a->H, a->Tq, a->Tk, false, sw) == BWD_FUSED,
+                "attention_bwd_proj: too many score elements for 32-bit dropout indices");
   const AttnP p = make_params(a);
   ProjP pj;
   pj.dy = dy; pj.lddy = lddy; pj.w = w_o; pj.ldw = ldw; pj.d_model = d_model;
   hipStream_t st = (hipStream_t)stream;
-  const int lds = 2 * 128 * 64 * 2 + 128 * 256 + 128 * 4 * 2 + 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_proj_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * 64.0;
+  allow_lds<attn_bwd_proj_kernel<false>>(fused_lds_bytes(64));
   // (profiled under the kind of the kernel it is an instance of, with the projection's flops and bytes added: the suite pins the
   // short backward's dispatch by that kind)
-  ImtProfScope prof("attn_bwd_fused_bf16", 10.0 * work + 2.0 * p.B * p.Tq * (double)d_model * d_model,
-                    ((double)p.B * p.H * 64 * 2.0) * (3.0 * p.Tq + 4.0 * p.Tk) + 2.0 * p.B * p.Tq * d_model + 2.0 * d_model * d_model, st);
+  ImtProfScope prof("attn_bwd_fused_bf16", 10.0 * attn_work(p, 64) + 2.0 * p.B * p.Tq * (double)d_model * d_model,
+                    attn_io(p, 64, 2, 3.0, 4.0) + 2.0 * p.B * p.Tq * d_model + 2.0 * d_model * d_model, st);
   ImtTrace tr("attn_bwd", p.B * p.H, st);
-  AttnP pt = p;
-  pt.trace = tr.dev;
-  hipLaunchKernelGGL((attn_bwd_proj_kernel<false>), dim3(p.B * p.H), dim3(512), lds, st, pt, pj);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
-}
-
-// q|k|v projection + self-attention forward in one launch (attn_qkv_fwd_kernel).  a: the attention arguments with Q / K / V
-// pointing at the OUTPUT views of the projection (element (b, t, h, e) as for imt_attention_fwd); x [B*T, d_model] (ldx), w
-// [3 d_model, d_model] row-major (q rows first, then k, then v: the runtime's fused projection weight), bias [3 d_model] or NULL.
-extern "C" int imt_attention_qkv_fwd_supported(int dtype, int head_dim, int H, int Tq, int Tk, int d_model, int has_mask3d) {
-  return dtype == IMT_BF16 && head_dim == 64 && H % 2 == 0 && H * head_dim == d_model && Tq == Tk && Tq > 64 && Tq <= 128 &&
-         d_model % 64 == 0 && d_model >= 128 && !has_mask3d;
-}
-extern "C" int imt_attention_qkv_fwd(const imt_attn_args* a, const void* x, int64_t ldx, const void* w, const void* bias, int d_model,
-                                     void* stream) {
-  int rc = check_args(a, false);
-  if (rc) return rc;
-  IMT_CHECK_ARG(x && w && ldx % 8 == 0 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0, "attention_qkv_fwd: x / w missing or misaligned");
-  IMT_CHECK_ARG(imt_attention_qkv_fwd_supported(a->dtype, a->head_dim, a->H, a->Tq, a->Tk, d_model, a->mask3d != nullptr),
-                "attention_qkv_fwd: unsupported shape (bf16, head_dim 64, even heads, 64 < T <= 128, self-attention, no 3-D mask)");
-  IMT_CHECK_ARG((double)a->B * a->H * a->Tq * a->Tk < 4294967296.0 && (int64_t)a->B * a->Tq * ldx * 2 < (1ll << 31) &&
-                (int64_t)3 * d_model * d_model * 2 < (1ll << 31), "attention_qkv_fwd: operand too large for 32-bit offsets");
-  const AttnP p = make_params(a);
-  QkvP g;
-  g.x = x; g.ldx = ldx; g.x_bytes = ((int64_t)(a->B * a->Tq - 1) * ldx + d_model) * 2; g.w = w; g.bias = bias; g.d_model = d_model;
-  hipStream_t st = (hipStream_t)stream;
-  const int lds = 2 * 65536;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_qkv_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  const double work = (double)p.B * p.H * p.Tq * p.Tk * a->head_dim;
-  ImtProfScope prof("attn_qkv_fwd_bf16", 4.0 * work + 2.0 * p.B * p.Tq * 3.0 * d_model * d_model,
-                    ((double)p.B * p.Tq * d_model * 2.0) * 5.0 + 6.0 * d_model * d_model, st);
-  hipLaunchKernelGGL((attn_qkv_fwd_kernel<false>), dim3(p.B * (p.H / 2)), dim3(512), lds, st, p, g);
-  IMT_CHECK_LAUNCH();
-  return IMT_OK;
+  return launch(attn_bwd_proj_kernel<false>, p.B * p.H, 512, fused_lds_bytes(64), st, traced(p, tr), pj);
 }

@@ -252,19 +252,26 @@ uint64_t site_seed(uint64_t base, int layer, int site) { return base + 0x9E3779B
 
 struct MaskSet { const uint8_t* key; const uint8_t* query; const uint8_t* m3d; int causal; };
 
-int attn_args(const Ctx& c, imt_attn_args& a, int B, int Tq, int Tk, const void* q, int64_t ldq, const void* k, int64_t ldk,
-              const void* v, int64_t ldv, void* o, float* lse, const MaskSet& ms, float drop_p, uint64_t seed) {
+inline const char* offp(const void* p, int64_t elems, int64_t es) { return reinterpret_cast<const char*>(p) + elems * es; }
+inline char* offp(void* p, int64_t elems, int64_t es) { return reinterpret_cast<char*>(p) + elems * es; }
+
+// what the forward and the backward of an attention block pass alike: self (cross == false): the strided q|k|v views of w.qkv;
+// cross: w.qkv against the key|value projections in w.kv.  The backward adds its gradient pointers.
+imt_attn_args attn_block_args(const Ctx& c, const AttnWs& w, bool cross, int B, int T, int Tk, const MaskSet& ms, float drop_p,
+                              uint64_t seed) {
+  const int d = c.m->d;
+  imt_attn_args a;
   memset(&a, 0, sizeof(a));
-  a.dtype = c.dtype; a.B = B; a.H = c.m->heads; a.Tq = Tq; a.Tk = Tk; a.head_dim = c.m->d / c.m->heads;
-  a.Q = q; a.ldq = ldq; a.K = k; a.ldk = ldk; a.V = v; a.ldv = ldv; a.O = o; a.ldo = c.m->d; a.lse = lse;
+  a.dtype = c.dtype; a.B = B; a.H = c.m->heads; a.Tq = T; a.Tk = cross ? Tk : T; a.head_dim = d / c.m->heads;
+  a.Q = w.qkv; a.ldq = cross ? d : 3 * d;
+  if (cross) { a.K = w.kv; a.ldk = w.kv_ld; a.V = offp(w.kv, d, c.es); a.ldv = w.kv_ld; }
+  else       { a.K = offp(w.qkv, d, c.es); a.ldk = 3 * d; a.V = offp(w.qkv, 2 * d, c.es); a.ldv = 3 * d; }
+  a.O = w.ctx; a.ldo = d; a.lse = w.lse;
   a.key_mask = ms.key; a.query_mask = ms.query; a.mask3d = ms.m3d; a.causal = ms.causal;
   a.scale = 1.0f / sqrtf((float)a.head_dim);
   a.dropout_p = drop_p; a.dropout_seed = seed;
-  return IMT_OK;
+  return a;
 }
-
-inline const char* offp(const void* p, int64_t elems, int64_t es) { return reinterpret_cast<const char*>(p) + elems * es; }
-inline char* offp(void* p, int64_t elems, int64_t es) { return reinterpret_cast<char*>(p) + elems * es; }
 
 // ------------------------------------------------------------------------------------------------ forward
 // attention block (BertAttention = BertSelfAttention + BertSelfOutput); kv_src == nullptr -> self attention
@@ -274,26 +281,15 @@ int attn_block_fwd(const Ctx& c, const imt_attn_block& p, AttnWs& w, const void*
   const int d = c.m->d;
   const int N = B * T;
   const float hp = training ? c.m->hidden_dropout : 0.f, ap = training ? c.m->attn_dropout : 0.f;
-  imt_attn_args a;
   if (!kv_src) {
-    attn_args(c, a, B, T, T, w.qkv, 3 * d, offp(w.qkv, d, c.es), 3 * d, offp(w.qkv, 2 * d, c.es), 3 * d, w.ctx, w.lse, ms, ap,
-              site_seed(seed, layer, site0));
-    // short self-attention in bf16: the q|k|v projection runs inside the attention launch (bit-identical to the pair)
-    static const bool qkv_fusion = getenv("IMT_ATTN_QKV_FUSION") && atoi(getenv("IMT_ATTN_QKV_FUSION")) != 0;  // measured neutral on C1: opt-in
-    if (qkv_fusion && p.qkv_b >= 0 && imt_attention_qkv_fwd_supported(c.dtype, a.head_dim, a.H, T, T, d, ms.m3d != nullptr) &&
-        (int64_t)B * T * d * c.es < (1ll << 31)) {
-      RC(imt_attention_qkv_fwd(&a, x, d, c.P(p.qkv_w), c.P(p.qkv_b), d, c.st));
-      RC(dense_resid_ln(c, w.ctx, d, N, d, p.o_w, p.o_b, d, x, p.ln_g, p.ln_b, w.pre_ln, w.out, w.mean, w.rstd, hp, site_seed(seed, layer, site0 + 1)));
-      return IMT_OK;
-    }
     RC(linear_fwd(c, x, d, N, d, p.qkv_w, p.qkv_b, 3 * d, w.qkv, 3 * d, nullptr, 0, nullptr, IMT_AUX_NONE, 0.f, 0));
   } else {
     const int Nk = B * Tk;
     RC(linear_fwd(c, x, d, N, d, p.qkv_w, p.qkv_b, d, w.qkv, d, nullptr, 0, nullptr, IMT_AUX_NONE, 0.f, 0));
     if (!kv_ready)  // (batched: the key|value projections of all layers were formed by one GEMM before the layer loop)
       RC(linear_fwd(c, kv_src, d, Nk, d, kv_w, kv_b, 2 * d, w.kv, w.kv_ld, nullptr, 0, nullptr, IMT_AUX_NONE, 0.f, 0));
-    attn_args(c, a, B, T, Tk, w.qkv, d, w.kv, w.kv_ld, offp(w.kv, d, c.es), w.kv_ld, w.ctx, w.lse, ms, ap, site_seed(seed, layer, site0));
   }
+  const imt_attn_args a = attn_block_args(c, w, kv_src != nullptr, B, T, Tk, ms, ap, site_seed(seed, layer, site0));
   RC(imt_attention_fwd(&a, c.st));
   RC(dense_resid_ln(c, w.ctx, d, N, d, p.o_w, p.o_b, d, x, p.ln_g, p.ln_b, w.pre_ln, w.out, w.mean, w.rstd, hp, site_seed(seed, layer, site0 + 1)));
   return IMT_OK;
@@ -314,35 +310,25 @@ int attn_block_bwd(const Ctx& c, const imt_attn_block& p, AttnWs& w, StackWs& sw
   dw.add(c, d_dense, d, w.ctx, d, N, d, d, p.o_w, p.o_b);
   // short attention in bf16: d_ctx = d_dense W_o is formed inside the attention backward (bit-identical to the pair), and
   // sw.d_ctx is neither written nor read
-  static const bool do_fusion = !(getenv("IMT_ATTN_DO_FUSION") && atoi(getenv("IMT_ATTN_DO_FUSION")) == 0);
-  const bool proj = do_fusion && imt_attention_bwd_proj_supported(c.dtype, d / c.m->heads, c.m->heads, T, kv_src ? Tk : T, d, ms.m3d != nullptr);
+  imt_attn_args a = attn_block_args(c, w, kv_src != nullptr, B, T, Tk, ms, ap, site_seed(seed, layer, site0));
+  const bool proj = imt_attention_bwd_proj_supported(a.dtype, a.head_dim, a.H, a.Tq, a.Tk, d, ms.m3d != nullptr);
   if (!proj) RC(linear_bwd_input(c, d_dense, d, N, d, p.o_w, d, sw.d_ctx, d, nullptr, 0, nullptr, IMT_AUX_NONE, 0));
-  auto attn_bwd = [&](imt_attn_args& a) {
-    if (!proj) return imt_attention_bwd(&a, c.st);
-    a.dO = nullptr;
-    return imt_attention_bwd_proj(&a, d_dense, d, c.P(p.o_w), d, d, c.st);
-  };
-  imt_attn_args a;
+  a.dO = proj ? nullptr : sw.d_ctx; a.lddo = d;
+  a.delta = sw.delta;
+  auto attn_bwd = [&]() { return proj ? imt_attention_bwd_proj(&a, d_dense, d, c.P(p.o_w), d, d, c.st) : imt_attention_bwd(&a, c.st); };
   if (!kv_src) {
-    attn_args(c, a, B, T, T, w.qkv, 3 * d, offp(w.qkv, d, c.es), 3 * d, offp(w.qkv, 2 * d, c.es), 3 * d, w.ctx, w.lse, ms, ap,
-              site_seed(seed, layer, site0));
-    a.dO = sw.d_ctx; a.lddo = d;
     a.dQ = sw.d_qkv; a.lddq = 3 * d; a.dK = offp(sw.d_qkv, d, c.es); a.lddk = 3 * d; a.dV = offp(sw.d_qkv, 2 * d, c.es); a.lddv = 3 * d;
-    a.delta = sw.delta;
-    RC(attn_bwd(a));
+    RC(attn_bwd());
     dw.add(c, sw.d_qkv, 3 * d, x, d, N, 3 * d, d, p.qkv_w, p.qkv_b);
     RC(linear_bwd_input(c, sw.d_qkv, 3 * d, N, 3 * d, p.qkv_w, d, sw.d_run, d, d_pre, d, nullptr, IMT_AUX_NONE, 0));
   } else {
     const int Nk = B * Tk;
-    attn_args(c, a, B, T, Tk, w.qkv, d, w.kv, w.kv_ld, offp(w.kv, d, c.es), w.kv_ld, w.ctx, w.lse, ms, ap, site_seed(seed, layer, site0));
-    a.dO = sw.d_ctx; a.lddo = d;
     // batched key|value projections: dK|dV of this layer go to its column block of d_kv_all; d(encoder states) and the
     // weight gradients of all layers are formed after the layer loop (imt_stack_backward)
     void* dkv = d_kv_batched ? d_kv_batched : sw.d_kv;
     const int64_t lddkv = d_kv_batched ? w.kv_ld : 2 * d;
     a.dQ = sw.d_q; a.lddq = d; a.dK = dkv; a.lddk = lddkv; a.dV = offp(dkv, d, c.es); a.lddv = lddkv;
-    a.delta = sw.delta;
-    RC(attn_bwd(a));
+    RC(attn_bwd());
     dw.add(c, sw.d_q, d, x, d, N, d, d, p.qkv_w, p.qkv_b);
     RC(linear_bwd_input(c, sw.d_q, d, N, d, p.qkv_w, d, sw.d_run, d, d_pre, d, nullptr, IMT_AUX_NONE, 0));
     // the key|value weight gradient stays in this layer's grouped launch either way (its 32 tiles fill CUs the other six

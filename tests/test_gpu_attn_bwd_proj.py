@@ -98,6 +98,14 @@ def test_bwd_proj_supported_shapes():
     assert sup(L.IMT_BF16, 64, 8, 128, 129, 512, 0) == 0
     assert sup(L.IMT_BF16, 64, 8, 128, 128, 576, 0) == 0  # d_model != 64 H
     assert sup(L.IMT_BF16, 64, 8, 128, 128, 512, 1) == 0  # explicit [B, Tq, Tk] mask: the pair
+    # the fused backward switched off: the instance this one is a variant of is not in use
+    import os
+    os.environ["IMT_ATTN_NO_FUSED_BWD"] = "1"
+    try:
+        assert sup(L.IMT_BF16, 64, 8, 128, 128, 512, 0) == 0
+    finally:
+        os.environ.pop("IMT_ATTN_NO_FUSED_BWD", None)
+    assert sup(L.IMT_BF16, 64, 8, 128, 128, 512, 0) == 1
 
 
 @pytest.mark.gpu
