@@ -17,7 +17,8 @@ from .option_parser import get_img_options_parser
 from .seq2seq import Seq2Seq
 from .seq_gen import BeamDecoder, get_outputs_until_eos
 from .textprocessor import TextProcessor
-from .train_image_mt import ImageMTTrainer, LossMeter, init_distributed, load_lex_dict, reject_off_path, use_lex_dict
+from .train_image_mt import ImageMTTrainer
+from .trainer import Trainer, batches_from, init_distributed, load_lex_dict, reject_off_path, use_lex_dict
 from .utils import build_optimizer
 
 
@@ -47,19 +48,11 @@ class ImageCaptionTrainer(ImageMTTrainer):
         self._finish_micro_step(accum)
         return loss.detach(), int(ntokens)
 
-    @torch.no_grad()
     def caption_dev_loss(self, img_dev_data):
-        self.model.eval()
-        tp = self.model.text_processor
-        total, count = 0.0, 0
-        for i in range(len(img_dev_data)):
-            batch = img_dev_data[i]
-            loss, n = self.model.loss_fused(tgt_inputs=batch["captions"], tgt_mask=batch["caption_mask"], pad_idx=tp.pad_token_id(),
-                                            tgt_langs=batch["langs"], batch=batch, proposals=self._proposals(batch))
-            total += float(loss) * int(n)
-            count += int(n)
-        self.model.train()
-        return total / max(count, 1)
+        pad = self.model.text_processor.pad_token_id()
+        return self._mean_dev_loss(img_dev_data, lambda batch: self.model.loss_fused(
+            tgt_inputs=batch["captions"], tgt_mask=batch["caption_mask"], pad_idx=pad, tgt_langs=batch["langs"], batch=batch,
+            proposals=self._proposals(batch)))
 
     @torch.no_grad()
     def eval_captions(self, img_test_data, max_batches: int = None):
@@ -81,41 +74,21 @@ class ImageCaptionTrainer(ImageMTTrainer):
     def train_epoch(self, img_data=None, mt_data=None, img_dev_data=None, mt_dev_data=None, step: int = 0,
                     max_step: int = 300000, save_path: str = None, accum: int = 1, mtl_weight: float = 0.1,
                     log_every: int = 50, eval_every: int = 5000, **kwargs):
-        order = [("img", i) for i in range(len(img_data) if img_data is not None else 0)]
-        order += [("mt", i) for i in range(len(mt_data or []))]
-        random.Random(self.seed + self.epoch).shuffle(order)
-        if self.world_size > 1 and order:
-            order = order + order[:(-len(order)) % self.world_size]
-        order = order[self.rank::self.world_size]
-        self.epoch += 1
-        meter, t0 = LossMeter(), datetime.datetime.now()
-        for kind, i in order:
-            if step >= max_step:
-                break
-            try:
-                if kind == "img":
-                    loss, n = self.caption_step(img_data[i], accum)
-                else:  # MT data as the second task (:59-75), weighted by mtl_weight (:83)
-                    loss, n = self.mt_step(mt_data[i], accum, loss_weight=mtl_weight)
-            except RuntimeError as err:
-                if self.world_size > 1:
-                    raise
-                print("skipping batch:", repr(err))
-                self.optimizer.zero_grad()
-                continue
-            if n == 0 and self.world_size == 1:
-                continue
-            step += 1  # (an empty batch of a multi-rank job counts: the other ranks counted theirs)
-            meter.add(loss, n)
-            if step % log_every == 0:
-                mean, tokens = meter.read()
-                if self.rank == 0:
-                    secs = (datetime.datetime.now() - t0).total_seconds()
-                    print(datetime.datetime.now(), "Epoch Step: %d Loss: %f Tokens per Sec: %f " % (step, mean, tokens / max(secs, 1e-9)), flush=True)
-                t0 = datetime.datetime.now()
+        order = Trainer.epoch_order(self, [("img", len(img_data) if img_data is not None else 0), ("mt", len(mt_data or []))])
+
+        def step_fn(kind, i, step):
+            if kind == "img":
+                return self.caption_step(img_data[i], accum)
+            return self.mt_step(mt_data[i], accum, loss_weight=mtl_weight)  # MT data as the second task (:59-75), weighted (:83)
+
+        def after_step(step):  # (without a dev set too: the latest weights are saved)
             if step % eval_every == 0:
                 self._validate(img_dev_data, mt_dev_data, save_path)
-        return step
+
+        return self.run_epoch(order, step_fn, step=step, max_step=max_step, log_every=log_every, after_step=after_step,
+                              skip_empty=True)  # a caption batch without a target token (caption_step) is no step of one process
+
+    log_line = Trainer.log_line  # the reference's "Epoch Step: ..." line, not ImageMTTrainer's
 
     def _validate(self, img_dev_data, mt_dev_data, save_path):
         score = None
@@ -177,12 +150,10 @@ class ImageCaptionTrainer(ImageMTTrainer):
                                        lex_dict=lex_dict)
         img_train = mk_img(dataset.ImageCaptionDataset, options.train_path)
         img_dev = mk_img(dataset.ImageCaptionDataset, options.dev_path) if options.dev_path else None
-        pad = tp.pad_token_id()
-        mk_mt = lambda path: dataset.MTDataset(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad,
-                                               max_seq_len=options.max_seq_len, batch_pickle_dir=path,
-                                               lex_dict=lex_dict).batches
-        mt_train = sum((mk_mt(p.strip()) for p in (options.mt_train_path or "").split(",") if p.strip()), []) or None
-        mt_dev = sum((mk_mt(p.strip()) for p in (options.mt_dev_path or "").split(",") if p.strip()), []) or None
+        mt_kw = dict(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=tp.pad_token_id(),
+                     max_seq_len=options.max_seq_len, lex_dict=lex_dict)
+        mt_train = batches_from(options.mt_train_path, **mt_kw) or None
+        mt_dev = batches_from(options.mt_dev_path, **mt_kw) or None
         if rank == 0:
             print("image batches", len(img_train), "MT batches", len(mt_train or []), flush=True)
         step, epoch = 0, 1

@@ -8,7 +8,6 @@ image-caption batches (``:202-237``): per batch ``--mmode`` picks the masked-cap
 contrastive step; back-translation over image batches is not built and refused.  What the reference trainer does around the step that needs
 absent packages (apex, sacrebleu, the torchvision image pipeline) is left out; the model step itself is the HIP path."""
 import datetime
-import math
 import os
 import random
 import torch
@@ -18,26 +17,19 @@ from torch.nn.utils.rnn import pad_sequence
 from . import dataset
 from .image_model import ImageMassSeq2Seq
 from .option_parser import get_img_options_parser
-from .parallel import GradSync, finish_micro_step, train_step
+from .parallel import train_step
 from .textprocessor import TextProcessor
+from .trainer import LossMeter, Trainer, batches_from, init_distributed, load_lex_dict, reject_off_path, use_lex_dict  # noqa: F401
 from .utils import build_optimizer, mass_mask_device
 
 
-class ImageMTTrainer:
+class ImageMTTrainer(Trainer):
     def __init__(self, model, mask_prob: float = 0.3, clip: float = 1.0, optimizer=None, rank: int = 0, world_size: int = 1,
                  seed: int = 1234, **kwargs):
-        self.model = model
-        self.clip = clip
-        self.optimizer = optimizer
+        super().__init__(model, optimizer, clip, rank, world_size, seed)
         self.mask_prob = mask_prob
-        self.rank, self.world_size = rank, world_size
-        self.sync = GradSync(model) if world_size > 1 else None
-        self.best_loss = float("inf")
-        self.seed = seed
-        self.epoch = 0
-        self.micro_step = 0  # backward passes so far: the optimizer steps when this reaches a multiple of `accum`
         # MASS span / replacement draws: a generator of this rank's own, so that the ranks' batch ORDER (drawn from a
-        # generator every rank seeds identically, below) never depends on how many MASS batches a rank has seen
+        # generator every rank seeds identically, Trainer.epoch_order) never depends on how many MASS batches a rank has seen
         self._mass_rng = random.Random((seed + 1) * 7919 + rank)
         # image batches (--mmode): the mixed mode's coin and the masked step's mask_prob ~ U(mask_prob, 1) come from a
         # generator of their own, so that the MASS draws above do not depend on how many image batches a rank has seen
@@ -50,15 +42,6 @@ class ImageMTTrainer:
         self.lex_dict = kwargs.get("lex_dict")  # --dict: the back-translation phase looks up proposals for what it generates
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
-
-    def _proposals(self, batch):
-        """batch["proposal"] ([B, Pmax], built by the datasets from --dict) when the model attends over proposals."""
-        return batch.get("proposal") if getattr(self.model, "use_proposals", False) else None
-
-    def _finish_micro_step(self, accum: int):
-        """clip after EVERY backward, step every `accum` (src/train_image_mt.py:291-295)."""
-        self.micro_step += 1
-        finish_micro_step(self.model, self.optimizer, self.sync, self.clip, update=self.micro_step % max(1, accum) == 0)
 
     # one MT batch (src/train_image_mt.py:239-295)
     def mt_step(self, batch, accum: int = 1, loss_weight: float = 1.0):
@@ -161,29 +144,25 @@ class ImageMTTrainer:
         return loss.detach(), int(ntokens)
 
     @torch.no_grad()
-    def dev_loss(self, dev_data):
+    def _mean_dev_loss(self, data, loss_of):
+        """Token-weighted mean of ``loss_of(batch)`` = (loss, ntokens) over data[0..len), in eval mode."""
         self.model.eval()
         total, count = 0.0, 0
-        for batch in dev_data:
-            loss, n = self.model.loss_fused(src_inputs=batch["src_texts"], tgt_inputs=batch["dst_texts"],
-                                            src_langs=batch["src_langs"], tgt_langs=batch["dst_langs"],
-                                            proposals=self._proposals(batch))
+        for i in range(len(data)):
+            loss, n = loss_of(data[i])
             total += float(loss) * int(n)
             count += int(n)
         self.model.train()
         return total / max(count, 1)
 
+    def dev_loss(self, dev_data):
+        return self._mean_dev_loss(dev_data, lambda batch: self.model.loss_fused(
+            src_inputs=batch["src_texts"], tgt_inputs=batch["dst_texts"], src_langs=batch["src_langs"],
+            tgt_langs=batch["dst_langs"], proposals=self._proposals(batch)))
+
     def epoch_order(self, n_mt: int, n_mass: int, n_img: int = 0):
-        """This rank's share of the epoch's batches: the same shuffle on every rank (a generator seeded with seed + epoch,
-        nothing else draws from it), padded by wrapping around to a multiple of the world size like torch's
-        DistributedSampler (src/train_image_mt.py:586-589), then strided -- every rank runs the SAME number of steps, so
-        no rank is left waiting in an all-reduce when an epoch ends."""
-        order = [("mt", i) for i in range(n_mt)] + [("mass", i) for i in range(n_mass)] + [("img", i) for i in range(n_img)]
-        random.Random(self.seed + self.epoch).shuffle(order)
-        if self.world_size > 1 and order:
-            short = (-len(order)) % self.world_size
-            order = order + order[:short]
-        return order[self.rank::self.world_size]
+        """``Trainer.epoch_order`` over this trainer's kinds, concatenated in the order mt, mass, img."""
+        return super().epoch_order([("mt", n_mt), ("mass", n_mass), ("img", n_img)])
 
     def train_epoch(self, mt_data=None, mass_data=None, dev_data=None, step: int = 0, max_step: int = 10 ** 9,
                     save_path: str = None, log_every: int = 50, eval_every: int = 500, accum: int = 1, fine_tune: bool = False,
@@ -192,38 +171,24 @@ class ImageMTTrainer:
             raise NotImplementedError("back-translation over image batches (src/train_image_mt.py:108-198 with is_img_batch) "
                                       "is not built")
         order = self.epoch_order(len(mt_data or []), len(mass_data or []), len(img_data) if img_data is not None else 0)
-        self.epoch += 1
-        meter, t0 = LossMeter(), datetime.datetime.now()
-        for kind, i in order:
-            if step >= max_step:
-                break
-            try:
-                if kind == "mt":
-                    loss, n = self.mt_step(mt_data[i], accum)
-                elif kind == "img":
-                    loss, n = self.image_step(img_data[i], accum)
-                elif fine_tune:  # back-translation phase: the monolingual batches are translated and trained on (:108-198)
-                    loss, n = self.bt_step(mass_data[i], lang_directions, accum)
-                else:
-                    loss, n = self.mass_step(mass_data[i], accum)
-            except RuntimeError as err:  # the reference trainer skips a failing batch and goes on (:327-333)
-                if self.world_size > 1:
-                    raise  # the other ranks are inside this step's collectives: skipping here would leave them hanging
-                print("skipping batch:", repr(err))
-                self.optimizer.zero_grad()
-                continue
-            step += 1
-            meter.add(loss, n)
-            if step % log_every == 0:
-                mean, tokens = meter.read()  # the only host read of the losses: once per log_every steps, on every rank
-                if self.rank == 0:
-                    secs = (datetime.datetime.now() - t0).total_seconds()
-                    print(datetime.datetime.now(), "step", step, "loss %.4f" % mean, "tokens/s %.0f" % (tokens / max(secs, 1e-9)),
-                          "lr %.2e" % self.optimizer.param_groups[0]["lr"], flush=True)
-                t0 = datetime.datetime.now()
+
+        def step_fn(kind, i, step):  # (the contrastive image step reports 0 tokens and still counts as a step)
+            if kind == "mt":
+                return self.mt_step(mt_data[i], accum)
+            if kind == "img":
+                return self.image_step(img_data[i], accum)
+            if fine_tune:  # back-translation phase: the monolingual batches are translated and trained on (:108-198)
+                return self.bt_step(mass_data[i], lang_directions, accum)
+            return self.mass_step(mass_data[i], accum)
+
+        def after_step(step):
             if dev_data is not None and step % eval_every == 0:
                 self.validate_and_save(dev_data, save_path)
-        return step
+
+        return self.run_epoch(order, step_fn, step=step, max_step=max_step, log_every=log_every, after_step=after_step)
+
+    def log_line(self, step, mean, count, secs):
+        return "step %d loss %.4f tokens/s %.0f lr %.2e" % (step, mean, count / max(secs, 1e-9), self.optimizer.param_groups[0]["lr"])
 
     def validate_and_save(self, dev_data, save_path):
         dl = self.dev_loss(dev_data)
@@ -235,71 +200,10 @@ class ImageMTTrainer:
         return dl
 
 
-class LossMeter:
-    """Token-weighted running mean of per-step losses that stay on the device until ``read()`` (the reference reads
-    ``loss.item()`` every step, src/train_image_mt.py:284: a host stall per step that lets the GPU idle while the host
-    prepares the next batch)."""
-
-    def __init__(self):
-        self.items = []
-
-    def add(self, loss, n: int):
-        if n:
-            self.items.append((loss, int(n)))
-
-    def read(self):
-        tokens = sum(n for _, n in self.items)
-        total = sum(float(l) * n for l, n in self.items)
-        self.items = []
-        return total / max(tokens, 1), tokens
-
-
 def get_option_parser():
     """The reference's flags (src/option_parser.py:37-88: --train_mt, --dev_mt, --mass_train, --acc, --fp16, --beam ...)
     plus the build's additions (option_parser.py)."""
     return get_img_options_parser()
-
-
-def init_distributed():
-    """One process per GPU (src/utils.py:93-97, src/train_image_mt.py:72-76); backend "nccl" is RCCL on ROCm."""
-    rank, world = 0, 1
-    if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        import torch.distributed as dist
-        local = int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if not dist.is_initialized():
-            dist.init_process_group("nccl")
-        rank, world = dist.get_rank(), dist.get_world_size()
-    return rank, world
-
-
-def reject_off_path(options, lm_supported: bool = False, dict_supported: bool = False):
-    """Flags whose feature is not built are refused, never silently ignored: a requested pretrained initialisation or a
-    resumed optimizer that quietly trains from scratch is worse than an error.  ``dict_supported``: the entry point builds a
-    model that attends over lexical proposals and feeds it from the dictionary (train_image_mt, train_captioning)."""
-    for flag, val in (("--dict", None if dict_supported else options.dict_path),):
-        if val:
-            raise NotImplementedError("%s: this entry point does not train with lexical proposals (train_image_mt and "
-                                      "train_captioning do, DESIGN section 6)" % flag)
-    for flag, val in (("--lm", None if lm_supported else options.lm_path), ("--cont", options.continue_train), ("--save-opt", options.save_opt)):
-        if val:
-            raise NotImplementedError("%s: not implemented by this trainer (masked-LM initialisation / pickled-optimizer resume, "
-                                      "src/train_image_mt.py:319-321,449-462); use --pretrained to continue from saved weights" % flag)
-
-
-def load_lex_dict(options):
-    """--dict FILE (src/train_image_mt.py:430-432): {source word id: [proposed ids]}, or None without the flag."""
-    return dataset.get_lex_dict(options.dict_path) if getattr(options, "dict_path", None) else None
-
-
-def use_lex_dict(model, lex_dict, what: str):
-    """The dictionary the data is built with: ``lex_dict`` for a model that attends over proposals, None otherwise.  A
-    checkpoint and a --dict flag that disagree are an error, not a silent choice."""
-    if bool(getattr(model, "use_proposals", False)) != (lex_dict is not None):
-        raise ValueError("%s: the model was %s lexical proposals but --dict is %s" % (
-            what, "built with" if model.use_proposals else "built without", "given" if lex_dict is not None else "missing"))
-    return lex_dict
 
 
 def load_image_data(options, tp, lex_dict=None):
@@ -352,18 +256,11 @@ def train(options):
                              max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio, mm_mode=options.mm_mode,
                              lex_dict=lex_dict)
     pad = tp.pad_token_id()
-    mk = lambda cls, path, **kw: cls(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad,
-                                     max_seq_len=options.max_seq_len, ngpu=1, lex_dict=lex_dict, **kw, **path)
-    mt_train, mass_train, mt_dev = [], [], None
-    for pth in (options.mt_train_path or "").split(","):
-        if pth.strip():
-            mt_train += mk(dataset.MTDataset, dict(batch_pickle_dir=pth.strip())).batches
-    for pth in (options.mass_train_path or "").split(","):
-        if pth.strip():
-            mass_train += mk(dataset.MassDataset, dict(batch_pickle_dir=pth.strip())).batches
-    for pth in (options.mt_dev_path or "").split(","):
-        if pth.strip():
-            mt_dev = (mt_dev or []) + mk(dataset.MTDataset, dict(batch_pickle_dir=pth.strip())).batches
+    kw = dict(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad, max_seq_len=options.max_seq_len,
+              ngpu=1, lex_dict=lex_dict)
+    mt_train = batches_from(options.mt_train_path, **kw)
+    mass_train = batches_from(options.mass_train_path, dataset.MassDataset, **kw)
+    mt_dev = batches_from(options.mt_dev_path, **kw) or None
     if rank == 0:
         print("MT batches", len(mt_train), "MASS batches", len(mass_train), "image batches", len(img_train or []),
               "dev batches", len(mt_dev or []), flush=True)

@@ -5,7 +5,6 @@ embedding from the caption: L2 distance over the batch divided by the number of 
 (``Caption2Image.loss_fused``: encoder stack, fused dropout + pooling, linear layer, ``imt_l2_dist``), then the clip + Adam
 step of the other trainers.  Checkpoints (``<model>.latest``) hold weights only: no pickled optimizer (``--save-opt`` is
 refused).  One process, one GPU."""
-import datetime
 import os
 import random
 
@@ -16,11 +15,13 @@ from .image_model import Caption2Image, ImageCaptioning
 from .option_parser import get_img_options_parser
 from .seq2seq import Seq2Seq
 from .textprocessor import TextProcessor
-from .train_image_mt import ImageMTTrainer, LossMeter, reject_off_path
+from .trainer import Trainer, reject_off_path
 from .utils import build_optimizer
 
 
-class Caption2ImageTrainer(ImageMTTrainer):
+class Caption2ImageTrainer(Trainer):
+    unit = "Image"
+
     def __init__(self, model, caption_model, **kw):
         super().__init__(model, **kw)
         if self.world_size > 1:
@@ -55,33 +56,18 @@ class Caption2ImageTrainer(ImageMTTrainer):
 
     def train_epoch(self, img_data, img_dev_data=None, step: int = 0, max_step: int = 300000, save_path: str = None,
                     accum: int = 1, log_every: int = 50, save_every: int = 10000, eval_every: int = 5000, **kwargs):
-        order = list(range(len(img_data)))
-        random.Random(self.seed + self.epoch).shuffle(order)
-        self.epoch += 1
-        # the reference logs sum(loss) / sum(images) (:70-85): the meter weighs by n, so it is fed loss / n
-        meter, t0 = LossMeter(), datetime.datetime.now()
-        for i in order:
-            if step >= max_step:
-                break
-            try:
-                loss, n = self.txt2image_step(img_data[i], accum)
-            except RuntimeError as err:
-                print("skipping batch:", repr(err))
-                self.optimizer.zero_grad()
-                continue
-            step += 1
-            meter.add(loss / n, n)
-            if step % log_every == 0:
-                mean, images = meter.read()  # the only host read of the losses
-                secs = (datetime.datetime.now() - t0).total_seconds()
-                print(datetime.datetime.now(), "Epoch Step: %d Loss: %f Image per Sec: %f " % (step, mean, images / max(secs, 1e-9)),
-                      flush=True)
-                t0 = datetime.datetime.now()
+        def step_fn(kind, i, step):
+            loss, n = self.txt2image_step(img_data[i], accum)
+            return loss / n, n  # the reference logs sum(loss) / sum(images) (:70-85): the meter weighs by n, so it is fed loss / n
+
+        def after_step(step):
             if save_path and step % save_every == 0:
                 self.model.save(save_path + ".latest")
             if img_dev_data is not None and step % eval_every == 0:
                 print("Dev Loss:", self.dev_loss(img_dev_data), flush=True)
-        return step
+
+        return self.run_epoch(self.epoch_order([("img", len(img_data))]), step_fn, step=step, max_step=max_step,
+                              log_every=log_every, after_step=after_step)
 
     @staticmethod
     def train(options):

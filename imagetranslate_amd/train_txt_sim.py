@@ -4,7 +4,6 @@
 ``imt_sensim_loss``), then the clip + Adam step of the other trainers.  The dev loss (``--dev_mt``) is the one-sided loss without
 negatives; its best value saves to ``--model``, the latest weights go to ``<model>.latest``.  Checkpoints hold weights only: no
 pickled optimizer (``--save-opt`` is refused).  One process, one GPU."""
-import datetime
 import os
 import random
 
@@ -16,7 +15,7 @@ from .option_parser import get_img_options_parser
 from .sen_sim import SenSim
 from .seq2seq import Seq2Seq
 from .textprocessor import TextProcessor
-from .train_image_mt import ImageMTTrainer, LossMeter, reject_off_path
+from .trainer import Trainer, batches_from, reject_off_path
 from .utils import build_optimizer
 
 NEG_FACTOR = 5  # the negatives' batch and capacity are five times the pairs' (src/train_txt_sim.py:181-182)
@@ -29,7 +28,9 @@ def draw_negative(seed: int, step: int, side: int, n_batches: int) -> int:
     return random.Random((int(seed) * 1000003 + int(step)) * 2 + int(side)).randrange(n_batches)
 
 
-class SenSimTrainer(ImageMTTrainer):
+class SenSimTrainer(Trainer):
+    unit = "Sentences"
+
     def __init__(self, model, **kw):
         if int(kw.get("world_size", 1)) > 1:
             raise NotImplementedError("SenSim trains in one process on one GPU")
@@ -71,32 +72,18 @@ class SenSimTrainer(ImageMTTrainer):
 
     def train_epoch(self, mt_data, src_neg, dst_neg, dev_data=None, step: int = 0, max_step: int = 300000, save_path: str = None,
                     accum: int = 1, log_every: int = 50, save_every: int = 500, eval_every: int = 5000, **kwargs):
-        order = list(range(len(mt_data)))
-        random.Random(self.seed + self.epoch).shuffle(order)
-        self.epoch += 1
-        meter, t0 = LossMeter(), datetime.datetime.now()
-        for i in order:
-            if step >= max_step:
-                break
-            try:
-                loss, n = self.sim_step(mt_data[i], src_neg, dst_neg, step, accum)
-            except RuntimeError as err:  # the reference trainer skips a failing batch and goes on (:99-101)
-                print("skipping batch:", repr(err))
-                self.optimizer.zero_grad()
-                continue
-            step += 1
-            meter.add(loss, n)  # the loss is already per sentence (divided by B): the meter weighs it by n (:71-75)
-            if step % log_every == 0:
-                mean, sens = meter.read()  # the only host read of the losses
-                secs = (datetime.datetime.now() - t0).total_seconds()
-                print(datetime.datetime.now(), "Epoch Step: %d Loss: %f Sentences per Sec: %f " % (step, mean, sens / max(secs, 1e-9)),
-                      flush=True)
-                t0 = datetime.datetime.now()
+        def step_fn(kind, i, step):  # `step` is the count before this batch: the negatives are drawn from it
+            # the loss is already per sentence (divided by B): the meter weighs it by n (:71-75)
+            return self.sim_step(mt_data[i], src_neg, dst_neg, step, accum)
+
+        def after_step(step):
             if save_path and step % save_every == 0:
                 self.model.save(save_path + ".latest")
             if dev_data is not None and step % eval_every == 0:
                 self.validate_and_save(dev_data, save_path)
-        return step
+
+        return self.run_epoch(self.epoch_order([("mt", len(mt_data))]), step_fn, step=step, max_step=max_step,
+                              log_every=log_every, after_step=after_step)
 
     def validate_and_save(self, dev_data, save_path):
         dl = self.dev_loss(dev_data)
@@ -131,19 +118,12 @@ class SenSimTrainer(ImageMTTrainer):
         """The training loop of ``train`` on a model that is already built."""
         model = model.set_compute_dtype(torch.float32 if options.fp32 else torch.bfloat16).cuda().train()
         optimizer = build_optimizer(model, options.learning_rate, options.warmup)
-        trainer = SenSimTrainer(model=model, mask_prob=options.mask_prob, optimizer=optimizer, clip=options.clip, seed=options.seed)
+        trainer = SenSimTrainer(model=model, optimizer=optimizer, clip=options.clip, seed=options.seed)
         pad = tp.pad_token_id()
-        mt_train, mt_dev = [], None
-        for pth in options.mt_train_path.split(","):
-            if pth.strip():
-                mt_train += dataset.MTDataset(batch_pickle_dir=pth.strip(), max_batch_capacity=options.total_capacity,
-                                              max_batch=options.batch, pad_idx=pad, max_seq_len=options.max_seq_len,
-                                              keep_pad_idx=False).batches
-        for pth in (options.mt_dev_path or "").split(","):
-            if pth.strip():
-                mt_dev = (mt_dev or []) + dataset.MTDataset(batch_pickle_dir=pth.strip(), max_batch_capacity=options.total_capacity,
-                                                            max_batch=options.batch, pad_idx=pad, max_seq_len=options.max_seq_len,
-                                                            keep_pad_idx=False).batches
+        mt_kw = dict(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad, max_seq_len=options.max_seq_len,
+                     keep_pad_idx=False)
+        mt_train = batches_from(options.mt_train_path, **mt_kw)
+        mt_dev = batches_from(options.mt_dev_path, **mt_kw) or None
         neg = lambda path: dataset.MassDataset(batch_pickle_dir=path, max_batch_capacity=options.total_capacity * NEG_FACTOR,
                                                max_batch=options.batch * NEG_FACTOR, pad_idx=pad, keep_pad_idx=False,
                                                max_seq_len=options.max_seq_len, keep_examples=False)
