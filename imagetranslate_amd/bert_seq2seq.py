@@ -8,6 +8,7 @@ load: SURVEY section 8b) -- ``embeddings.{word,position,token_type}_embeddings``
 parameters (views into the flat store, param_store.py).  ``forward`` of a whole stack is one autograd.Function
 that calls ``imt_stack_forward`` / ``imt_stack_backward`` through the C ABI; there is no CPU fallback.
 """
+import contextlib
 import copy
 import ctypes
 import weakref
@@ -171,6 +172,20 @@ def dropout_seed(module, active: bool, salt: int = 0) -> int:
         return 0
     fixed = getattr(module, "_imt_dropout_seed", None)
     return int(fixed) + salt if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+@contextlib.contextmanager
+def dropout_seed_offset(module, offset: int):
+    """A further pass over ``module`` within one forward: inside the block a pinned ``_imt_dropout_seed`` (tests) reads
+    ``offset`` higher, so the pass gets masks of its own.  Without a pinned seed every pass draws its own seed anyway."""
+    fixed = getattr(module, "_imt_dropout_seed", None)
+    if fixed is not None:
+        module._imt_dropout_seed = int(fixed) + offset
+    try:
+        yield
+    finally:
+        if fixed is not None:
+            module._imt_dropout_seed = fixed
 
 
 class _Pretrained(nn.Module):

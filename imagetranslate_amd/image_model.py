@@ -25,7 +25,7 @@ from . import lm_config
 from .bert_seq2seq import BertConfig, BertDecoderModel, BertEncoderModel, _LinearFn, _Pretrained, dropout_seed
 from .mass_seq2seq import MassSeq2Seq
 from .param_store import store_of
-from .seq2seq import FlatStoreModel, future_mask  # noqa: F401
+from .seq2seq import DecoderStream, FlatStoreModel, _GatedMixFn, future_mask, gated_mix, unwrap  # noqa: F401
 
 
 class _ImageHeadFn(torch.autograd.Function):
@@ -118,31 +118,6 @@ class _ObjectHeadFn(torch.autograd.Function):
         return None, None, None, None, None, None, None, None, None
 
 
-class _GatedMixFn(torch.autograd.Function):
-    """sigmoid(gate + 1e-7) * a + (1 - sigmoid(gate + 1e-7)) * b (src/image_model.py:362-366): ``imt_gated_mix`` forward,
-    ``imt_gated_mix_bwd`` backward (the gate's gradient goes straight into the flat fp32 gradient)."""
-
-    @staticmethod
-    def forward(ctx, anchor, a, b, model, gate_param):
-        store = store_of(model).ensure()
-        d = a.shape[-1]
-        gate = store.views(a.dtype, gate_param)[0].view(-1)
-        a2, b2 = a.reshape(-1, d).contiguous(), b.to(a.dtype).reshape(-1, d).contiguous()
-        ctx.store, ctx.gate_param, ctx.layout_version, ctx.shape = store, gate_param, store.layout_version, a.shape
-        ctx.save_for_backward(a2, b2, gate)
-        return O.gated_mix(a2, b2, gate).view(a.shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        a2, b2, gate = ctx.saved_tensors
-        d = a2.shape[1]
-        ctx.store.check_layout(ctx.layout_version, "gated mix")
-        da, db = O.gated_mix_bwd(dout.to(a2.dtype).reshape(-1, d).contiguous(), a2, b2, gate,
-                                 ctx.store.grad_view(ctx.gate_param).view(-1))
-        ctx.store.attach_grad_views()
-        return None, da.view(ctx.shape), db.view(ctx.shape), None, None
-
-
 class _ContrastiveTailFn(torch.autograd.Function):
     """Contrastive tail (src/image_model.py:240-263) as one node: ``imt_attn_pool_fwd`` on the caption states (masked by
     src_pads), the negative-sample states (masked by neg_mask), both with encoder_attention_w, and on the image regions with
@@ -187,11 +162,6 @@ class _ContrastiveTailFn(torch.autograd.Function):
         d_im = O.attn_pool_bwd(img, wi, None, img_u, p_i, n_i, d_img, gw_i, gb_i, du_scale=g)
         store.attach_grad_views()
         return None, d_enc, None, d_neg, None, d_im, None
-
-
-def gated_mix(model, gate_param, a, b):
-    """Autograd-aware sigmoid-gated mix of two [..., d] streams with a gate parameter of ``model``'s flat store."""
-    return _GatedMixFn.apply(store_of(model).ensure().anchor_if_grad(), a, b, model, gate_param)
 
 
 class ImageHead(nn.Module):
@@ -294,31 +264,9 @@ class ImageMassSeq2Seq(MassSeq2Seq):
     def encode(self, src_inputs, src_mask, src_langs, images=None):
         encoder_states = super().encode(src_inputs, src_mask, src_langs)
         if images is not None:
-            if isinstance(images, list):
-                images = images[0]
-            image_embeddings = self.image_model(images, self._imt_compute_dtype)
+            image_embeddings = self.image_model(unwrap(images), self._imt_compute_dtype)
             return encoder_states[0], image_embeddings
         return encoder_states
-
-    @staticmethod
-    def _un(x):
-        return x[0] if isinstance(x, list) else x
-
-    def _mix_image_stream(self, text_output, image_embeddings, batch_lang, **dec_kw):
-        """The SAME decoder a second time, over the image regions with no key mask (src/image_model.py:213-216), and the
-        sigmoid-gated mix of the two outputs (:217-219).  The pass draws its own dropout seed; the shared decoder parameters
-        receive both passes' gradients (the stack runtime accumulates into the flat gradient)."""
-        decoder = self._decoder_for(batch_lang)
-        dec_kw["encoder_attention_mask"] = None
-        fixed = getattr(decoder, "_imt_dropout_seed", None)
-        if fixed is not None:  # a pinned seed (tests): the second pass still gets masks of its own
-            decoder._imt_dropout_seed = int(fixed) + 1
-        try:
-            image_output = decoder(encoder_states=image_embeddings, **dec_kw)
-        finally:
-            if fixed is not None:
-                decoder._imt_dropout_seed = fixed
-        return gated_mix(self, self.multimodal_attention_gate, text_output, image_output)
 
     def _encode_text_and_image(self, src_inputs, src_pads, src_langs, batch):
         """(encoder states, image embeddings, src_pads on the device) of src/image_model.py:185-190.  The reference's head
@@ -331,16 +279,20 @@ class ImageMassSeq2Seq(MassSeq2Seq):
         src_pads = (src_inputs != self.text_processor.pad_token_id()) if src_pads is None else src_pads.to(device)
         src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
         encoder_states = MassSeq2Seq.encode(self, src_inputs, src_pads, src_langs_t)[0]
-        images = batch["images"]
-        image_embeddings = self.image_model(images[0] if isinstance(images, list) else images, self._imt_compute_dtype)[0]
+        image_embeddings = self.image_model(unwrap(batch["images"]), self._imt_compute_dtype)[0]
         return encoder_states, image_embeddings, src_pads
 
     def _multimodal_rows(self, src_inputs, src_pads, tgt_inputs, src_langs, tgt_langs, pad_idx, tgt_positions, batch, proposals):
         """Non-pad decoder rows of the gated text + image branch (src/image_model.py:192-226)."""
         assert tgt_inputs is not None
         encoder_states, image_embeddings, src_pads = self._encode_text_and_image(src_inputs, src_pads, src_langs, batch)
-        return self._target_rows(encoder_states, src_pads, tgt_inputs, None, tgt_langs if tgt_langs is not None else src_langs,
-                                 pad_idx, tgt_positions, proposals, img_states=image_embeddings)
+        langs = tgt_langs if tgt_langs is not None else src_langs
+        batch_lang = int(langs[0])
+        decoder = self._decoder_for(batch_lang)
+        # the SAME decoder over the text states (key mask src_pads) and over the image regions, no key mask (:213-216)
+        streams = [DecoderStream(decoder, encoder_states, src_pads, None),
+                   DecoderStream(decoder, image_embeddings, None, self.multimodal_attention_gate)]
+        return self._target_rows(streams, tgt_inputs, None, langs, pad_idx, tgt_positions, proposals) + (batch_lang,)
 
     def _contrastive_loss(self, src_inputs, src_pads, src_langs, tgt_langs, batch, neg_samples, neg_mask):
         """src/image_model.py:231-264: the captions, the negative samples and the image regions pooled to unit vectors, and the
@@ -365,7 +317,7 @@ class ImageMassSeq2Seq(MassSeq2Seq):
         reference keeps the (grid, objects) tuple, :153, and fails); and ``tgt_langs``, which both branches read (:197, :235) but
         the reference trainer never passes (src/train_image_mt.py:218-236), defaults to ``src_langs`` -- the masked caption is
         recovered, and the negatives are written, in the captions' own language, as in the MASS step."""
-        u = self._un
+        u = unwrap
         batch, src_langs, tgt_langs, src_pads = u(batch), u(src_langs), u(tgt_langs), u(src_pads)
         src_inputs, tgt_positions, tgt_inputs, proposals = u(src_inputs), u(tgt_positions), u(tgt_inputs), u(proposals)
         if batch is None:
@@ -383,19 +335,17 @@ class ImageMassSeq2Seq(MassSeq2Seq):
                    neg_mask=None, **kwargs):
         """(loss, ntokens).  With ``batch``: the gated text + image branch through the fused projection + loss, or, with
         ``neg_samples``, the contrastive loss and 0 tokens (nothing is predicted, src/train_image_mt.py:274-276)."""
-        u = self._un
-        batch = u(batch)
-        if batch is not None:
-            if neg_samples is not None:
-                return self._contrastive_loss(u(src_inputs), u(src_pads), u(src_langs), u(tgt_langs), batch, u(neg_samples),
-                                              u(neg_mask)), 0
-            rows, tgt_inputs, tgt_mask, batch_lang = self._multimodal_rows(u(src_inputs), u(src_pads), u(tgt_inputs), u(src_langs),
-                                                                           u(tgt_langs), pad_idx, u(tgt_positions), batch,
-                                                                           u(proposals))
-            return self._loss_from_rows(rows, tgt_inputs, tgt_mask, batch_lang, epsilon)
-        return MassSeq2Seq.loss_fused(self, u(src_inputs), u(tgt_inputs), u(src_langs), tgt_langs=u(tgt_langs),
-                                      pad_idx=pad_idx, tgt_positions=u(tgt_positions), epsilon=epsilon,
-                                      proposals=u(proposals))
+        u = unwrap
+        batch, src_langs, tgt_langs, src_pads = u(batch), u(src_langs), u(tgt_langs), u(src_pads)
+        src_inputs, tgt_positions, tgt_inputs, proposals = u(src_inputs), u(tgt_positions), u(tgt_inputs), u(proposals)
+        if batch is None:
+            return MassSeq2Seq.loss_fused(self, src_inputs, tgt_inputs, src_langs, tgt_langs=tgt_langs, pad_idx=pad_idx,
+                                          tgt_positions=tgt_positions, epsilon=epsilon, proposals=proposals)
+        if neg_samples is not None:
+            return self._contrastive_loss(src_inputs, src_pads, src_langs, tgt_langs, batch, u(neg_samples), u(neg_mask)), 0
+        rows, tgt_inputs, tgt_mask, batch_lang = self._multimodal_rows(src_inputs, src_pads, tgt_inputs, src_langs, tgt_langs, pad_idx,
+                                                                       tgt_positions, batch, proposals)
+        return self._loss_from_rows(rows, tgt_inputs, tgt_mask, batch_lang, epsilon)
 
 
 class ImageCaptioning(ImageMassSeq2Seq):
@@ -455,36 +405,30 @@ class ImageCaptioning(ImageMassSeq2Seq):
         """Images: (image_embeddings, object_fc or None) (src/image_model.py:298-308).  ``objects`` (build extension):
         pre-extracted detector output in place of the frozen Faster-RCNN (see ``_objects_present``)."""
         if images is not None:
-            if isinstance(images, list):
-                images = images[0]
-            image_embeddings, _ = self.image_model(images, self._imt_compute_dtype)
+            image_embeddings, _ = self.image_model(unwrap(images), self._imt_compute_dtype)
             object_fc = None
             if "obj_decoder" in self._modules:
-                object_fc = self.image_model.objects_forward(self._un(objects), self._imt_compute_dtype)
+                object_fc = self.image_model.objects_forward(unwrap(objects), self._imt_compute_dtype)
             return image_embeddings, object_fc
         return MassSeq2Seq.encode(self, src_inputs, src_mask, src_langs)
 
     def _obj_decoder_for(self, batch_lang):
         return self.obj_decoder[batch_lang] if self.lang_dec else self.obj_decoder
 
-    def _mix_object_stream(self, decoder_output, object_fc, batch_lang, **dec_kw):
-        """Second decoder pass over object_fc (no key mask: padded object rows take part, src/image_model.py:357-361) and
-        the sigmoid-gated mix with the image decoder's output (:362-366)."""
-        object_output = self._obj_decoder_for(batch_lang)(encoder_states=object_fc, **dec_kw)
-        return gated_mix(self, self.multistream_attention_gate, decoder_output, object_output)
-
     def _caption_rows(self, batch, src_pads, tgt_inputs, tgt_langs, tgt_mask, pad_idx, tgt_positions, proposals):
-        u = self._un
-        tgt_positions, tgt_inputs, tgt_mask, tgt_langs = u(tgt_positions), u(tgt_inputs), u(tgt_mask), u(tgt_langs)
+        tgt_positions, tgt_inputs, tgt_mask, tgt_langs, src_pads = map(unwrap, (tgt_positions, tgt_inputs, tgt_mask, tgt_langs, src_pads))
         image_embeddings, object_fc = self.encode(images=batch["images"], objects=batch.get("objects"))
         assert tgt_inputs is not None
-        return self._target_rows(image_embeddings, u(src_pads), tgt_inputs, tgt_mask, tgt_langs, pad_idx, tgt_positions,
-                                 proposals, obj_states=object_fc)
+        batch_lang = int(tgt_langs[0])
+        streams = [DecoderStream(self._decoder_for(batch_lang), image_embeddings, src_pads, None)]
+        if object_fc is not None:  # second decoder over the object rows, same key mask (None for caption batches, :357-361)
+            streams.append(DecoderStream(self._obj_decoder_for(batch_lang), object_fc, src_pads, self.multistream_attention_gate))
+        return self._target_rows(streams, tgt_inputs, tgt_mask, tgt_langs, pad_idx, tgt_positions, proposals) + (batch_lang,)
 
     def forward(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, tgt_mask=None,
                 pad_idx: int = 0, tgt_positions=None, batch=None, proposals=None, log_softmax: bool = False,
                 encode_only: bool = False, **kwargs):
-        batch = self._un(batch)
+        batch = unwrap(batch)
         if batch is None or src_inputs is not None:  # text-based input (:318-320)
             return ImageMassSeq2Seq.forward(self, src_inputs=src_inputs, src_mask=src_pads, tgt_inputs=tgt_inputs,
                                             src_langs=src_langs, tgt_langs=tgt_langs, proposals=proposals,
@@ -497,7 +441,7 @@ class ImageCaptioning(ImageMassSeq2Seq):
 
     def loss_fused(self, src_inputs=None, src_pads=None, tgt_inputs=None, src_langs=None, tgt_langs=None, tgt_mask=None,
                    pad_idx: int = 0, tgt_positions=None, batch=None, proposals=None, epsilon: float = 0.1, **kwargs):
-        batch = self._un(batch)
+        batch = unwrap(batch)
         if batch is None or src_inputs is not None:
             return ImageMassSeq2Seq.loss_fused(self, src_inputs=src_inputs, tgt_inputs=tgt_inputs, src_langs=src_langs,
                                                tgt_langs=tgt_langs, pad_idx=pad_idx, epsilon=epsilon,
@@ -608,8 +552,7 @@ class Caption2Image(FlatStoreModel):
 
     def forward(self, src_inputs, src_mask, src_langs):
         """[B, 49 * d] in the compute dtype: encoder stack -> dropout (training) + attention pooling, one kernel -> linear."""
-        un = ImageMassSeq2Seq._un
-        src_inputs, src_mask, src_langs = un(src_inputs), un(src_mask), un(src_langs)
+        src_inputs, src_mask, src_langs = unwrap(src_inputs), unwrap(src_mask), unwrap(src_langs)
         device = self._device
         src_langs = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1)).to(device)
         src_inputs, src_mask = src_inputs.to(device), src_mask.to(device)
@@ -624,7 +567,7 @@ class Caption2Image(FlatStoreModel):
         """(loss, number of images): |forward(...) - image_encoding|_2 / B (src/train_txt2image.py:62-67).  ``image_encoding``
         ([B, 49, d] or [B, 49 * d], e.g. ``ImageCaptioning(batch=..., encode_only=True)``) is a constant."""
         pred = self(src_inputs, src_mask, src_langs)
-        target = ImageMassSeq2Seq._un(image_encoding).detach()
+        target = unwrap(image_encoding).detach()
         if target.size(0) != pred.size(0) or target.numel() != pred.numel():
             raise ValueError("Caption2Image: image_encoding %s does not match the %d x %d predictions" % (tuple(target.shape), pred.size(0), pred.size(1)))
         target = target.reshape(pred.shape).to(device=pred.device, dtype=pred.dtype).contiguous()

@@ -1,22 +1,10 @@
 """MASS masked-seq2seq forward -- drop-in for the reference's ``src/mass_seq2seq.py:6-60``."""
 import torch
 
-from .seq2seq import Seq2Seq, future_mask  # noqa: F401
+from .seq2seq import DecoderStream, Seq2Seq, future_mask, unwrap  # noqa: F401
 
 
 class MassSeq2Seq(Seq2Seq):
-    def _unwrap_mass_args(self, src_inputs, tgt_inputs, src_langs, tgt_positions):
-        # threaded-DP convention of the reference: any argument may arrive wrapped in a 1-element list (:14-21)
-        if isinstance(tgt_inputs, list):
-            assert len(tgt_inputs) == 1
-            tgt_inputs = tgt_inputs[0]
-            src_langs = src_langs[0]
-        if isinstance(src_inputs, list):
-            src_inputs = src_inputs[0]
-        if isinstance(tgt_positions, list):
-            tgt_positions = tgt_positions[0]
-        return src_inputs, tgt_inputs, src_langs, tgt_positions
-
     def _mass_rows(self, src_inputs, tgt_inputs, src_langs, pad_idx, tgt_positions, proposals):
         device = self._device
         tgt_inputs = tgt_inputs.to(device)  # (first, as it always was: the copies to the device come before the encoder's launches)
@@ -24,12 +12,14 @@ class MassSeq2Seq(Seq2Seq):
         src_pads = src_inputs != pad_idx
         src_langs_t = self._lang_grid(src_langs, src_inputs.size(-1), device)
         encoder_states = self.encode(src_inputs, src_pads, src_langs_t)[0]
-        return self._target_rows(encoder_states, src_pads, tgt_inputs, None, src_langs, pad_idx, tgt_positions, proposals)
+        batch_lang = int(src_langs[0])
+        streams = [DecoderStream(self._decoder_for(batch_lang), encoder_states, src_pads, None)]
+        return self._target_rows(streams, tgt_inputs, None, src_langs, pad_idx, tgt_positions, proposals) + (batch_lang,)
 
     def forward(self, src_inputs, tgt_inputs, src_langs, tgt_langs=None, pad_idx: int = 0, tgt_positions=None,
                 log_softmax: bool = False, proposals=None):
-        src_inputs, tgt_inputs, src_langs, tgt_positions = self._unwrap_mass_args(src_inputs, tgt_inputs, src_langs,
-                                                                                 tgt_positions)
+        # threaded-DP convention of the reference: any argument may arrive wrapped in a 1-element list (:14-21)
+        src_inputs, tgt_inputs, src_langs, tgt_positions = unwrap(src_inputs), unwrap(tgt_inputs), unwrap(src_langs), unwrap(tgt_positions)
         if tgt_langs is not None:
             # back-translation / MT loss (:27-30)
             tgt_inputs = tgt_inputs.to(self._device)
@@ -44,8 +34,7 @@ class MassSeq2Seq(Seq2Seq):
     def loss_fused(self, src_inputs, tgt_inputs, src_langs, tgt_langs=None, pad_idx: int = 0, tgt_positions=None,
                    epsilon: float = 0.1, proposals=None, **kwargs):
         """Fast-path loss for MT (tgt_langs given) or MASS batches; returns (loss, ntokens)."""
-        src_inputs, tgt_inputs, src_langs, tgt_positions = self._unwrap_mass_args(src_inputs, tgt_inputs, src_langs,
-                                                                                 tgt_positions)
+        src_inputs, tgt_inputs, src_langs, tgt_positions = unwrap(src_inputs), unwrap(tgt_inputs), unwrap(src_langs), unwrap(tgt_positions)
         if tgt_langs is not None:
             tgt_inputs = tgt_inputs.to(self._device)
             return Seq2Seq.loss_fused(self, src_inputs, tgt_inputs, src_inputs != pad_idx, tgt_inputs != pad_idx,

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import hip_ops as O
 from . import lm_config
-from .bert_seq2seq import BertConfig, BertEncoderModel
+from .bert_seq2seq import BertConfig, BertEncoderModel, dropout_seed_offset
 from .param_store import store_of
 from .seq2seq import FlatStoreModel
 
@@ -159,14 +159,8 @@ class SenSim(FlatStoreModel):
         device = self._device
         inputs, mask = inputs.to(device), mask.to(device)
         langs = langs.to(device).unsqueeze(-1).expand(-1, inputs.size(-1))
-        fixed = getattr(self.encoder, "_imt_dropout_seed", None)
-        if fixed is None or pass_index == 0:
+        with dropout_seed_offset(self.encoder, pass_index):
             return self.encoder(inputs, attention_mask=mask, token_type_ids=langs), mask
-        self.encoder._imt_dropout_seed = int(fixed) + pass_index
-        try:
-            return self.encoder(inputs, attention_mask=mask, token_type_ids=langs), mask
-        finally:
-            self.encoder._imt_dropout_seed = fixed
 
     @torch.no_grad()
     def encode(self, src_inputs, src_mask, src_langs):

@@ -15,14 +15,29 @@ import json
 import os
 import pickle
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from . import hip_ops as O
 from . import lm_config
-from .bert_seq2seq import BertConfig, BertDecoderModel, BertEncoderModel, BertOutputLayer, _Pretrained
+from .bert_seq2seq import BertConfig, BertDecoderModel, BertEncoderModel, BertOutputLayer, _Pretrained, dropout_seed_offset
 from .param_store import store_of
+
+
+def unwrap(x):
+    """Threaded-DP convention of the reference: any argument may arrive wrapped in a 1-element list."""
+    return x[0] if isinstance(x, list) else x
+
+
+class DecoderStream(NamedTuple):
+    """One encoder-side input of the decoder: the stack that reads it, its states [B, Tk, d], the key mask over Tk (None: no
+    mask) and the gate parameter that mixes this pass into the output of the streams before it (None for the first)."""
+    decoder: nn.Module
+    states: torch.Tensor
+    key_mask: Optional[torch.Tensor]
+    gate: Optional[nn.Parameter]
 
 
 def future_mask(tgt_mask):
@@ -143,6 +158,36 @@ class _ProposalAttnFn(torch.autograd.Function):
                                  store.grad_view(ln.weight), store.grad_view(ln.bias), rows_per_group, pad_idx)
         store.attach_grad_views()
         return None, dx.view(shape), None, None, None, None
+
+
+class _GatedMixFn(torch.autograd.Function):
+    """sigmoid(gate + 1e-7) * a + (1 - sigmoid(gate + 1e-7)) * b (src/image_model.py:362-366): ``imt_gated_mix`` forward,
+    ``imt_gated_mix_bwd`` backward (the gate's gradient goes straight into the flat fp32 gradient)."""
+
+    @staticmethod
+    def forward(ctx, anchor, a, b, model, gate_param):
+        store = store_of(model).ensure()
+        d = a.shape[-1]
+        gate = store.views(a.dtype, gate_param)[0].view(-1)
+        a2, b2 = a.reshape(-1, d).contiguous(), b.to(a.dtype).reshape(-1, d).contiguous()
+        ctx.store, ctx.gate_param, ctx.layout_version, ctx.shape = store, gate_param, store.layout_version, a.shape
+        ctx.save_for_backward(a2, b2, gate)
+        return O.gated_mix(a2, b2, gate).view(a.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        a2, b2, gate = ctx.saved_tensors
+        d = a2.shape[1]
+        ctx.store.check_layout(ctx.layout_version, "gated mix")
+        da, db = O.gated_mix_bwd(dout.to(a2.dtype).reshape(-1, d).contiguous(), a2, b2, gate,
+                                 ctx.store.grad_view(ctx.gate_param).view(-1))
+        ctx.store.attach_grad_views()
+        return None, da.view(ctx.shape), db.view(ctx.shape), None, None
+
+
+def gated_mix(model, gate_param, a, b):
+    """Autograd-aware sigmoid-gated mix of two [..., d] streams with a gate parameter of ``model``'s flat store."""
+    return _GatedMixFn.apply(store_of(model).ensure().anchor_if_grad(), a, b, model, gate_param)
 
 
 class FlatStoreModel(nn.Module):
@@ -429,21 +474,21 @@ class Seq2Seq(FlatStoreModel):
         idx = torch.nonzero(tgt_mask[:, 1:].reshape(-1), as_tuple=False).view(-1)
         return idx.to(torch.int32), tgt_inputs[:, 1:].reshape(-1)[idx]
 
-    def _decode(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=None,
-                proposals=None, pad_idx=0, sel_idx=None, obj_states=None, img_states=None):
-        decoder = self._decoder_for(batch_lang)
+    def _decode(self, streams, tgt_inputs, tgt_mask, tgt_langs_t, position_ids=None, proposals=None, pad_idx=0, sel_idx=None):
+        """Non-pad decoder rows over ``streams``: the first ``DecoderStream``'s pass, then every later one's mixed in through its
+        gate (src/image_model.py:213-219 text + image, :357-369 image + objects), before attend_proposal.  A stack that reads k
+        streams runs k times: every pass draws its own dropout seed (pinned seed: + 0, + 1, ...) and adds to the stack's gradient."""
         info = self.__dict__.get("_imt_grid_info", {}).get(id(tgt_langs_t))
         if info is not None:  # a cached uniform grid: use the (T-1)-wide one instead of a non-contiguous slice
             types = self._uniform_grid(info[0], tgt_langs_t.size(1) - 1, info[1], tgt_langs_t.device)
         else:
             types = tgt_langs_t[:, :-1]
-        dec_kw = dict(input_ids=tgt_inputs[:, :-1], encoder_attention_mask=enc_mask, tgt_query_mask=tgt_mask[:, :-1],
-                      position_ids=position_ids, token_type_ids=types)
-        decoder_output = decoder(encoder_states=encoder_states, **dec_kw)
-        if img_states is not None:  # ImageMassSeq2Seq's text + image branch: second pass over the regions, gated (src/image_model.py:213-219)
-            decoder_output = self._mix_image_stream(decoder_output, img_states, batch_lang, **dec_kw)
-        if obj_states is not None:  # ImageCaptioning's object stream, mixed in before attend_proposal (src/image_model.py:357-369)
-            decoder_output = self._mix_object_stream(decoder_output, obj_states, batch_lang, **dec_kw)
+        dec_kw = dict(input_ids=tgt_inputs[:, :-1], tgt_query_mask=tgt_mask[:, :-1], position_ids=position_ids, token_type_ids=types)
+        decoder_output = None
+        for k, s in enumerate(streams):
+            with dropout_seed_offset(s.decoder, sum(1 for earlier in streams[:k] if earlier.decoder is s.decoder)):
+                out = s.decoder(encoder_states=s.states, encoder_attention_mask=s.key_mask, **dec_kw)
+            decoder_output = out if k == 0 else gated_mix(self, s.gate, decoder_output, out)
         if self.use_proposals:
             decoder_output = self.attend_proposal(decoder_output, proposals, pad_idx)
         flat = decoder_output.reshape(-1, decoder_output.size(-1))
@@ -453,20 +498,16 @@ class Seq2Seq(FlatStoreModel):
             return flat  # no padding: the ordered selection of every row is the identity -- no gather / scatter launches
         return _SelectRowsFn.apply(flat, sel_idx)
 
-    def _target_rows(self, encoder_states, enc_mask, tgt_inputs, tgt_mask, langs, pad_idx, tgt_positions, proposals,
-                     **streams):
-        """Target side shared by the MASS, text + image and captioning forwards: (non-pad decoder rows, ``tgt_inputs`` and
-        ``tgt_mask`` on the device, language of the batch).  ``tgt_mask`` None: every non-pad position.  ``streams``:
-        ``img_states=`` / ``obj_states=`` of ``_decode``."""
+    def _target_rows(self, streams, tgt_inputs, tgt_mask, langs, pad_idx, tgt_positions, proposals):
+        """Target side shared by the MASS, text + image and captioning forwards: (non-pad decoder rows over ``streams``,
+        ``tgt_inputs`` and ``tgt_mask`` on the device).  ``tgt_mask`` None: every non-pad position."""
         device = self._device
         tgt_inputs = tgt_inputs.to(device)
         tgt_mask = (tgt_inputs != pad_idx) if tgt_mask is None else tgt_mask.to(device)
-        batch_lang = int(langs[0])
         tgt_langs_t = self._lang_grid(langs, tgt_inputs.size(-1), device)
         pos = tgt_positions[:, :-1].to(device) if tgt_positions is not None else None
-        rows = self._decode(encoder_states, enc_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, position_ids=pos,
-                            proposals=proposals, pad_idx=pad_idx, **streams)
-        return rows, tgt_inputs, tgt_mask, batch_lang
+        rows = self._decode(streams, tgt_inputs, tgt_mask, tgt_langs_t, position_ids=pos, proposals=proposals, pad_idx=pad_idx)
+        return rows, tgt_inputs, tgt_mask
 
     def _project(self, rows, batch_lang, log_softmax):
         outputs = self._output_layer(batch_lang)(rows)
@@ -481,14 +522,11 @@ class Seq2Seq(FlatStoreModel):
         batch_lang = int(tgt_langs[0])
         src_langs = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1))
         tgt_langs = tgt_langs.unsqueeze(-1).expand(-1, tgt_inputs.size(-1)).to(device)
-        src_inputs = src_inputs.to(device)
-        src_langs = src_langs.to(device)
-        tgt_inputs = tgt_inputs.to(device)
-        tgt_mask = tgt_mask.to(device)
-        src_mask = src_mask.to(device)
+        src_inputs, src_langs = src_inputs.to(device), src_langs.to(device)
+        tgt_inputs, tgt_mask, src_mask = tgt_inputs.to(device), tgt_mask.to(device), src_mask.to(device)
         encoder_states = self.encode(src_inputs, src_mask, src_langs)[0]
-        rows = self._decode(encoder_states, src_mask, tgt_inputs, tgt_mask, tgt_langs, batch_lang, proposals=proposals,
-                            pad_idx=self.text_processor.pad_token_id())
+        rows = self._decode([DecoderStream(self._decoder_for(batch_lang), encoder_states, src_mask, None)], tgt_inputs, tgt_mask, tgt_langs,
+                            proposals=proposals, pad_idx=self.text_processor.pad_token_id())
         return self._project(rows, batch_lang, log_softmax)
 
     def loss_fused(self, src_inputs, tgt_inputs, src_mask, tgt_mask, src_langs, tgt_langs, epsilon: float = 0.1,
@@ -506,8 +544,8 @@ class Seq2Seq(FlatStoreModel):
         src_mask, tgt_mask = src_mask.to(device), tgt_mask.to(device)
         sel_idx, targets = self._selection(tgt_inputs, tgt_mask, ntokens)
         encoder_states = self.encode(src_inputs, src_mask, src_langs_t)[0]
-        rows = self._decode(encoder_states, src_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang, proposals=proposals,
-                            pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
+        rows = self._decode([DecoderStream(self._decoder_for(batch_lang), encoder_states, src_mask, None)], tgt_inputs, tgt_mask,
+                            tgt_langs_t, proposals=proposals, pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
         return self._loss_from_rows(rows, tgt_inputs, tgt_mask, batch_lang, epsilon, targets=targets)
 
     def _loss_from_rows(self, rows, tgt_inputs, tgt_mask, batch_lang, epsilon, targets=None):
@@ -551,8 +589,8 @@ class Seq2Seq(FlatStoreModel):
         if targets.numel() == 0:
             scores = torch.zeros(tgt_inputs.size(0), dtype=torch.float32, device=device)
             return (scores, scores.new_zeros(0), offsets) if return_token_logprobs else scores
-        rows = self._decode(encoder_states, src_mask, tgt_inputs, tgt_mask, tgt_langs_t, batch_lang,
-                            pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
+        rows = self._decode([DecoderStream(self._decoder_for(batch_lang), encoder_states, src_mask, None)], tgt_inputs, tgt_mask,
+                            tgt_langs_t, pad_idx=self.text_processor.pad_token_id(), sel_idx=sel_idx)
         # the projection operands in the compute dtype, straight from the flat store (as _LinearFn takes them)
         output_layer = self._output_layer(batch_lang)
         weight, bias = store_of(output_layer).ensure().views(rows.dtype, output_layer.layer.weight, output_layer.layer.bias)

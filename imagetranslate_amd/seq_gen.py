@@ -12,16 +12,11 @@ What differs is HOW a step is computed:
     "every hypothesis has EOS" stop condition (``:134-136``) every ``sync_every`` steps.
   * ``kv_cache=False`` keeps the reference's literal per-step recomputation (on the HIP decoder) -- used by the
     tests to show both modes produce the same tokens.
-  * ``objects=`` (build extension, ImageCaptioning with ``use_obj``): pre-extracted detector output in place of the
-    frozen Faster-RCNN (``{"feats", "boxes", "labels"}``, see image_model).  A second incremental decoder runs
-    ``obj_decoder`` over the object rows (its own cross K/V with Tk = N, workspace and self cache; the slot table is
-    shared) and its state is mixed into the image decoder's through the sigmoid gate before the projection
-    (``:164-180``; no key mask, the object rows of a sentence serve all its beams like the image states).
-  * ``src_inputs=`` together with ``images=`` on an ``ImageMassSeq2Seq`` (``:105-106,180-188``): the text and the image are both
-    encoded (the image embeddings are element 0 of the image head's output; ``image_embed=``, when given as well, replaces that
-    encoding), and per step the decoder runs over the text states with the source mask and over the image states without one,
-    mixed through ``multimodal_attention_gate``.  With ``kv_cache`` the second pass is a second incremental decoder over the SAME
-    stack, built like the object stream's.  (``src_inputs=`` with ``image_embed=`` alone stays the text search, as in ``:94``.)
+  * ``objects=`` (build extension, ImageCaptioning with ``use_obj``: pre-extracted detector output ``{"feats", "boxes", "labels"}``
+    in place of the frozen Faster-RCNN, see image_model) and ``src_inputs=`` together with ``images=`` on an ``ImageMassSeq2Seq``
+    (``:105-106``) give every step a second stream, mixed into the first through a sigmoid gate before the projection:
+    ``decoder_streams`` says which stack reads what with which key mask.  With ``kv_cache`` each stream has an incremental
+    decoder of its own (cross K/V, workspace, self cache; the slot table is shared).
 Ties between equal scores (``torch.topk`` leaves them unspecified, and ``:194-196`` creates them on purpose) are
 broken towards the lowest flat index.  ``:216`` is taken as floor division (torch 1.4 semantics).
 """
@@ -33,6 +28,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import hip_ops as O
 from .param_store import store_of
+from .seq2seq import DecoderStream, unwrap
 
 
 def get_outputs_until_eos(eos, outputs, size_limit=None, remove_first_token: bool = False):
@@ -46,36 +42,137 @@ def get_outputs_until_eos(eos, outputs, size_limit=None, remove_first_token: boo
     begin = 1 if remove_first_token else 0
     cut = []
     for r in range(outputs.size(0)):
-        if bool(has[r]):
-            end = int(first[r])
-        else:
-            end = outputs.size(1) if size_limit is None else int(size_limit[r])
+        end = int(first[r]) if bool(has[r]) else (outputs.size(1) if size_limit is None else int(size_limit[r]))
         cut.append(outputs[r, begin:end])
     return cut
 
 
-def _un(x):
-    return x[0] if isinstance(x, list) else x
-
-
 class _BeamState:
-    """Device-resident ping-pong state of one search (all sizes fixed up front: r_max = B*beam rows)."""
+    """Device-resident ping-pong state of one search (all sizes fixed up front: r_max = B*beam rows), seeded with the first
+    tokens; ``cur`` is the side the next step reads.  ``args``: the ``BeamArgs`` with the sizes and this state's fixed pointers."""
 
-    def __init__(self, B, beam, t_max, V, device, use_slots):
+    def __init__(self, first_tokens, eos, beam, t_max, use_slots):
+        B, device = first_tokens.numel(), first_tokens.device
         r = B * beam
         i64, i32, f32, u8 = torch.int64, torch.int32, torch.float32, torch.uint8
         z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=device)
+        self.B, self.beam, self.t_max = B, beam, t_max
         self.hist = [z(r, t_max, dtype=i64), z(r, t_max, dtype=i64)]
         self.slots = [z(r, t_max, dtype=i32), z(r, t_max, dtype=i32)] if use_slots else [None, None]
         self.scores = [z(r, dtype=f32), z(r, dtype=f32)]
         self.sizes = [z(r, dtype=f32), z(r, dtype=f32)]
         self.eos = [z(r, dtype=u8), z(r, dtype=u8)]
-        self.cand_scores = z(r, beam, dtype=f32)
-        self.cand_idx = z(r, beam, dtype=i32)
-        self.parent = z(r, dtype=i32)
-        self.tokens = z(r, dtype=i64)
-        self.eos_count = z(t_max, dtype=i32)
+        self.cand_scores, self.cand_idx = z(r, beam, dtype=f32), z(r, beam, dtype=i32)
+        self.parent, self.tokens, self.eos_count = z(r, dtype=i32), z(r, dtype=i64), z(t_max, dtype=i32)
         self.cur = 0
+        self.hist[0][:B, 0] = first_tokens
+        self.eos[0][:B] = (first_tokens == eos).to(u8)
+        if use_slots:
+            self.slots[0][:B, 0] = torch.arange(B, dtype=i32, device=device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self.sides = [[ptr(t[k]) for t in (self.scores, self.sizes, self.eos, self.hist, self.slots)] for k in (0, 1)]
+        self.args = a = L.BeamArgs()
+        a.B, a.beam, a.t_max, a.cand_scores, a.cand_idx = B, beam, t_max, ptr(self.cand_scores), ptr(self.cand_idx)
+        a.parent_out, a.tokens_out, a.eos_count = ptr(self.parent), ptr(self.tokens), ptr(self.eos_count)
+
+    def bind_step(self, rep, step):
+        """``args`` for one step: it reads side ``cur`` and writes the other."""
+        a = self.args
+        a.rep, a.step = rep, step
+        a.scores_in, a.sizes_in, a.eos_in, a.hist_in, a.slots_in = self.sides[self.cur]
+        a.scores_out, a.sizes_out, a.eos_out, a.hist_out, a.slots_out = self.sides[self.cur ^ 1]
+        return a
+
+    def best(self, n_cols):
+        """The first hypothesis of every sentence, ``n_cols`` columns (1: no step ran, still one row per sentence)."""
+        hist = self.hist[self.cur]
+        return hist[:self.B, :1] if n_cols == 1 else hist.view(self.B, self.beam, self.t_max)[:, 0, :n_cols]
+
+
+def length_limits(max_len, max_len_a, max_len_b, max_pos, batch_size, src_len=None, src_sizes=None, images=False):
+    """(max_len, per-sentence limits, t_max) of one search -- pure host arithmetic (src/seq_gen.py:86-91,113-121).
+    ``max_len`` None: 512 when ``images`` are given (:90-91), else the limit of the source width ``src_len`` (:116-117).  With a
+    source (``src_len`` not None) sentence b may grow to min(int(max_len_a * src_sizes[b] + max_len_b), max_pos) tokens (:113-114,
+    :121); without one every sentence gets ``max_len`` (:118-119).  ``t_max`` >= 2: the first token and one step always fit."""
+    limit = lambda s: min(int(max_len_a * s + max_len_b), max_pos)
+    if max_len is None:
+        max_len = 512 if images else limit(src_len)
+    max_lens = [max_len] * batch_size if src_len is None else [limit(int(s)) for s in src_sizes]
+    return max_len, max_lens, max(int(max_len), 2)
+
+
+def decoder_streams(model, batch_lang, text=None, text_mask=None, image=None, objects=None):
+    """The ``DecoderStream``s one search step decodes, from already-encoded tensors (no kernel runs here):
+      text                 the language's decoder over ``text`` with the source mask (src/seq_gen.py:163-166);
+      text + image         and the SAME decoder over ``image`` with no key mask, mixed through multimodal_attention_gate (:181-188);
+      caption              the decoder over ``image`` (from ``images`` or ``image_embed``), no key mask (:152-154,164-166);
+      caption + objects    and ``obj_decoder`` over ``objects``, no key mask, mixed through multistream_attention_gate (:167-179)."""
+    decoder = model._decoder_for(batch_lang)
+    if text is not None:
+        streams = [DecoderStream(decoder, text, text_mask, None)]
+        if image is not None:
+            streams.append(DecoderStream(decoder, image, None, model.multimodal_attention_gate))
+        return streams
+    streams = [DecoderStream(decoder, image, None, None)]
+    if objects is not None:
+        streams.append(DecoderStream(model._obj_decoder_for(batch_lang), objects, None, model.multistream_attention_gate))
+    return streams
+
+
+def _mixed(out, states, gate):
+    """``states`` of a further stream mixed into ``out`` through its gate (the first stream: ``states`` as they are)."""
+    return states if out is None else O.gated_mix(out.contiguous(), states.contiguous(), gate)
+
+
+class _CachedSteps:
+    """Step provider of ``kv_cache=True``: per stream an ``_Incremental`` (cross K/V, self cache, workspace) and a hidden buffer;
+    a step decodes one position per hypothesis.  The slot table of ``st`` is shared by the streams."""
+
+    def __init__(self, streams, gates, st, first_tokens, type_rows, store, dtype, flat):
+        lib, cu_stream = L.load(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.st, self.first_tokens, self.type_rows, self.gates = st, first_tokens, type_rows, gates
+        self.incs = [_Incremental(lib, s.decoder, store, dtype, flat, s.states, s.key_mask, st.B, st.beam, st.t_max, cu_stream)
+                     for s in streams]
+        self.hidden = [torch.empty((st.B * st.beam, s.states.size(-1)), dtype=dtype, device=s.states.device) for s in streams]
+
+    def states(self, i, rep):
+        """[B * rep, d] decoder states of step ``i`` (position i - 1)."""
+        st, rows = self.st, self.st.B * rep
+        ids, types = (self.first_tokens if i == 1 else st.tokens), self.type_rows[rep > 1]
+        out = None
+        for inc, hidden, gate in zip(self.incs, self.hidden, self.gates):
+            inc.step(i - 1, rows, rep, ids, types, st.slots[st.cur], hidden)
+            out = _mixed(out, hidden[:rows], gate)
+        return out
+
+    def finish(self):
+        """Raises if a one-launch decoder step was abandoned (bounded waits); synchronises, the outputs are read next anyway."""
+        for inc in reversed(self.incs):
+            inc.check()
+
+
+class _RecomputedSteps:
+    """Step provider of ``kv_cache=False``: every stream's decoder over the whole prefix at every step, the reference's literal
+    recomputation (src/seq_gen.py:146-188)."""
+
+    def __init__(self, streams, gates, st, type_rows):
+        self.streams, self.gates, self.st, self.type_rows = streams, gates, st, type_rows
+
+    def states(self, i, rep):
+        """[B * rep, d] decoder states of step ``i``: the last position of the prefix."""
+        prefix = self.st.hist[self.st.cur][:self.st.B * rep, :i].contiguous()
+        types = self.type_rows[rep > 1].unsqueeze(-1).expand(-1, i)
+        out = None
+        for s, gate in zip(self.streams, self.gates):
+            enc = s.states if rep == 1 else torch.repeat_interleave(s.states, rep, 0)
+            mask = s.key_mask if rep == 1 or s.key_mask is None else torch.repeat_interleave(s.key_mask, rep, 0)
+            last = s.decoder(encoder_states=enc, input_ids=prefix, encoder_attention_mask=mask,
+                             tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
+            out = _mixed(out, last, gate)
+        return out
+
+    def finish(self):
+        pass
 
 
 class BeamDecoder(nn.Module):
@@ -99,181 +196,105 @@ class BeamDecoder(nn.Module):
     def forward(self, src_inputs=None, src_sizes=None, first_tokens=None, src_mask=None, src_langs=None, tgt_langs=None,
                 pad_idx=None, max_len: int = None, unpad_output: bool = True, beam_width: int = None, images=None,
                 proposals=None, image_embed=None, objects=None):
-        tgt_langs, first_tokens, src_langs, src_mask = _un(tgt_langs), _un(first_tokens), _un(src_langs), _un(src_mask)
-        src_sizes, src_inputs, images, image_embed = _un(src_sizes), _un(src_inputs), _un(images), _un(image_embed)
-        proposals, objects = _un(proposals), _un(objects)
+        # ---- arguments
+        (src_inputs, src_sizes, first_tokens, src_mask, src_langs, tgt_langs, images, proposals, image_embed, objects) = map(
+            unwrap, (src_inputs, src_sizes, first_tokens, src_mask, src_langs, tgt_langs, images, proposals, image_embed, objects))
         model = self.seq2seq_model.module if hasattr(self.seq2seq_model, "module") else self.seq2seq_model
-        if beam_width is None:
-            beam_width = self.beam_width
+        beam = int(self.beam_width if beam_width is None else beam_width)
         if pad_idx is None:
             pad_idx = model.text_processor.pad_token_id()
         device = model._device
         if device.type != "cuda":
             raise L.ImtError("imagetranslate_amd: beam search needs the model on the GPU (no CPU fallback)")
-        batch_lang = int(tgt_langs[0])
-        if src_inputs is not None:
-            batch_size = src_inputs.size(0)
-        elif images is not None:
-            batch_size = images.size(0)
-        elif image_embed is not None:
-            batch_size = image_embed.size(0)
-        else:
+        given = [x for x in (src_inputs, images, image_embed) if x is not None]
+        if not given:
             raise ValueError("BeamDecoder needs src_inputs, images or image_embed")
-        if images is not None and max_len is None:
-            max_len = 512
+        B, batch_lang = given[0].size(0), int(tgt_langs[0])
+        eos, V = model.text_processor.sep_token_id(), model.config.vocab_size
+        max_len, max_lens_host, t_max = length_limits(
+            max_len, self.max_len_a, self.max_len_b, model.encoder.embeddings.position_embeddings.num_embeddings, B,
+            src_len=None if src_inputs is None else src_inputs.size(1), src_sizes=src_sizes, images=images is not None)
 
-        # ---- encoder side (once per search, :94-107)
-        enc_mask = None
-        obj_fc = img_states = None
-        if src_inputs is not None:
-            src_mask = src_mask.to(device)
-            src_langs_t = src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1))
-            encoder_states = model.encode(src_inputs, src_mask, src_langs_t)[0]
-            enc_mask = src_mask.to(torch.uint8).contiguous()
-            if images is not None:  # a source sentence AND an image (:105-106): the decoder also attends to the regions
-                if not hasattr(model, "multimodal_attention_gate"):
-                    raise ValueError("text + image beam search needs an ImageMassSeq2Seq (multimodal_attention_gate)")
-                if image_embed is not None:
-                    img_states = image_embed.to(device)
-                else:  # element 0 of the image head's output (the reference keeps the tuple and fails)
-                    img_states = model.image_model(images.to(device), model._imt_compute_dtype)[0]
-        else:
-            if image_embed is None:
-                encoder_states, obj_fc = model.encode(images=images.to(device), **({"objects": objects} if objects is not None else {}))
-            else:
-                encoder_states = image_embed.to(device)
-                if objects is not None and "obj_decoder" in model._modules:
-                    obj_fc = model.image_model.objects_forward(objects, model._imt_compute_dtype)
-        dtype = model._imt_compute_dtype
-        encoder_states = encoder_states.to(dtype).contiguous()
-        Tk = encoder_states.size(1)
-        if obj_fc is not None:
-            obj_fc = obj_fc.to(dtype).contiguous()
-        if img_states is not None:
-            if img_states.size(0) != batch_size:
-                raise ValueError("text + image beam search: %d images for %d sentences" % (img_states.size(0), batch_size))
-            img_states = img_states.to(dtype).contiguous()
-
-        eos = model.text_processor.sep_token_id()
-        V = model.config.vocab_size
-        max_pos = model.encoder.embeddings.position_embeddings.num_embeddings
-        max_len_func = lambda s: min(int(self.max_len_a * s + self.max_len_b), max_pos)
-        if max_len is None:
-            max_len = max_len_func(src_inputs.size(1))
-        if src_inputs is None:
-            max_lens_host = torch.LongTensor([max_len] * batch_size)
-        else:
-            max_lens_host = torch.LongTensor([max_len_func(int(x)) for x in src_sizes])
-        max_lens = max_lens_host.to(device)
-
-        decoder, output_layer = model._decoder_for(batch_lang), model._output_layer(batch_lang)
-
-        first_tokens = first_tokens.to(device=device, dtype=torch.int64).contiguous()
-        B, beam = batch_size, int(beam_width)
-        t_max = max(int(max_len), 2)
-        st = _BeamState(B, beam, t_max, V, device, self.kv_cache)
-        st.hist[0][:B, 0] = first_tokens
-        st.eos[0][:B] = (first_tokens == eos).to(torch.uint8)
-        if self.kv_cache:
-            st.slots[0][:B, 0] = torch.arange(B, dtype=torch.int32, device=device)
-        langs = tgt_langs.to(device=device, dtype=torch.int64)
-        type_rows = [langs.contiguous(), torch.repeat_interleave(langs, beam, 0).contiguous()]
-
-        obj_decoder = gate_param = None
-        if obj_fc is not None:
-            obj_decoder, gate_param = model._obj_decoder_for(batch_lang), model.multistream_attention_gate
-        elif img_states is not None:
-            # the second stream is the SAME decoder over the image regions, no key mask (:184-188); from here on it is handled
-            # like the object stream: `obj_fc` = the second stream's encoder side, `obj_decoder` the stack that reads it
-            obj_decoder, obj_fc, gate_param = decoder, img_states, model.multimodal_attention_gate
-        store = store_of(decoder).ensure()
+        # ---- encoder side, once per search
+        streams = self._encode(model, batch_lang, B, src_inputs, src_mask, src_langs, images, image_embed, objects)
+        dtype, output_layer = model._imt_compute_dtype, model._output_layer(batch_lang)
+        store = store_of(streams[0].decoder).ensure()
         flat = store.params_for(dtype)  # the whole buffer as well: the incremental decoders' descriptors point at it
-        W, bias, gate = store.views(dtype, output_layer.layer.weight, output_layer.layer.bias, gate_param, flat=flat)
-        if gate is not None:
-            gate = gate.view(-1)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        lib = L.load()
+        W, bias, *gates = store.views(dtype, output_layer.layer.weight, output_layer.layer.bias, *(s.gate for s in streams), flat=flat)
+        gates = [None if g is None else g.view(-1) for g in gates]
 
-        inc = inc_obj = None
+        # ---- search state and step provider
+        first_tokens = first_tokens.to(device=device, dtype=torch.int64).contiguous()
+        st = _BeamState(first_tokens, eos, beam, t_max, self.kv_cache)
+        langs = tgt_langs.to(device=device, dtype=torch.int64)
+        type_rows = [langs.contiguous(), torch.repeat_interleave(langs, beam, 0).contiguous()]  # [rep == 1, rep == beam]
         if self.kv_cache:
-            inc = _Incremental(lib, decoder, store, dtype, flat, encoder_states, enc_mask, B, beam, t_max, stream)
-            if obj_fc is not None:
-                inc_obj = _Incremental(lib, obj_decoder, store, dtype, flat, obj_fc, None, B, beam, t_max, stream)
+            steps = _CachedSteps(streams, gates, st, first_tokens, type_rows, store, dtype, flat)
+        else:
+            steps = _RecomputedSteps(streams, gates, st, type_rows)
         logits = O.alloc_rows(B * beam, V, torch.float32, device)  # leading dimension padded to 8 for odd vocabularies
-        hidden = torch.empty((B * beam, model.config.hidden_size), dtype=dtype, device=device)
-        hidden_obj = torch.empty_like(hidden) if inc_obj is not None else None
+        max_lens = torch.tensor(max_lens_host, dtype=torch.int64).to(device)
+        a = st.args  # the rest of what no step changes
+        a.V, a.logits, a.ld, a.max_lens = V, logits.data_ptr(), logits.stride(0), max_lens.data_ptr()
+        a.len_penalty_ratio, a.pad_idx, a.eos = float(self.len_penalty_ratio), int(pad_idx), int(eos)
 
-        n_cols = 1
-        done_at = None
-        if beam == 1 and bool((first_tokens == eos).all()):
-            done_at = 0
-        for i in range(1, max_len):
-            if done_at is not None:
-                break
-            rep = 1 if i == 1 else beam
-            rows = B * rep
-            cur, nxt = st.cur, st.cur ^ 1
-            if inc is not None:
-                ids = first_tokens if i == 1 else st.tokens
-                inc.step(i - 1, rows, rep, ids, type_rows[0 if rep == 1 else 1], st.slots[cur], hidden)
-                states = hidden[:rows]
-                if inc_obj is not None:
-                    inc_obj.step(i - 1, rows, rep, ids, type_rows[0 if rep == 1 else 1], st.slots[cur], hidden_obj)
-                    states = O.gated_mix(states, hidden_obj[:rows], gate)
-            else:
-                enc = encoder_states if rep == 1 else torch.repeat_interleave(encoder_states, rep, 0)
-                emask = None
-                if enc_mask is not None:
-                    emask = enc_mask if rep == 1 else torch.repeat_interleave(enc_mask, rep, 0)
-                prefix = st.hist[cur][:rows, :i].contiguous()
-                types = type_rows[0 if rep == 1 else 1].unsqueeze(-1).expand(-1, i)
-                states = decoder(encoder_states=enc, input_ids=prefix, encoder_attention_mask=emask,
-                                 tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
-                if obj_fc is not None:
-                    objs = obj_fc if rep == 1 else torch.repeat_interleave(obj_fc, rep, 0)
-                    obj_states = obj_decoder(encoder_states=objs, input_ids=prefix, encoder_attention_mask=None,
-                                             tgt_attention_mask=torch.ones_like(prefix), token_type_ids=types)[:, -1, :]
-                    states = O.gated_mix(states.contiguous(), obj_states.contiguous(), gate)
+        def project(states, rep):  # [B * rep, d] states -> logits[:B * rep]
             if model.use_proposals:
                 states = model.attend_proposal(states.contiguous(), proposals, pad_idx, rows_per_group=rep)
-            O.gemm(states.contiguous(), W, O.IMT_NT, bias=bias, out=logits[:rows])
+            O.gemm(states.contiguous(), W, O.IMT_NT, bias=bias, out=logits[:B * rep])
 
-            a = L.BeamArgs()
-            a.B, a.beam, a.rep, a.V, a.step, a.t_max = B, beam, rep, V, i, t_max
-            a.logits, a.ld = logits.data_ptr(), logits.stride(0)
-            a.scores_in, a.sizes_in, a.eos_in = st.scores[cur].data_ptr(), st.sizes[cur].data_ptr(), st.eos[cur].data_ptr()
-            a.max_lens, a.hist_in = max_lens.data_ptr(), st.hist[cur].data_ptr()
-            a.len_penalty_ratio, a.pad_idx, a.eos = float(self.len_penalty_ratio), int(pad_idx), int(eos)
-            a.cand_scores, a.cand_idx = st.cand_scores.data_ptr(), st.cand_idx.data_ptr()
-            a.scores_out, a.sizes_out, a.eos_out = st.scores[nxt].data_ptr(), st.sizes[nxt].data_ptr(), st.eos[nxt].data_ptr()
-            a.hist_out, a.parent_out, a.tokens_out = st.hist[nxt].data_ptr(), st.parent.data_ptr(), st.tokens.data_ptr()
-            if self.kv_cache:
-                a.slots_in, a.slots_out = st.slots[cur].data_ptr(), st.slots[nxt].data_ptr()
-            a.eos_count = st.eos_count.data_ptr()
-            O.beam_step(a)
-            st.cur = nxt
-            n_cols = i + 1
+        nothing_to_decode = beam == 1 and bool((first_tokens == eos).all())
+        n_cols = 1 if nothing_to_decode else self._search(steps, project, st, max_len)
+        steps.finish()
+        object_gate = getattr(model, "multistream_attention_gate", None)
+        if any(s.gate is object_gate for s in streams[1:]):  # an object stream: its labels may have been device tensors
+            model.image_model.check_object_labels(wait=True)  # the search has synchronised anyway
+
+        # ---- outputs
+        if unpad_output:
+            return get_outputs_until_eos(eos, st.best(n_cols), size_limit=max_lens_host)
+        return list(st.best(n_cols).cpu())
+
+    @staticmethod
+    def _encode(model, batch_lang, B, src_inputs, src_mask, src_langs, images, image_embed, objects):
+        """The encoder side of one search (src/seq_gen.py:93-106) as ``decoder_streams``: states in the compute dtype, the source
+        mask as uint8.  ``src_inputs`` with ``images``: text + image (``image_embed``, when given as well, replaces the image
+        head's output); ``src_inputs`` without ``images``: the text search, whatever ``image_embed`` is (:94)."""
+        device, dtype = model._device, model._imt_compute_dtype
+        ready = lambda t: None if t is None else t.to(device).to(dtype).contiguous()
+        if src_inputs is None:
+            if image_embed is None:
+                image, obj_fc = model.encode(images=images.to(device), **({"objects": objects} if objects is not None else {}))
+            else:
+                image, obj_fc = image_embed, None
+                if objects is not None and "obj_decoder" in model._modules:
+                    obj_fc = model.image_model.objects_forward(objects, dtype)
+            return decoder_streams(model, batch_lang, image=ready(image), objects=ready(obj_fc))
+        src_mask = src_mask.to(device)
+        text = model.encode(src_inputs, src_mask, src_langs.unsqueeze(-1).expand(-1, src_inputs.size(-1)))[0]
+        image = None
+        if images is not None:  # a source sentence AND an image (:105-106): the decoder also attends to the regions
+            if not hasattr(model, "multimodal_attention_gate"):
+                raise ValueError("text + image beam search needs an ImageMassSeq2Seq (multimodal_attention_gate)")
+            image = image_embed if image_embed is not None else model.image_model(images.to(device), dtype)[0]  # element 0, DESIGN.md
+            if image.size(0) != B:
+                raise ValueError("text + image beam search: %d images for %d sentences" % (image.size(0), B))
+        return decoder_streams(model, batch_lang, text=ready(text), text_mask=src_mask.to(torch.uint8).contiguous(), image=ready(image))
+
+    def _search(self, steps, project, st, max_len):
+        """The search loop: ``steps.states`` -> ``project`` -> ``imt_beam_step`` per step; ``st.args`` holds everything that no
+        step changes.  Returns the number of columns of the history that hold the result (1: no step ran)."""
+        for i in range(1, max_len):
+            rep = 1 if i == 1 else st.beam
+            project(steps.states(i, rep), rep)
+            O.beam_step(st.bind_step(rep, i))
+            st.cur ^= 1
             # stop condition (:134-136), looked at every `sync_every` steps; columns decoded past it are dropped
             if i % self.sync_every == 0 or i == max_len - 1:
-                full = (st.eos_count[1:i + 1] == B * beam).nonzero()
+                full = (st.eos_count[1:i + 1] == st.B * st.beam).nonzero()
                 if full.numel() > 0:
-                    done_at = int(full[0, 0]) + 1
-        if done_at is not None and done_at >= 1:
-            n_cols = min(n_cols, done_at + 1)
-        if inc_obj is not None:
-            inc_obj.check()
-        if inc is not None:
-            inc.check()
-        if obj_fc is not None and img_states is None:
-            model.image_model.check_object_labels(wait=True)  # device labels: the search synchronises here anyway   # raises if a one-launch decoder step was abandoned (bounded waits); one sync, the outputs are read next anyway
-        if n_cols == 1:   # no step ran (max_len <= 1, or beam 1 with every first token EOS): one row per sentence
-            outputs = st.hist[st.cur][:B, :1]
-        else:
-            outputs = st.hist[st.cur].view(B, beam, t_max)[:, 0, :n_cols]
-        if unpad_output:
-            return get_outputs_until_eos(eos, outputs, size_limit=max_lens_host)
-        outputs = outputs.cpu()
-        return [outputs[r] for r in range(outputs.size(0))]
+                    return int(full[0, 0]) + 2
+        return max(1, max_len)
 
 
 class _Incremental:

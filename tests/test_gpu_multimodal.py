@@ -127,17 +127,20 @@ def test_contrastive_kernel_against_fp64(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ model level
-def _pair(seed=0, d=128, heads=4, enc=2, dec=2, V=1000, double=True, sharpen=False, **kw):
+def _pair(seed=0, d=128, heads=4, enc=2, dec=2, V=1000, double=True, sharpen=False, lang_dec=False, **kw):
     from imagetranslate_amd.image_model import ImageMassSeq2Seq
     torch.manual_seed(seed)
     tp = R.SyntheticTextProcessor(V)
-    args = dict(lang_dec=False, enc_layer=enc, dec_layer=dec, embed_dim=d, intermediate_dim=4 * d, num_attention_heads=heads,
+    args = dict(lang_dec=lang_dec, enc_layer=enc, dec_layer=dec, embed_dim=d, intermediate_dim=4 * d, num_attention_heads=heads,
                 image_feat_dim=64, **kw)
     ref = M.MultimodalSeq2Seq(tp, **args).eval()
     with torch.no_grad():
         ref.multimodal_attention_gate.normal_(0.0, 1.0)   # away from its 0.1 fill: both streams matter, per column
         ref.encoder_attention_w.weight.mul_(3.0)          # pooling weights away from uniform
         ref.image_attention_w.weight.mul_(3.0)
+        if lang_dec:  # the per-language decoders start as copies of one another: language 0's must differ, so that running it shows
+            for lyr in ref.decoder[0].decoder.layer:
+                lyr.output.dense.weight.neg_()
     if sharpen:
         ref.load_state_dict(beam_state_dict(ref.state_dict()))
     ours = ImageMassSeq2Seq(tp, **args)
@@ -299,6 +302,7 @@ def test_bf16_fused_paths_against_torch_composition(cuda, monkeypatch):
     most 1.5 x as far from fp64 as the composition (the margin tests/test_gpu_decode_oracle.py gives the one-launch step);
     both distances go to profiles/multimodal_parity.json."""
     import imagetranslate_amd.image_model as IM
+    import imagetranslate_amd.seq2seq as S2S
     report = {}
     for branch in ("contrastive", "gated"):
         ref, ours = _pair(seed=2)
@@ -319,7 +323,7 @@ def test_bf16_fused_paths_against_torch_composition(cuda, monkeypatch):
             with monkeypatch.context() as mp:
                 if path == "torch_ops":
                     mp.setattr(IM, "_ContrastiveTailFn", _TorchTail)
-                    mp.setattr(IM, "gated_mix", _torch_gated_mix)
+                    mp.setattr(S2S, "gated_mix", _torch_gated_mix)   # where the decoder's stream loop looks it up
                 ours.zero_grad()
                 loss = ours.loss_fused(batch=batch, **kw)[0]
                 loss.backward()
@@ -354,11 +358,11 @@ def _search_inputs(B=4, S=10, seed=3):
         torch.randn(B, 49, 64, generator=g)
 
 
-@pytest.mark.parametrize("beam", [1, 3])
-def test_text_and_image_beam_search_fp32_matches_oracle(cuda, beam):
+@pytest.mark.parametrize("beam,lang_dec", [(1, False), (3, False), (1, True), (3, True)], ids=["1", "3", "1-lang_dec", "3-lang_dec"])
+def test_text_and_image_beam_search_fp32_matches_oracle(cuda, beam, lang_dec):
     from imagetranslate_amd.seq_gen import BeamDecoder
     from oracle import seq_gen as OG
-    ref, ours = _pair(seed=3, double=False, sharpen=True)
+    ref, ours = _pair(seed=3, double=False, sharpen=True, lang_dec=lang_dec)
     inp, images = _search_inputs()
     want = M.beam_search(ref, images, beam, max_len=16, **inp)
     text_only = OG.BeamDecoder(ref, beam_width=beam)(max_len=16, **inp)

@@ -287,21 +287,37 @@ def test_c3_size_with_objects_bf16_against_oracle(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ beam search
-@pytest.mark.parametrize("beam", [1, 3])
-def test_beam_search_fp32_matches_oracle(cuda, beam):
+# (beam, lang_dec, B, objects per image, detections): the first two rows are the long-standing cases; the lang_dec rows are the
+# toy size of an object-stream search through per-language decoders (decoder[1] and obj_decoder[1] must be the ones that run)
+BEAM_CASES = [(1, False, 4, 19, [19, 3, 0, 11]), (3, False, 4, 19, [19, 3, 0, 11]),
+              (1, True, 3, 5, [5, 2, 0]), (3, True, 3, 5, [5, 2, 0])]
+
+
+@pytest.mark.parametrize("beam,lang_dec,B,N,counts", BEAM_CASES, ids=["1", "3", "1-lang_dec", "3-lang_dec"])
+def test_beam_search_fp32_matches_oracle(cuda, beam, lang_dec, B, N, counts):
     from imagetranslate_amd.seq_gen import BeamDecoder
-    ref, ours = _pair(seed=3)
+    ref, ours = _pair(lang_dec, seed=3)
+    if lang_dec:  # the per-language stacks start as copies of one another: language 0's must differ, so that running them shows
+        with torch.no_grad():
+            for stack in (ref.decoder[0], ref.obj_decoder[0]):
+                for lyr in stack.decoder.layer:
+                    lyr.output.dense.weight.neg_()
     sd = beam_state_dict(ref.state_dict())
     ref.load_state_dict(sd)
     ours.load_state_dict(sd, strict=False)
-    b = _caption_batch(B=4, N=19, seed=8, counts=[19, 3, 0, 11])
-    kw = dict(first_tokens=torch.full((4,), 5, dtype=torch.long), tgt_langs=torch.ones(4, dtype=torch.long), pad_idx=0, max_len=14)
+    b = _caption_batch(B=B, N=N, seed=8, counts=counts)
+    kw = dict(first_tokens=torch.full((B,), 5, dtype=torch.long), tgt_langs=torch.ones(B, dtype=torch.long), pad_idx=0, max_len=14)
     want = beam_search(ref, b["images"], b["objects"], beam, **kw)
     no_obj = beam_search(ref, b["images"], None, beam, **kw)
     assert [w.tolist() for w in want] != [w.tolist() for w in no_obj], "the object stream must change the search"
     for kv in (True, False):
         got = BeamDecoder(ours, beam_width=beam, kv_cache=kv)(images=b["images"], objects=b["objects"], **kw)
         assert [g.tolist() for g in got] == [w.tolist() for w in want], "kv_cache=%s" % kv
+        # precomputed image embeddings together with objects= (the object head still runs): the same search
+        with torch.no_grad():
+            emb = ours.image_model(b["images"].cuda(), torch.float32)[0]
+        got = BeamDecoder(ours, beam_width=beam, kv_cache=kv)(image_embed=emb, objects=b["objects"], **kw)
+        assert [g.tolist() for g in got] == [w.tolist() for w in want], "image_embed=, kv_cache=%s" % kv
 
 
 def test_one_launch_step_with_objects_against_chain(cuda, monkeypatch):

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import CONFIGS, build_model, make_batch  # noqa: E402
 from imagetranslate_amd import hip_ops as O  # noqa: E402
 from imagetranslate_amd.param_store import store_of  # noqa: E402
-from imagetranslate_amd.seq2seq import _LogSoftmaxFn  # noqa: E402
+from imagetranslate_amd.seq2seq import DecoderStream, _LogSoftmaxFn  # noqa: E402
 
 
 def _timed(fns, calls, warmup=10):
@@ -64,7 +64,8 @@ def run_config(name, calls):
     with torch.no_grad():
         sel_idx, targets = model._selection(tgt, tmask)
         enc = model.encode(args[0], args[2], model._lang_grid(args[4], args[0].size(1), dev))[0]
-        rows = model._decode(enc, args[2], tgt, tmask, model._lang_grid(args[5], tgt.size(1), dev), 1, sel_idx=sel_idx).contiguous()
+        streams = [DecoderStream(model._decoder_for(1), enc, args[2], None)]
+        rows = model._decode(streams, tgt, tmask, model._lang_grid(args[5], tgt.size(1), dev), sel_idx=sel_idx).contiguous()
     counts = tmask[:, 1:].sum(1, dtype=torch.int64)
     offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=offsets[1:])
