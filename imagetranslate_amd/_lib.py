@@ -143,6 +143,19 @@ class BeamArgs(Structure):
     ]
 
 
+class SampleArgs(Structure):
+    _fields_ = [
+        ("B", c_int32), ("n", c_int32), ("rep", c_int32), ("V", c_int32), ("step", c_int32), ("t_max", c_int32),
+        ("logits", c_void_p), ("ld", c_int64),
+        ("scores_in", c_void_p), ("eos_in", c_void_p), ("max_lens", c_void_p), ("hist_in", c_void_p), ("slots_in", c_void_p),
+        ("temperature", c_float), ("topk", c_int32), ("seed", c_uint64),
+        ("pad_idx", c_int64), ("eos", c_int64),
+        ("scores_out", c_void_p), ("eos_out", c_void_p),
+        ("hist_out", c_void_p), ("slots_out", c_void_p), ("parent_out", c_void_p), ("tokens_out", c_void_p),
+        ("eos_count", c_void_p),
+    ]
+
+
 class MassArgs(Structure):
     _fields_ = [
         ("n_rows", c_int32), ("width", c_int32), ("recover_width", c_int32), ("n_special", c_int32), ("vocab", c_int32),
@@ -250,6 +263,7 @@ SIGNATURES = {
     "imt_decode_step": (c_int, [POINTER(StackDesc), POINTER(DecodeIO), _P, c_int64, _P]),
     "imt_decode_check": (c_int, [POINTER(StackDesc), c_int, _P, _P]),
     "imt_beam_step": (c_int, [POINTER(BeamArgs), _P]),
+    "imt_sample_step": (c_int, [POINTER(SampleArgs), _P]),
     "imt_select_plan": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "imt_mass_mask": (c_int, [POINTER(MassArgs), _P]),
     "imt_mass_unmask": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
@@ -265,7 +279,7 @@ class ImtError(RuntimeError):
 ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_row": ProfRow, "imt_attn_block": AttnBlock,
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
-               "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs}
+               "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs}
 
 
 def load():

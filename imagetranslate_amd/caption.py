@@ -1,7 +1,8 @@
 """Caption a directory of images with beam search -- counterpart of src/caption.py (``build_model`` ``:62-73``,
 ``build_data_loader`` ``:49-59``, ``caption_batch`` ``:32-46``; same flags).  The image directory holds pre-extracted
 region features (``features.pt``, dataset.RegionFeatures) in place of pixels: the CNN trunk is outside the hot path.
-With ``--obj`` the detector output stored beside them (``obj_feats`` / ``obj_boxes`` / ``obj_labels``) feeds the object stream."""
+With ``--obj`` the detector output stored beside them (``obj_feats`` / ``obj_boxes`` / ``obj_labels``) feeds the object stream.
+``--sampling`` (build extension) draws ``--nsamples`` N captions per image instead: sample k of image i is output line i*N + k."""
 import datetime
 from optparse import OptionParser
 
@@ -10,7 +11,7 @@ import torch
 from . import dataset
 from .image_model import ImageCaptioning
 from .seq2seq import Seq2Seq
-from .seq_gen import BeamDecoder
+from .seq_gen import BeamDecoder, add_sampling_options, sampling_kwargs
 
 
 def get_lm_option_parser():
@@ -24,14 +25,15 @@ def get_lm_option_parser():
         parser.add_option(flag, dest=dest, type=kind, default=default)
     for flag, dest in (("--fp16", "fp16"), ("--obj", "obj"), ("--fp32", "fp32")):
         parser.add_option(flag, action="store_true", dest=dest, default=False)
-    return parser
+    return add_sampling_options(parser)
 
 
 @torch.no_grad()
 def caption_batch(batch, generator, text_processor, max_len: int = 256):
     outputs = generator(first_tokens=batch["first_tokens"], images=batch["images"], tgt_langs=batch["tgt_langs"],
                         pad_idx=text_processor.pad_token_id(), max_len=max_len, objects=batch.get("objects"))
-    return [text_processor.decode(h[1:].tolist()) for h in outputs], batch["paths"]
+    per_image = len(outputs) // len(batch["paths"])  # sampling with nsamples > 1: image-major
+    return [text_processor.decode(h[1:].tolist()) for h in outputs], [p for p in batch["paths"] for _ in range(per_image)]
 
 
 def build_data(options, text_processor):
@@ -46,7 +48,7 @@ def build_model(options):
     model.set_compute_dtype(torch.float32 if options.fp32 else torch.bfloat16)
     model = model.cuda().eval()
     generator = BeamDecoder(model, beam_width=options.beam_width, max_len_a=options.max_len_a, max_len_b=options.max_len_b,
-                            len_penalty_ratio=options.len_penalty_ratio)
+                            len_penalty_ratio=options.len_penalty_ratio, **sampling_kwargs(options))
     return generator, model.text_processor
 
 

@@ -1,16 +1,10 @@
 // On-device batch construction for MASS (src/utils.py:41-82): span selection, the shifted
 // decoder input with its original positions, compaction of the hidden tokens and the 80/10/10 replacement -- integer
 // work, one workgroup per sentence, so a MASS step needs no per-token host loop and no host->device copy of masks.
-// Randomness is counter-based (mix32 of (seed, stream, index)), restated bit for bit by oracle/batch_oracle.py.
+// Randomness is counter-based (counter_uniform of common.hpp: mix32 of (seed, stream, index)), restated bit for bit by oracle/batch_oracle.py.
 #include "common.hpp"
 
 namespace {
-
-IMT_DEVICE float mass_uniform(uint64_t seed, uint32_t stream, uint32_t index) {  // [0, 1) with 24 bits
-  uint32_t h = mix32(index ^ (uint32_t)seed);
-  h = mix32(h + stream * 0x9e3779b9U + (uint32_t)(seed >> 32));
-  return (float)(h >> 8) * (1.0f / 16777216.0f);
-}
 
 __global__ __launch_bounds__(256) void mass_mask_kernel(imt_mass_args a) {
   __shared__ int s_first, s_len;
@@ -28,12 +22,12 @@ __global__ __launch_bounds__(256) void mass_mask_kernel(imt_mass_args a) {
       bound = (float)pad - prod;
     }
     const int hint = (int)ceilf(bound);
-    const float u0 = mass_uniform(a.seed, 0u, (uint32_t)row);
+    const float u0 = counter_uniform(a.seed, 0u, (uint32_t)row);
     int first;
     if (u0 > 0.8f) first = 1;
     else if (u0 > 0.6f) first = hint;
     else if (hint >= 2) {
-      first = 2 + (int)(mass_uniform(a.seed, 1u, (uint32_t)row) * (float)(hint - 1));
+      first = 2 + (int)(counter_uniform(a.seed, 1u, (uint32_t)row) * (float)(hint - 1));
       if (first > hint) first = hint;
     } else first = 2;
     s_first = first; s_len = span_len;
@@ -58,12 +52,12 @@ __global__ __launch_bounds__(256) void mass_mask_kernel(imt_mass_args a) {
     const int64_t orig = text[c];
     a.targets[off + k] = orig;
     const uint32_t idx = (uint32_t)(row * a.width + c);
-    const float u = mass_uniform(a.seed, 2u, idx);
+    const float u = counter_uniform(a.seed, 2u, idx);
     int64_t repl = orig;
     if (u < 0.8f) repl = a.mask_id;
     else if (u < 0.9f) {
       const int span = a.vocab - a.n_special;
-      int r = (int)(mass_uniform(a.seed, 3u, idx) * (float)span);
+      int r = (int)(counter_uniform(a.seed, 3u, idx) * (float)span);
       if (r >= span) r = span - 1;
       repl = a.n_special + r;
     }

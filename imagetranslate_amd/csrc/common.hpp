@@ -206,6 +206,16 @@ IMT_DEVICE float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// (score desc, index asc) ordering of the search kernels (decode.hip, sample.hip): a "better" than b
+IMT_DEVICE bool better(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+IMT_DEVICE void wave_best(float& s, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float so = __shfl_xor(s, o, 64);
+    const int io = __shfl_xor(i, o, 64);
+    if (better(so, io, s, i)) { s = so; i = io; }
+  }
+}
 
 // ---------------------------------------------------------------- math
 // exact-erf GELU (src/lm_config.py:7 "gelu" == F.gelu) evaluated with the Abramowitz-Stegun 7.1.26 rational form:
@@ -286,6 +296,13 @@ IMT_DEVICE float gelu_erf_grad(float z) {
 IMT_DEVICE uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
+}
+// counter-based uniform in [0, 1) with 24 bits from (seed, stream, index): the draws of imt_mass_mask (batch.hip) and
+// imt_sample_step (sample.hip), restated bit for bit by oracle/batch_oracle.counter_uniform
+IMT_DEVICE float counter_uniform(uint64_t seed, uint32_t stream, uint32_t index) {
+  uint32_t h = mix32(index ^ (uint32_t)seed);
+  h = mix32(h + stream * 0x9e3779b9U + (uint32_t)(seed >> 32));
+  return (float)(h >> 8) * (1.0f / 16777216.0f);
 }
 IMT_DEVICE uint32_t dropout_key(uint64_t seed) { return (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9e3779b9U); }
 // the 4 x 16 draws of block idx4 (= element index >> 2) as two words

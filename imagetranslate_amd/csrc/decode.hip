@@ -7,18 +7,7 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------ beam step
-// (score desc, index asc) ordering: a "better" than b
-IMT_DEVICE bool better(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
-
-IMT_DEVICE void wave_best(float& s, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float so = __shfl_xor(s, o, 64);
-    const int io = __shfl_xor(i, o, 64);
-    if (better(so, io, s, i)) { s = so; i = io; }
-  }
-}
-
+// (score desc, index asc) ordering: better() / wave_best() of common.hpp
 constexpr int BEAM_THREADS = 256;
 constexpr int MAX_BEAM = 32;
 

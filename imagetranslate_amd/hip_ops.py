@@ -819,6 +819,10 @@ def beam_step(args: "L.BeamArgs"):
     L.check(L.load().imt_beam_step(ctypes.byref(args), _stream()), "imt_beam_step")
 
 
+def sample_step(args: "L.SampleArgs"):
+    L.check(L.load().imt_sample_step(ctypes.byref(args), _stream()), "imt_sample_step")
+
+
 def select_plan(mask, ids, col0: int = 1, count=None):
     """(idx int32 [n], targets int64 [n]) of the positions with mask[b, col0 + t] set; ONE small kernel + one 4-byte
     device->host read (the row count shapes everything downstream, so this is the step's only synchronisation).

@@ -17,6 +17,9 @@ What differs is HOW a step is computed:
     (``:105-106``) give every step a second stream, mixed into the first through a sigmoid gate before the projection:
     ``decoder_streams`` says which stack reads what with which key mask.  With ``kv_cache`` each stream has an incremental
     decoder of its own (cross K/V, workspace, self cache; the slot table is shared).
+  * ``sampling=True`` (build extension, the reference only searches): the same loop with ``imt_sample_step`` in place of
+    ``imt_beam_step`` -- ``nsamples`` hypotheses per sentence, each extended by one token DRAWN from softmax(logits / temperature)
+    over the ``sampling_topk`` best tokens (0: the whole vocabulary); ``last_scores`` holds the model's own log-probabilities.
 Ties between equal scores (``torch.topk`` leaves them unspecified, and ``:194-196`` creates them on purpose) are
 broken towards the lowest flat index.  ``:216`` is taken as floor division (torch 1.4 semantics).
 """
@@ -87,6 +90,50 @@ class _BeamState:
         """The first hypothesis of every sentence, ``n_cols`` columns (1: no step ran, still one row per sentence)."""
         hist = self.hist[self.cur]
         return hist[:self.B, :1] if n_cols == 1 else hist.view(self.B, self.beam, self.t_max)[:, 0, :n_cols]
+
+
+class _SampleState(_BeamState):
+    """The same state with ``nsamples`` for the beam, driven by ``imt_sample_step``: ``args`` is a ``SampleArgs`` (the hypothesis
+    sizes and the candidate workspace of the beam step stay unused)."""
+
+    def __init__(self, first_tokens, eos, nsamples, t_max, use_slots, temperature, topk, seed):
+        super().__init__(first_tokens, eos, nsamples, t_max, use_slots)
+        beam_args, self.args = self.args, L.SampleArgs()
+        a = self.args
+        a.B, a.n, a.t_max = self.B, nsamples, t_max
+        a.parent_out, a.tokens_out, a.eos_count = beam_args.parent_out, beam_args.tokens_out, beam_args.eos_count
+        a.temperature, a.topk, a.seed = float(temperature), int(topk), int(seed)
+
+    def bind_step(self, rep, step):
+        a = self.args
+        a.rep, a.step = rep, step
+        a.scores_in, _, a.eos_in, a.hist_in, a.slots_in = self.sides[self.cur]
+        a.scores_out, _, a.eos_out, a.hist_out, a.slots_out = self.sides[self.cur ^ 1]
+        return a
+
+    def all_rows(self, n_cols):
+        """Every hypothesis, sentence-major (sample k of sentence b in row b * nsamples + k), ``n_cols`` columns."""
+        return self.hist[self.cur][:, :n_cols]
+
+
+_SEED_STRIDE = 0x9E3779B97F4A7C15  # search number c of a sampling decoder draws with seed + c * stride (mod 2^64)
+
+
+def add_sampling_options(parser):
+    """--sampling / --sampling-topk / --temperature / --nsamples / --seed of the generation entry points (optparse)."""
+    parser.add_option("--sampling", action="store_true", dest="sampling", default=False,
+                      help="draw from the model instead of searching it")
+    parser.add_option("--sampling-topk", dest="sampling_topk", type="int", default=0, help="draw among the K best tokens (0: all)")
+    parser.add_option("--temperature", dest="temperature", type="float", default=1.0)
+    parser.add_option("--nsamples", dest="nsamples", type="int", default=1, help="samples per input (output line i*N + k)")
+    parser.add_option("--seed", dest="seed", type="int", default=1234)
+    return parser
+
+
+def sampling_kwargs(options):
+    """The ``BeamDecoder`` keywords of ``add_sampling_options``' flags."""
+    return dict(sampling=options.sampling, sampling_topk=options.sampling_topk, temperature=options.temperature,
+                nsamples=options.nsamples, seed=options.seed)
 
 
 def length_limits(max_len, max_len_a, max_len_b, max_pos, batch_size, src_len=None, src_sizes=None, images=False):
@@ -177,7 +224,8 @@ class _RecomputedSteps:
 
 class BeamDecoder(nn.Module):
     def __init__(self, seq2seq_model, beam_width: int = 5, max_len_a: float = 1.1, max_len_b: int = 5,
-                 len_penalty_ratio: float = 0.8, *, kv_cache: bool = True, sync_every: int = 8):
+                 len_penalty_ratio: float = 0.8, *, kv_cache: bool = True, sync_every: int = 8, sampling: bool = False,
+                 sampling_topk: int = 0, temperature: float = 1.0, nsamples: int = 1, seed: int = 1234):
         super(BeamDecoder, self).__init__()
         self.seq2seq_model = seq2seq_model
         self.beam_width = beam_width
@@ -186,6 +234,15 @@ class BeamDecoder(nn.Module):
         self.len_penalty_ratio = len_penalty_ratio
         self.kv_cache = kv_cache
         self.sync_every = max(1, int(sync_every))
+        self.sampling, self.sampling_topk, self.temperature = bool(sampling), int(sampling_topk), float(temperature)
+        self.nsamples, self.seed = int(nsamples), int(seed)
+        if self.sampling:
+            if not 1 <= self.nsamples <= 32:
+                raise ValueError("nsamples must be in 1..32, got %d" % self.nsamples)
+            if not (0.0 < self.temperature < float("inf")):
+                raise ValueError("temperature must be positive and finite, got %r" % (temperature,))
+        self.searches = 0        # sampled searches run so far: each draws with a seed of its own
+        self.last_scores = None  # sampling: [B, nsamples] fp32 summed model log-probabilities of the last search (CPU)
 
     def len_penalty(self, lengths: torch.Tensor):
         """GNMT length penalty (https://arxiv.org/abs/1609.08144 section 7); the search itself evaluates it on device."""
@@ -201,6 +258,10 @@ class BeamDecoder(nn.Module):
             unwrap, (src_inputs, src_sizes, first_tokens, src_mask, src_langs, tgt_langs, images, proposals, image_embed, objects))
         model = self.seq2seq_model.module if hasattr(self.seq2seq_model, "module") else self.seq2seq_model
         beam = int(self.beam_width if beam_width is None else beam_width)
+        if self.sampling:
+            if beam_width is not None and int(beam_width) != 1:
+                raise ValueError("a sampling BeamDecoder has no beam: beam_width must be None or 1, got %r" % (beam_width,))
+            beam = self.nsamples  # the width of the search state
         if pad_idx is None:
             pad_idx = model.text_processor.pad_token_id()
         device = model._device
@@ -225,7 +286,15 @@ class BeamDecoder(nn.Module):
 
         # ---- search state and step provider
         first_tokens = first_tokens.to(device=device, dtype=torch.int64).contiguous()
-        st = _BeamState(first_tokens, eos, beam, t_max, self.kv_cache)
+        if self.sampling:
+            if B * beam * V >= 1 << 32:
+                raise ValueError("sampling: batch * nsamples * vocabulary = %d * %d * %d does not fit the 32-bit noise index"
+                                 % (B, beam, V))
+            st = _SampleState(first_tokens, eos, beam, t_max, self.kv_cache, self.temperature, self.sampling_topk,
+                              (self.seed + self.searches * _SEED_STRIDE) % (1 << 64))
+            self.searches += 1
+        else:
+            st = _BeamState(first_tokens, eos, beam, t_max, self.kv_cache)
         langs = tgt_langs.to(device=device, dtype=torch.int64)
         type_rows = [langs.contiguous(), torch.repeat_interleave(langs, beam, 0).contiguous()]  # [rep == 1, rep == beam]
         if self.kv_cache:
@@ -236,7 +305,9 @@ class BeamDecoder(nn.Module):
         max_lens = torch.tensor(max_lens_host, dtype=torch.int64).to(device)
         a = st.args  # the rest of what no step changes
         a.V, a.logits, a.ld, a.max_lens = V, logits.data_ptr(), logits.stride(0), max_lens.data_ptr()
-        a.len_penalty_ratio, a.pad_idx, a.eos = float(self.len_penalty_ratio), int(pad_idx), int(eos)
+        a.pad_idx, a.eos = int(pad_idx), int(eos)
+        if not self.sampling:
+            a.len_penalty_ratio = float(self.len_penalty_ratio)
 
         def project(states, rep):  # [B * rep, d] states -> logits[:B * rep]
             if model.use_proposals:
@@ -251,6 +322,13 @@ class BeamDecoder(nn.Module):
             model.image_model.check_object_labels(wait=True)  # the search has synchronised anyway
 
         # ---- outputs
+        if self.sampling:
+            self.last_scores = st.scores[st.cur].view(B, beam).cpu()
+            if beam > 1:  # every sample, sentence-major (a search without a step is a single sample per sentence: below)
+                rows = st.all_rows(n_cols) if n_cols > 1 else torch.repeat_interleave(st.best(1), beam, 0)  # (no step ran)
+                if unpad_output:
+                    return get_outputs_until_eos(eos, rows, size_limit=[m for m in max_lens_host for _ in range(beam)])
+                return list(rows.cpu())
         if unpad_output:
             return get_outputs_until_eos(eos, st.best(n_cols), size_limit=max_lens_host)
         return list(st.best(n_cols).cpu())
@@ -282,12 +360,13 @@ class BeamDecoder(nn.Module):
         return decoder_streams(model, batch_lang, text=ready(text), text_mask=src_mask.to(torch.uint8).contiguous(), image=ready(image))
 
     def _search(self, steps, project, st, max_len):
-        """The search loop: ``steps.states`` -> ``project`` -> ``imt_beam_step`` per step; ``st.args`` holds everything that no
-        step changes.  Returns the number of columns of the history that hold the result (1: no step ran)."""
+        """The search loop: ``steps.states`` -> ``project`` -> ``imt_beam_step`` (sampling: ``imt_sample_step``) per step; ``st.args``
+        holds everything that no step changes.  Returns the number of columns of the history that hold the result (1: no step ran)."""
+        advance = O.sample_step if self.sampling else O.beam_step
         for i in range(1, max_len):
             rep = 1 if i == 1 else st.beam
             project(steps.states(i, rep), rep)
-            O.beam_step(st.bind_step(rep, i))
+            advance(st.bind_step(rep, i))
             st.cur ^= 1
             # stop condition (:134-136), looked at every `sync_every` steps; columns decoded past it are dropped
             if i % self.sync_every == 0 or i == max_len - 1:

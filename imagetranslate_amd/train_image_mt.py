@@ -42,6 +42,9 @@ class ImageMTTrainer(Trainer):
         self.lex_dict = kwargs.get("lex_dict")  # --dict: the back-translation phase looks up proposals for what it generates
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
+        if kwargs.get("bt_sampling", False):  # sampled sources (--bt-sampling): one draw per sentence, this rank's own noise
+            self.bt_kw.update(beam_width=1, sampling=True, sampling_topk=kwargs.get("bt_topk", 0),
+                              temperature=kwargs.get("bt_temperature", 1.0), nsamples=1, seed=seed + rank)
 
     # one MT batch (src/train_image_mt.py:239-295)
     def mt_step(self, batch, accum: int = 1, loss_weight: float = 1.0):
@@ -122,11 +125,13 @@ class ImageMTTrainer(Trainer):
             self.generator = BeamDecoder(model, **self.bt_kw)
         was_training = model.training
         model.eval()
-        with torch.no_grad():
-            outs = self.generator(src_inputs=src, src_sizes=batch["pad_idx"], first_tokens=target_tags, src_langs=batch["langs"],
-                                  tgt_langs=dst_langs, pad_idx=pad, src_mask=src_mask, unpad_output=False,
-                                  beam_width=self.bt_kw["beam_width"], proposals=self._proposals(batch))
-        model.train(was_training)
+        try:
+            with torch.no_grad():
+                outs = self.generator(src_inputs=src, src_sizes=batch["pad_idx"], first_tokens=target_tags, src_langs=batch["langs"],
+                                      tgt_langs=dst_langs, pad_idx=pad, src_mask=src_mask, unpad_output=False,
+                                      beam_width=self.bt_kw["beam_width"], proposals=self._proposals(batch))
+        finally:  # a failing search must not leave the model in eval mode
+            model.train(was_training)
         outs = [o.cpu() for o in outs]
         translations = pad_sequence(outs, batch_first=True, padding_value=pad)
         translation_proposals = None
@@ -202,8 +207,14 @@ class ImageMTTrainer(Trainer):
 
 def get_option_parser():
     """The reference's flags (src/option_parser.py:37-88: --train_mt, --dev_mt, --mass_train, --acc, --fp16, --beam ...)
-    plus the build's additions (option_parser.py)."""
-    return get_img_options_parser()
+    plus the build's additions (option_parser.py), and on top of them this entry point's own: --bt-sampling / --bt-topk /
+    --bt-temperature draw the back-translation phase's sources from the model instead of searching for them."""
+    parser = get_img_options_parser()
+    parser.add_option("--bt-sampling", action="store_true", dest="bt_sampling", default=False,
+                      help="back-translation: sample the sources (seed: --seed + rank)")
+    parser.add_option("--bt-topk", dest="bt_topk", type="int", default=0, help="sample among the K best tokens (0: all)")
+    parser.add_option("--bt-temperature", dest="bt_temperature", type="float", default=1.0)
+    return parser
 
 
 def load_image_data(options, tp, lex_dict=None):
@@ -254,7 +265,8 @@ def train(options):
     trainer = ImageMTTrainer(model, mask_prob=options.mask_prob, clip=options.clip, optimizer=optimizer, rank=rank, world_size=world,
                              seed=options.seed, bt_beam_width=options.bt_beam_width, max_len_a=options.max_len_a,
                              max_len_b=options.max_len_b, len_penalty_ratio=options.len_penalty_ratio, mm_mode=options.mm_mode,
-                             lex_dict=lex_dict)
+                             lex_dict=lex_dict, bt_sampling=getattr(options, "bt_sampling", False),
+                             bt_topk=getattr(options, "bt_topk", 0), bt_temperature=getattr(options, "bt_temperature", 1.0))
     pad = tp.pad_token_id()
     kw = dict(max_batch_capacity=options.total_capacity, max_batch=options.batch, pad_idx=pad, max_seq_len=options.max_seq_len,
               ngpu=1, lex_dict=lex_dict)

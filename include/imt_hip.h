@@ -47,7 +47,7 @@ const char* imt_last_error(void);
  * launches (2*M*N*K per GEMM; minimal operand traffic for the HBM-bound kernels).  Off by default. */
 /* sizeof() of the argument structures below as THIS library was compiled, by name ("imt_gemm_args", "imt_attn_args",
  * "imt_prof_row", "imt_attn_block", "imt_layer_desc", "imt_stack_desc", "imt_stack_io", "imt_attn_decode_args",
- * "imt_decode_io", "imt_beam_args", "imt_mass_args", "imt_score_args"); -1 for an unknown name.  A binding checks its own layout against it
+ * "imt_decode_io", "imt_beam_args", "imt_mass_args", "imt_score_args", "imt_sample_args"); -1 for an unknown name.  A binding checks its own layout against it
  * once at load time (imagetranslate_amd/_lib.py does): a stale binding then fails loudly instead of passing shifted fields. */
 int imt_abi_sizeof(const char* struct_name);
 
@@ -681,6 +681,42 @@ typedef struct imt_beam_args {
   int32_t* eos_count;              /* [t_max] (pre-zeroed by the caller) or NULL */
 } imt_beam_args;
 int imt_beam_step(const imt_beam_args* a, void* stream);
+
+/* One SAMPLING step on device: the counterpart of imt_beam_step for drawing from the model instead of searching it (the
+ * reference has no such mode).  Output row r' = b*n + k extends input row p = b*rep + (rep == 1 ? 0 : k): every hypothesis
+ * keeps its own parent, n samples per sentence run side by side.  With x = logits[p, :V]:
+ *   masked rows   eos_in[p], or step > 1 and max_lens[b] < step + 1 (the rule of imt_beam_step): token pad_idx, score unchanged,
+ *                 eos_out = eos_in[p];
+ *   kept set K    the first `topk` indices by (x descending, index ascending) -- ties at the k-th place go to the lowest
+ *                 indices -- or all of [0, V) when topk <= 0 or topk >= V;
+ *   noise         u(v) = max(counter_uniform(seed, stream = step, index = r'*V + v), 2^-25) (the generator of imt_mass_mask,
+ *                 indexed by the OUTPUT row: the n children of one parent at step 1 draw differently), g(v) = -log(-log(u(v)));
+ *   token         argmax over v in K of x[v] / temperature + g(v) by (value descending, index ascending): Gumbel-max, an
+ *                 exact draw from softmax(x / temperature) restricted to K;
+ *   score         scores_in[p] + x[token] - logsumexp(x): the MODEL's log-probability (temperature 1, whole vocabulary);
+ *   bookkeeping   history, eos_out, slots_out, parent_out, tokens_out, eos_count[step] as in imt_beam_step.
+ * Deterministic: no floating-point atomics, nothing crosses workgroups; two calls on the same input give the same bits. */
+typedef struct imt_sample_args {
+  int32_t B, n, rep, V;            /* n samples per sentence (1..32); rep = 1 (only at step 1) or n */
+  int32_t step, t_max;
+  const float* logits; int64_t ld; /* [B*rep, V] fp32, rows ld apart; columns [V, ld) are never read */
+  const float* scores_in;          /* [B*rep] */
+  const uint8_t* eos_in;           /* [B*rep] */
+  const int64_t* max_lens;         /* [B] */
+  const int64_t* hist_in;          /* [B*rep, t_max] */
+  const int32_t* slots_in;         /* [B*rep, t_max] or NULL */
+  float temperature;               /* > 0, finite */
+  int32_t topk;                    /* <= 0 or >= V: the whole vocabulary */
+  uint64_t seed;
+  int64_t pad_idx, eos;
+  float* scores_out; uint8_t* eos_out; /* [B*n] */
+  int64_t* hist_out;               /* [B*n, t_max] */
+  int32_t* slots_out;              /* [B*n, t_max] or NULL */
+  int32_t* parent_out;             /* [B*n] */
+  int64_t* tokens_out;             /* [B*n] */
+  int32_t* eos_count;              /* [t_max] (pre-zeroed by the caller) or NULL */
+} imt_sample_args;
+int imt_sample_step(const imt_sample_args* a, void* stream);
 
 /* ------------------------------------------------------------------ MASS batch construction on device
  * mass_mask / mass_unmask of src/utils.py:41-82.  Per sentence (row): a contiguous span of int(pad_index/2) tokens
