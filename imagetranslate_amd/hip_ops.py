@@ -462,7 +462,8 @@ def scaled_sum(x, scale: float):
     """scale * x.sum() as a 0-d fp32 tensor (one small deterministic kernel)."""
     _req_cuda(x)
     out = torch.empty((), device=x.device, dtype=torch.float32)
-    L.check(L.load().imt_scaled_sum(_p(x), x.numel(), float(scale), _p(out), _stream()), "imt_scaled_sum")
+    src = x if x.numel() else out  # an empty tensor has no address (the C side refuses NULL); with n = 0 nothing is read
+    L.check(L.load().imt_scaled_sum(_p(src), x.numel(), float(scale), _p(out), _stream()), "imt_scaled_sum")
     return out
 
 

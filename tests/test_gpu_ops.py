@@ -3,6 +3,8 @@
 fp32 mode: 1e-4 relative (north_star tolerance).  bf16 mode: inputs are rounded to bf16 first and the reference
 is computed in fp32 from the rounded inputs; tolerance 2.5e-2 relative to the output's max magnitude.
 All calls go through the C ABI (imagetranslate_amd.hip_ops -> ctypes -> libimt_hip.so).
+Each row kernel (loss, optimizer, embedding, LayerNorm, column sum) runs here at one convenient shape; the sizes at which their
+strided loops wrap, their vector tails begin and their dispatch changes kernel are in tests/test_gpu_row_edges.py.
 """
 import math
 
