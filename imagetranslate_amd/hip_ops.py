@@ -262,13 +262,21 @@ def _attn_args(q, k, v, B, H, Tq, Tk, head_dim, key_mask, query_mask, mask3d, ca
 
 
 def attention_fwd(q, k, v, B, H, Tq, Tk, head_dim, key_mask=None, query_mask=None, mask3d=None, causal=False,
-                  scale=None, dropout_p=0.0, dropout_seed=0):
-    """q: [B*Tq, >=H*head_dim] row-major view (heads merged), k/v: [B*Tk, ...]; masks uint8."""
-    _req_cuda(q, k, v, key_mask, query_mask, mask3d)
+                  scale=None, dropout_p=0.0, dropout_seed=0, o=None, lse=None):
+    """q: [B*Tq, >=H*head_dim] row-major view (heads merged), k/v: [B*Tk, ...]; masks uint8.  ``o`` ([B*Tq, H*head_dim]
+    row-major view of q's dtype, any 16-byte-multiple leading dimension) and ``lse`` (contiguous fp32 [B, H, Tq]) receive
+    the results when given, as dq / dk / dv do in attention_bwd."""
+    _req_cuda(q, k, v, key_mask, query_mask, mask3d, o, lse)
     a = _attn_args(q, k, v, B, H, Tq, Tk, head_dim, key_mask, query_mask, mask3d, causal, scale, dropout_p, dropout_seed)
-    o = torch.empty((B * Tq, H * head_dim), device=q.device, dtype=q.dtype)
-    lse = torch.empty((B, H, Tq), device=q.device, dtype=torch.float32)
-    a.O, a.ldo, a.lse = o.data_ptr(), o.stride(0), lse.data_ptr()
+    if o is None:
+        o = torch.empty((B * Tq, H * head_dim), device=q.device, dtype=q.dtype)
+    else:
+        assert o.dtype == q.dtype and tuple(o.shape) == (B * Tq, H * head_dim), "attention_fwd: o must be [B*Tq, H*head_dim] of q's dtype"
+    if lse is None:
+        lse = torch.empty((B, H, Tq), device=q.device, dtype=torch.float32)
+    else:
+        assert lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, Tq) and lse.is_contiguous(), "attention_fwd: lse must be contiguous fp32 [B, H, Tq]"
+    a.O, a.ldo, a.lse = o.data_ptr(), _rowmajor(o), lse.data_ptr()
     L.check(L.load().imt_attention_fwd(ctypes.byref(a), _stream()), "imt_attention_fwd")
     return o, lse
 
