@@ -4,7 +4,8 @@ MT batches as a second task whose loss is weighted by ``--mtlw`` (``:83``); grad
 runs after every backward and the optimizer steps every ``--acc`` micro-steps (``:91-97``).  The model step is the HIP
 path (``ImageCaptioning.loss_fused``); when features.pt carries detector output (``obj_*`` keys, dataset.RegionFeatures)
 and the model has its object stream (no ``--no-obj``), the batches' ``objects`` train it.  BLEU evaluation needs sacrebleu (absent): the dev set is scored by its loss and,
-with ``eval_captions``, decoded with beam search."""
+with ``eval_captions``, decoded with beam search.  ``--save-state`` adds ``train_state.pt`` (checkpoint.py) to ``<model>.latest`` every
+``--save-steps`` steps; ``--resume DIR`` continues the run saved there (trainer.py)."""
 import datetime
 import os
 import random
@@ -18,7 +19,8 @@ from .seq2seq import Seq2Seq
 from .seq_gen import BeamDecoder, get_outputs_until_eos
 from .textprocessor import TextProcessor
 from .train_image_mt import ImageMTTrainer
-from .trainer import Trainer, batches_from, init_distributed, load_lex_dict, reject_off_path, use_lex_dict
+from .trainer import (Trainer, add_resume_options, batches_from, init_distributed, load_lex_dict, reject_off_path, resume_dir_of,
+                      use_lex_dict)
 from .utils import build_optimizer
 
 
@@ -74,6 +76,9 @@ class ImageCaptionTrainer(ImageMTTrainer):
     def train_epoch(self, img_data=None, mt_data=None, img_dev_data=None, mt_dev_data=None, step: int = 0,
                     max_step: int = 300000, save_path: str = None, accum: int = 1, mtl_weight: float = 0.1,
                     log_every: int = 50, eval_every: int = 5000, **kwargs):
+        self.track_dataset(img_data)
+        self.track_dataset(img_dev_data)  # (its negatives are drawn when a batch is read: the dev loss continues its stream too)
+        start = self.take_resume_pos()
         order = Trainer.epoch_order(self, [("img", len(img_data) if img_data is not None else 0), ("mt", len(mt_data or []))])
 
         def step_fn(kind, i, step):
@@ -86,7 +91,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
                 self._validate(img_dev_data, mt_dev_data, save_path)
 
         return self.run_epoch(order, step_fn, step=step, max_step=max_step, log_every=log_every, after_step=after_step,
-                              skip_empty=True)  # a caption batch without a target token (caption_step) is no step of one process
+                              start=start, skip_empty=True)  # a caption batch without a target token (caption_step) is no step of one process
 
     log_line = Trainer.log_line  # the reference's "Epoch Step: ..." line, not ImageMTTrainer's
 
@@ -101,8 +106,9 @@ class ImageCaptionTrainer(ImageMTTrainer):
             if self.rank == 0:
                 print(datetime.datetime.now(), "MT dev loss %.4f" % mt, flush=True)
             score = mt if score is None else score
+        if save_path:
+            self.save_latest(save_path)
         if self.rank == 0 and save_path:
-            self.model.save(save_path + ".latest")
             if score is not None and score < self.best_loss:
                 self.model.save(save_path)
         if score is not None:
@@ -111,6 +117,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
     @staticmethod
     def train(options):
         reject_off_path(options, lm_supported=True, dict_supported=True)
+        resume = resume_dir_of(options)  # --resume DIR: the model is built from DIR as --pretrained builds it
         rank, world = init_distributed()
         random.seed(options.seed)
         torch.manual_seed(options.seed)
@@ -119,8 +126,8 @@ class ImageCaptionTrainer(ImageMTTrainer):
         tp = TextProcessor(options.tokenizer_path)
         assert tp.pad_token_id() == 0
         lex_dict = load_lex_dict(options)
-        if options.pretrained_path is not None:
-            caption_model = Seq2Seq.load(ImageCaptioning, options.pretrained_path, tok_dir=options.tokenizer_path,
+        if resume or options.pretrained_path is not None:
+            caption_model = Seq2Seq.load(ImageCaptioning, resume or options.pretrained_path, tok_dir=options.tokenizer_path,
                                          use_obj=not options.no_obj)
         else:
             caption_model = ImageCaptioning(text_processor=tp, tie_embed=options.tie_embed, resnet_depth=options.resnet_depth,
@@ -156,12 +163,12 @@ class ImageCaptionTrainer(ImageMTTrainer):
         mt_dev = batches_from(options.mt_dev_path, **mt_kw) or None
         if rank == 0:
             print("image batches", len(img_train), "MT batches", len(mt_train or []), flush=True)
-        step, epoch = 0, 1
-        while options.step > 0 and step < options.step and epoch <= options.num_epochs:
+        step = trainer.begin_run(options, resume)
+        while options.step > 0 and step < options.step and trainer.epochs_begun < options.num_epochs:
             step = trainer.train_epoch(img_data=img_train, mt_data=mt_train, img_dev_data=img_dev, mt_dev_data=mt_dev, step=step,
                                        max_step=options.step, save_path=options.model_path, accum=options.accum,
                                        mtl_weight=options.mtl_weight, log_every=options.log_steps, eval_every=options.eval_steps)
-            epoch += 1
+        trainer.finish_snapshots()
         trainer._validate(img_dev, mt_dev, options.model_path)
         if rank == 0 and options.model_path and not os.path.exists(os.path.join(options.model_path, "mt_model.state_dict")):
             caption_model.save(options.model_path)
@@ -169,7 +176,7 @@ class ImageCaptionTrainer(ImageMTTrainer):
 
 
 def main(argv=None):
-    options, _ = get_img_options_parser().parse_args(argv)
+    options, _ = add_resume_options(get_img_options_parser()).parse_args(argv)
     ImageCaptionTrainer.train(options)
     print("Finished Training!")
 

@@ -6,7 +6,10 @@ Round 3 adds the back-translation phase (``--fstep`` / ``--langs`` / ``--bt-beam
 beam search, no gradient) and trained on as (translation -> original).  ``--image DIR`` with the caption file of ``--train`` adds
 image-caption batches (``:202-237``): per batch ``--mmode`` picks the masked-caption step (the gated text + image branch) or the
 contrastive step; back-translation over image batches is not built and refused.  What the reference trainer does around the step that needs
-absent packages (apex, sacrebleu, the torchvision image pipeline) is left out; the model step itself is the HIP path."""
+absent packages (apex, sacrebleu, the torchvision image pipeline) is left out; the model step itself is the HIP path.
+``--save-state`` writes ``<model>.latest/`` (the model's files, then ``train_state.pt``: checkpoint.py) every ``--save-steps`` steps and at
+the end; ``--resume DIR`` builds the model from DIR, restores weights, Adam moments, counters, phase and random streams, and goes on
+where the run stopped -- inside the back-translation phase too, without a second schedule reset.  ``--step`` / ``--fstep`` stay totals."""
 import datetime
 import os
 import random
@@ -19,7 +22,8 @@ from .image_model import ImageMassSeq2Seq
 from .option_parser import get_img_options_parser
 from .parallel import train_step
 from .textprocessor import TextProcessor
-from .trainer import LossMeter, Trainer, batches_from, init_distributed, load_lex_dict, reject_off_path, use_lex_dict  # noqa: F401
+from .trainer import (LossMeter, Trainer, add_resume_options, batches_from, init_distributed, load_lex_dict,  # noqa: F401
+                      reject_off_path, resume_dir_of, use_lex_dict)
 from .utils import build_optimizer, mass_mask_device
 
 
@@ -39,6 +43,10 @@ class ImageMTTrainer(Trainer):
         self._img_rng = random.Random((seed + 2) * 104729 + rank)
         self.image_steps, self.last_image_step = 0, None  # image batches consumed; (kind, loss) of the last one
         self.generator = None  # BeamDecoder of the back-translation phase (built on first use)
+        self._pending_searches = None  # generator.searches of a loaded snapshot, until the generator is built
+        # "train", or "bt" once the back-translation phase has begun; the step count and the epoch count at which the phase began
+        # (its bound is phase_start_step + --fstep) and the bound it ran under
+        self.phase, self.phase_start_step, self.phase_epoch0, self.phase_bound = "train", 0, 0, 0
         self.lex_dict = kwargs.get("lex_dict")  # --dict: the back-translation phase looks up proposals for what it generates
         self.bt_kw = dict(beam_width=kwargs.get("bt_beam_width", 1), max_len_a=kwargs.get("max_len_a", 1.3),
                           max_len_b=kwargs.get("max_len_b", 5), len_penalty_ratio=kwargs.get("len_penalty_ratio", 0.8))
@@ -123,6 +131,8 @@ class ImageMTTrainer(Trainer):
         dst_langs = torch.LongTensor([tp.languages[tp.id2token(lang_directions[l])] for l in first])
         if self.generator is None:
             self.generator = BeamDecoder(model, **self.bt_kw)
+            if self._pending_searches is not None:  # a resumed run's sampled sources continue the saved stream of seeds
+                self.generator.searches, self._pending_searches = self._pending_searches, None
         was_training = model.training
         model.eval()
         try:
@@ -165,6 +175,43 @@ class ImageMTTrainer(Trainer):
             src_inputs=batch["src_texts"], tgt_inputs=batch["dst_texts"], src_langs=batch["src_langs"],
             tgt_langs=batch["dst_langs"], proposals=self._proposals(batch)))
 
+    # ------------------------------------------------------------------ state that travels (checkpoint.py)
+    def begin_phase(self, phase: str, bound: int):
+        """The phase that starts now, at this step and epoch count, and runs until ``bound`` steps."""
+        self.drop_resume_pos()  # (a snapshot taken on the last step of the phase before: its epoch is not entered again)
+        self.phase, self.phase_start_step, self.phase_epoch0, self.phase_bound = phase, int(self.step), int(self.epoch), int(bound)
+
+    def rank_state(self):
+        from .trainer import pack_random_state
+        out = super().rank_state()
+        out["mass_rng"] = pack_random_state(self._mass_rng.getstate())
+        out["img_rng"] = pack_random_state(self._img_rng.getstate())
+        out["searches"] = self._pending_searches if self.generator is None else int(self.generator.searches)
+        return out
+
+    def load_rank_state(self, state):
+        from .trainer import unpack_random_state
+        super().load_rank_state(state)
+        self._mass_rng.setstate(unpack_random_state(state["mass_rng"]))
+        self._img_rng.setstate(unpack_random_state(state["img_rng"]))
+        if state.get("searches") is not None:
+            if self.generator is None:
+                self._pending_searches = int(state["searches"])
+            else:
+                self.generator.searches = int(state["searches"])
+
+    def state_dict(self):
+        out = super().state_dict()
+        out.update(image_steps=int(self.image_steps), phase=self.phase, phase_start_step=int(self.phase_start_step),
+                   phase_epoch0=int(self.phase_epoch0), phase_bound=int(self.phase_bound))
+        return out
+
+    def load_state_dict(self, state):
+        super().load_state_dict(state)
+        self.image_steps = int(state.get("image_steps", 0))
+        self.phase, self.phase_bound = str(state.get("phase", "train")), int(state.get("phase_bound", 0))
+        self.phase_start_step, self.phase_epoch0 = int(state.get("phase_start_step", 0)), int(state.get("phase_epoch0", 0))
+
     def epoch_order(self, n_mt: int, n_mass: int, n_img: int = 0):
         """``Trainer.epoch_order`` over this trainer's kinds, concatenated in the order mt, mass, img."""
         return super().epoch_order([("mt", n_mt), ("mass", n_mass), ("img", n_img)])
@@ -175,6 +222,8 @@ class ImageMTTrainer(Trainer):
         if fine_tune and img_data is not None and len(img_data) > 0:
             raise NotImplementedError("back-translation over image batches (src/train_image_mt.py:108-198 with is_img_batch) "
                                       "is not built")
+        self.track_dataset(img_data)
+        start = self.take_resume_pos()
         order = self.epoch_order(len(mt_data or []), len(mass_data or []), len(img_data) if img_data is not None else 0)
 
         def step_fn(kind, i, step):  # (the contrastive image step reports 0 tokens and still counts as a step)
@@ -190,7 +239,7 @@ class ImageMTTrainer(Trainer):
             if dev_data is not None and step % eval_every == 0:
                 self.validate_and_save(dev_data, save_path)
 
-        return self.run_epoch(order, step_fn, step=step, max_step=max_step, log_every=log_every, after_step=after_step)
+        return self.run_epoch(order, step_fn, step=step, max_step=max_step, log_every=log_every, after_step=after_step, start=start)
 
     def log_line(self, step, mean, count, secs):
         return "step %d loss %.4f tokens/s %.0f lr %.2e" % (step, mean, count / max(secs, 1e-9), self.optimizer.param_groups[0]["lr"])
@@ -214,7 +263,7 @@ def get_option_parser():
                       help="back-translation: sample the sources (seed: --seed + rank)")
     parser.add_option("--bt-topk", dest="bt_topk", type="int", default=0, help="sample among the K best tokens (0: all)")
     parser.add_option("--bt-temperature", dest="bt_temperature", type="float", default=1.0)
-    return parser
+    return add_resume_options(parser)
 
 
 def load_image_data(options, tp, lex_dict=None):
@@ -235,8 +284,35 @@ def load_image_data(options, tp, lex_dict=None):
                                        neg_seed=options.seed, lex_dict=lex_dict)
 
 
+def run_phases(trainer, options, step, mt_train, mass_train, mt_dev=None, img_train=None, lang_directions=None):
+    """The two phases of ``train`` from ``step`` on -- a fresh run's 0, or where a loaded snapshot stands (``trainer.phase``,
+    ``epoch``, ``epoch_pos``): --step ordinary steps, then --fstep back-translation steps.  Returns the step count."""
+    optimizer = trainer.optimizer
+    if trainer.phase == "train":
+        trainer.phase_bound = options.step  # --step is a total: a resumed run stops where the uninterrupted one would
+    while trainer.phase == "train" and step < options.step and trainer.epochs_begun - trainer.phase_epoch0 < options.num_epochs:
+        step = trainer.train_epoch(mt_data=mt_train, mass_data=mass_train, dev_data=mt_dev, step=step, max_step=options.step,
+                                   save_path=options.model_path, log_every=options.log_steps, eval_every=options.eval_steps,
+                                   accum=options.accum, img_data=img_train)
+    # back-translation phase (src/train_image_mt.py:509-533): optimizer schedule reset, then --fstep more steps in which the
+    # monolingual batches are back-translated.  The reference's flag default is 125000 steps; here the phase runs only when a
+    # language pair is given (--langs), which is what makes it well-defined.
+    if lang_directions is not None and options.finetune_step > 0 and mass_train:
+        if trainer.phase != "bt":  # (a run resumed inside this phase goes on with its schedule: no second reset)
+            optimizer.reset()
+            trainer.begin_phase("bt", step + options.finetune_step)
+        total = trainer.phase_bound = trainer.phase_start_step + options.finetune_step
+        while step < total and trainer.epochs_begun - trainer.phase_epoch0 < options.num_epochs:
+            step = trainer.train_epoch(mt_data=None if options.ignore_mt_mass else mt_train, mass_data=mass_train, dev_data=mt_dev,
+                                       step=step, max_step=total, save_path=options.model_path, log_every=options.log_steps,
+                                       eval_every=options.eval_steps, accum=options.accum, fine_tune=True,
+                                       lang_directions=lang_directions)
+    return step
+
+
 def train(options):
     reject_off_path(options, dict_supported=True)
+    resume = resume_dir_of(options)  # --resume DIR: the model is built from DIR as --pretrained builds it
     if getattr(options, "image_dir", "") and len([l for l in (options.bt_langs or "").split(",") if l.strip()]) >= 2 \
             and options.finetune_step > 0:
         raise NotImplementedError("--image with --langs / --fstep: back-translation over image batches (src/train_image_mt.py:108-198 "
@@ -249,8 +325,8 @@ def train(options):
     img_train = load_image_data(options, tp, lex_dict)  # before the model is built: a missing features.pt fails at once
     if img_train is not None and world > 1:
         raise NotImplementedError("--image under data parallelism is not built (ImageMTTrainer.image_step)")
-    if options.pretrained_path:
-        model = ImageMassSeq2Seq.load(ImageMassSeq2Seq, options.pretrained_path, tok_dir=options.tokenizer_path)
+    if resume or options.pretrained_path:
+        model = ImageMassSeq2Seq.load(ImageMassSeq2Seq, resume or options.pretrained_path, tok_dir=options.tokenizer_path)
     else:
         model = ImageMassSeq2Seq(text_processor=tp, lang_dec=options.lang_decoder, tie_embed=options.tie_embed,
                                  use_proposals=lex_dict is not None,
@@ -276,27 +352,9 @@ def train(options):
     if rank == 0:
         print("MT batches", len(mt_train), "MASS batches", len(mass_train), "image batches", len(img_train or []),
               "dev batches", len(mt_dev or []), flush=True)
-    step = 0
-    for epoch in range(options.num_epochs):
-        if step >= options.step:
-            break
-        step = trainer.train_epoch(mt_data=mt_train, mass_data=mass_train, dev_data=mt_dev, step=step, max_step=options.step,
-                                   save_path=options.model_path, log_every=options.log_steps, eval_every=options.eval_steps,
-                                   accum=options.accum, img_data=img_train)
-    # back-translation phase (src/train_image_mt.py:509-533): optimizer schedule reset, then --fstep more steps in which the
-    # monolingual batches are back-translated.  The reference's flag default is 125000 steps; here the phase runs only when a
-    # language pair is given (--langs), which is what makes it well-defined.
-    lang_directions = ImageMTTrainer.get_lang_dirs(options.bt_langs, tp)
-    if lang_directions is not None and options.finetune_step > 0 and mass_train:
-        optimizer.reset()
-        total = step + options.finetune_step
-        for epoch in range(options.num_epochs):
-            if step >= total:
-                break
-            step = trainer.train_epoch(mt_data=None if options.ignore_mt_mass else mt_train, mass_data=mass_train, dev_data=mt_dev,
-                                       step=step, max_step=total, save_path=options.model_path, log_every=options.log_steps,
-                                       eval_every=options.eval_steps, accum=options.accum, fine_tune=True,
-                                       lang_directions=lang_directions)
+    step = trainer.begin_run(options, resume)
+    step = run_phases(trainer, options, step, mt_train, mass_train, mt_dev, img_train, ImageMTTrainer.get_lang_dirs(options.bt_langs, tp))
+    trainer.finish_snapshots()  # (before the closing evaluation: a resumed run meets best_loss as the loop left it)
     if mt_dev is not None:
         trainer.validate_and_save(mt_dev, options.model_path)
     elif rank == 0 and options.model_path:

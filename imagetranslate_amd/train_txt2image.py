@@ -4,7 +4,8 @@ features of every image into its 49 x d embedding (eval mode, no gradient), and 
 embedding from the caption: L2 distance over the batch divided by the number of images.  The model step is the HIP path
 (``Caption2Image.loss_fused``: encoder stack, fused dropout + pooling, linear layer, ``imt_l2_dist``), then the clip + Adam
 step of the other trainers.  Checkpoints (``<model>.latest``) hold weights only: no pickled optimizer (``--save-opt`` is
-refused).  One process, one GPU."""
+refused); with ``--save-state`` the student's ``train_state.pt`` (checkpoint.py) goes beside them and ``--resume DIR`` continues from
+it -- the frozen captioner is reloaded from ``--pretrained`` as ever.  One process, one GPU."""
 import os
 import random
 
@@ -15,7 +16,7 @@ from .image_model import Caption2Image, ImageCaptioning
 from .option_parser import get_img_options_parser
 from .seq2seq import Seq2Seq
 from .textprocessor import TextProcessor
-from .trainer import Trainer, reject_off_path
+from .trainer import Trainer, add_resume_options, reject_off_path
 from .utils import build_optimizer
 
 
@@ -62,16 +63,21 @@ class Caption2ImageTrainer(Trainer):
 
         def after_step(step):
             if save_path and step % save_every == 0:
-                self.model.save(save_path + ".latest")
+                self.save_latest(save_path)
             if img_dev_data is not None and step % eval_every == 0:
                 print("Dev Loss:", self.dev_loss(img_dev_data), flush=True)
 
+        self.track_dataset(img_data)
+        self.track_dataset(img_dev_data)
+        start = self.take_resume_pos()
         return self.run_epoch(self.epoch_order([("img", len(img_data))]), step_fn, step=step, max_step=max_step,
-                              log_every=log_every, after_step=after_step)
+                              log_every=log_every, after_step=after_step, start=start)
 
     @staticmethod
     def train(options):
         reject_off_path(options)
+        if getattr(options, "resume_dir", None) and not os.path.isfile(os.path.join(options.resume_dir, "train_state.pt")):
+            raise FileNotFoundError("--resume %s: no train_state.pt there" % options.resume_dir)
         if not options.pretrained_path:
             raise ValueError("--pretrained: the directory of the trained ImageCaptioning model is required")
         random.seed(options.seed)
@@ -80,6 +86,8 @@ class Caption2ImageTrainer(Trainer):
         assert tp.pad_token_id() == 0
         caption_model = Seq2Seq.load(ImageCaptioning, options.pretrained_path, tok_dir=options.tokenizer_path,
                                      use_obj=not options.no_obj)
+        # --resume DIR holds the STUDENT's snapshot only; the frozen captioner comes from --pretrained as ever.  The student is
+        # built from the flags (the snapshot carries its weights and refuses another layout)
         model = Caption2Image(text_processor=tp, enc_layer=options.encoder_layer, embed_dim=options.embed_dim,
                               intermediate_dim=options.intermediate_layer_dim, num_attention_heads=options.heads)
         return Caption2ImageTrainer.run(options, model, caption_model, tp)
@@ -103,22 +111,22 @@ class Caption2ImageTrainer(Trainer):
         img_train = mk(options.train_path)
         img_dev = mk(options.dev_path) if options.dev_path else None
         print("image batches", len(img_train), flush=True)
-        step, epoch = 0, 1
-        while options.step > 0 and step < options.step and epoch <= options.num_epochs:
-            print("train epoch", epoch, flush=True)
+        step = trainer.begin_run(options, getattr(options, "resume_dir", None))
+        while options.step > 0 and step < options.step and trainer.epochs_begun < options.num_epochs:
+            print("train epoch", trainer.epochs_begun + 1, flush=True)
             step = trainer.train_epoch(img_data=img_train, img_dev_data=img_dev, step=step, max_step=options.step,
                                        save_path=options.model_path, accum=options.accum, log_every=options.log_steps,
                                        save_every=options.save_steps, eval_every=options.eval_steps)
-            epoch += 1
         if options.model_path:
-            model.save(options.model_path + ".latest")
+            trainer.save_latest(options.model_path)
+        trainer.finish_snapshots()
         if img_dev is not None:
             print("Dev Loss:", trainer.dev_loss(img_dev), flush=True)
         return trainer
 
 
 def main(argv=None):
-    options, _ = get_img_options_parser().parse_args(argv)
+    options, _ = add_resume_options(get_img_options_parser()).parse_args(argv)
     Caption2ImageTrainer.train(options)
     print("Finished Training!")
 

@@ -3,7 +3,8 @@
 ``--src-neg`` / ``--dst-neg`` each step, the two-sided contrastive loss of ``SenSim`` (encoder stack x 4, fused pooling,
 ``imt_sensim_loss``), then the clip + Adam step of the other trainers.  The dev loss (``--dev_mt``) is the one-sided loss without
 negatives; its best value saves to ``--model``, the latest weights go to ``<model>.latest``.  Checkpoints hold weights only: no
-pickled optimizer (``--save-opt`` is refused).  One process, one GPU."""
+pickled optimizer (``--save-opt`` is refused); with ``--save-state`` ``train_state.pt`` (checkpoint.py) goes beside them and ``--resume
+DIR`` continues from it (the negatives are drawn from (seed, step): they continue with the step count).  One process, one GPU."""
 import os
 import random
 
@@ -15,7 +16,7 @@ from .option_parser import get_img_options_parser
 from .sen_sim import SenSim
 from .seq2seq import Seq2Seq
 from .textprocessor import TextProcessor
-from .trainer import Trainer, batches_from, reject_off_path
+from .trainer import Trainer, add_resume_options, batches_from, reject_off_path
 from .utils import build_optimizer
 
 NEG_FACTOR = 5  # the negatives' batch and capacity are five times the pairs' (src/train_txt_sim.py:181-182)
@@ -78,12 +79,13 @@ class SenSimTrainer(Trainer):
 
         def after_step(step):
             if save_path and step % save_every == 0:
-                self.model.save(save_path + ".latest")
+                self.save_latest(save_path)
             if dev_data is not None and step % eval_every == 0:
                 self.validate_and_save(dev_data, save_path)
 
+        start = self.take_resume_pos()
         return self.run_epoch(self.epoch_order([("mt", len(mt_data))]), step_fn, step=step, max_step=max_step,
-                              log_every=log_every, after_step=after_step)
+                              log_every=log_every, after_step=after_step, start=start)
 
     def validate_and_save(self, dev_data, save_path):
         dl = self.dev_loss(dev_data)
@@ -109,7 +111,10 @@ class SenSimTrainer(Trainer):
         assert tp.pad_token_id() == 0
         model = SenSim(text_processor=tp, enc_layer=options.encoder_layer, embed_dim=options.embed_dim,
                        intermediate_dim=options.intermediate_layer_dim, num_attention_heads=options.heads)
-        if options.pretrained_path:
+        if getattr(options, "resume_dir", None) and not os.path.isfile(os.path.join(options.resume_dir, "train_state.pt")):
+            raise FileNotFoundError("--resume %s: no train_state.pt there" % options.resume_dir)
+        if options.pretrained_path:  # (--pretrained is a language model here, not a SenSim: --resume does not replace it; the
+            # model is built from the flags, the snapshot carries its weights and refuses another layout)
             model.init_from_lm(Seq2Seq.load(Seq2Seq, options.pretrained_path, tok_dir=options.tokenizer_path))
         return SenSimTrainer.run(options, model, tp)
 
@@ -131,22 +136,22 @@ class SenSimTrainer(Trainer):
         if not len(mt_train) or not len(src_neg) or not len(dst_neg):
             raise ValueError("no batches: %d of sentence pairs, %d / %d of negatives" % (len(mt_train), len(src_neg), len(dst_neg)))
         print("MT batches", len(mt_train), "negative batches", len(src_neg), len(dst_neg), "dev batches", len(mt_dev or []), flush=True)
-        step, epoch = 0, 1
-        while options.step > 0 and step < options.step and epoch <= options.num_epochs:
-            print("train epoch", epoch, flush=True)
+        step = trainer.begin_run(options, getattr(options, "resume_dir", None))
+        while options.step > 0 and step < options.step and trainer.epochs_begun < options.num_epochs:
+            print("train epoch", trainer.epochs_begun + 1, flush=True)
             step = trainer.train_epoch(mt_train, src_neg, dst_neg, dev_data=mt_dev, step=step, max_step=options.step,
                                        save_path=options.model_path, accum=options.accum, log_every=options.log_steps,
                                        save_every=options.save_steps, eval_every=options.eval_steps)
-            epoch += 1
         if options.model_path:
-            model.save(options.model_path + ".latest")
+            trainer.save_latest(options.model_path)
+        trainer.finish_snapshots()
         if mt_dev is not None:
             trainer.validate_and_save(mt_dev, options.model_path)
         return trainer
 
 
 def main(argv=None):
-    options, _ = get_img_options_parser().parse_args(argv)
+    options, _ = add_resume_options(get_img_options_parser()).parse_args(argv)
     SenSimTrainer.train(options)
     print("Finished Training!")
 

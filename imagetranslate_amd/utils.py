@@ -63,6 +63,72 @@ class AdamInverseSqrtWithWarmup(torch.optim.Optimizer):
         for param_group in self.param_groups:
             param_group['num_updates'] = 0
 
+    # ------------------------------------------------------------------ state that travels (checkpoint.py)
+    def _params(self):
+        return [p for g in self.param_groups for p in g['params']]
+
+    @torch.no_grad()
+    def state_dict(self):
+        """What torch's Adam would return: ``param_groups`` (with ``num_updates`` and ``lr``) and ``state[i] = {"exp_avg",
+        "exp_avg_sq"}`` shaped like parameter ``i``.  On the fused path the moments live in the flat store, not in
+        ``self.state``: they are COPIED out of the store's spans here (after an update still running on the side stream)."""
+        params = self._params()
+        index, groups = {id(p): i for i, p in enumerate(params)}, []
+        for g in self.param_groups:
+            groups.append({**{k: v for k, v in g.items() if k != 'params'}, 'params': [index[id(p)] for p in g['params']]})
+        st = self._store()
+        state = {}
+        if st is not None:
+            st.ensure()
+            st.wait_updates(0)
+            if st.exp_avg is not None:
+                for i, p in enumerate(params):
+                    state[i] = {'exp_avg': st._view(st.exp_avg, p).clone(), 'exp_avg_sq': st._view(st.exp_avg_sq, p).clone()}
+        else:
+            for i, p in enumerate(params):
+                if self.state.get(p):
+                    state[i] = {k: self.state[p][k].clone() for k in ('exp_avg', 'exp_avg_sq')}
+        return {'state': state, 'param_groups': groups}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Moments back into the flat store at each parameter's offset (generic path: into ``self.state``), ``num_updates``
+        from the file, ``lr`` from THIS optimizer's schedule at that update count: a resumed run may be given another --lr or
+        --warmup, the file decides only how far the schedule has advanced.  A parameter without saved moments gets zeros.
+        Another parameter count or another shape is refused."""
+        params, state = self._params(), state_dict['state']
+        saved_groups = state_dict['param_groups']
+        n_saved = sum(len(g['params']) for g in saved_groups)
+        if n_saved != len(params) or len(saved_groups) != len(self.param_groups):
+            raise ValueError("optimizer state holds %d parameters in %d groups, this optimizer has %d in %d"
+                             % (n_saved, len(saved_groups), len(params), len(self.param_groups)))
+        for i, p in enumerate(params):
+            for k in ('exp_avg', 'exp_avg_sq'):
+                if i in state and tuple(state[i][k].shape) != tuple(p.shape):
+                    raise ValueError("optimizer state: %s of parameter %d has shape %s, the parameter has %s"
+                                     % (k, i, tuple(state[i][k].shape), tuple(p.shape)))
+        st = self._store()
+        if st is not None:
+            st.ensure()
+            st.wait_updates(0)
+            m, v = st.moments()
+            for i, p in enumerate(params):
+                for buf, k in ((m, 'exp_avg'), (v, 'exp_avg_sq')):
+                    view = st._view(buf, p)
+                    if i in state:
+                        view.copy_(state[i][k])
+                    else:
+                        view.zero_()
+        else:
+            for i, p in enumerate(params):
+                if i in state:
+                    self.state[p] = {k: state[i][k].to(device=p.device, dtype=p.dtype).clone() for k in ('exp_avg', 'exp_avg_sq')}
+                else:
+                    self.state.pop(p, None)
+        for g, saved in zip(self.param_groups, saved_groups):
+            g['num_updates'] = int(saved['num_updates'])
+            g['lr'] = self.get_lr_for_step(g['num_updates'])
+
     def _store(self):
         st = None
         n = 0
