@@ -160,7 +160,8 @@ class MassArgs(Structure):
     _fields_ = [
         ("n_rows", c_int32), ("width", c_int32), ("recover_width", c_int32), ("n_special", c_int32), ("vocab", c_int32),
         ("mask_prob", c_float), ("seed", c_uint64), ("mask_id", c_int64), ("pad_id", c_int64),
-        ("src_text", c_void_p), ("pad_indices", c_void_p), ("row_offsets", c_void_p), ("src_mask", c_void_p),
+        ("src_text", c_void_p), ("pad_indices", c_void_p), ("row_offsets", c_void_p), ("first", c_void_p),
+        ("src_mask", c_void_p),
         ("to_recover", c_void_p), ("positions", c_void_p), ("targets", c_void_p),
     ]
 

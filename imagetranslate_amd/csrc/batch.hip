@@ -1,39 +1,22 @@
 // On-device batch construction for MASS (src/utils.py:41-82): span selection, the shifted
 // decoder input with its original positions, compaction of the hidden tokens and the 80/10/10 replacement -- integer
 // work, one workgroup per sentence, so a MASS step needs no per-token host loop and no host->device copy of masks.
-// Randomness is counter-based (counter_uniform of common.hpp: mix32 of (seed, stream, index)), restated bit for bit by oracle/batch_oracle.py.
+// Randomness is counter-based (counter_uniform of common.hpp: mix32 of (seed, stream, index)), restated bit for bit by oracle/batch_oracle.py;
+// the span starts (streams 0, 1) are drawn on the host by utils.mass_span_starts, the 80/10/10 replacement (streams 2, 3) here.
 #include "common.hpp"
 
 namespace {
 
 __global__ __launch_bounds__(256) void mass_mask_kernel(imt_mass_args a) {
-  __shared__ int s_first, s_len;
   const int row = blockIdx.x;
   int64_t* text = a.src_text + (int64_t)row * a.width;
-  if (threadIdx.x == 0) {
-    const int64_t pad = a.pad_indices[row];
-    const int span_len = (int)(pad / 2);
-    // float32 with TWO roundings like the reference's tensor expression pad - (1-p)*pad: no fused multiply-add (HIP's
-    // __fmul_rn / __fsub_rn are plain operators and would be contracted), e.g. pad = 50: 50 - 35.0 = 15, fma gives 15.0000006
-    float bound;
-    {
-#pragma clang fp contract(off)
-      const float prod = (1.0f - a.mask_prob) * (float)pad;
-      bound = (float)pad - prod;
-    }
-    const int hint = (int)ceilf(bound);
-    const float u0 = counter_uniform(a.seed, 0u, (uint32_t)row);
-    int first;
-    if (u0 > 0.8f) first = 1;
-    else if (u0 > 0.6f) first = hint;
-    else if (hint >= 2) {
-      first = 2 + (int)(counter_uniform(a.seed, 1u, (uint32_t)row) * (float)(hint - 1));
-      if (first > hint) first = hint;
-    } else first = 2;
-    s_first = first; s_len = span_len;
-  }
-  __syncthreads();
-  const int first = s_first, len = s_len;
+  // The span start is the caller's draw (imt_hip.h): row_offsets, recover_width and the size of `targets` follow from the
+  // span CLIPPED at the row's end, so the start that sized them and the start that writes must be one number.  The two
+  // clamps and the clip below are restated once on the host, in utils.mass_span_sizes: change them together.
+  const int64_t f64 = a.first[row];
+  const int first = (int)(f64 < 1 ? 1 : (f64 > a.width ? a.width : f64));
+  const int64_t len64 = a.pad_indices[row] / 2;
+  const int len = (int)(len64 < 0 ? 0 : (len64 > a.width ? a.width : len64));
   const int last = min(first + len, a.width);  // python slice semantics
   const int64_t off = a.row_offsets[row];
   // span mask
@@ -161,7 +144,7 @@ extern "C" int imt_mass_mask(const imt_mass_args* a, void* stream) {
   IMT_CHECK_ARG(a->n_rows > 0 && a->width > 1 && a->recover_width > 0, "mass_mask: bad sizes");
   IMT_CHECK_ARG(a->mask_prob > 0.f && a->mask_prob < 1.f, "mass_mask: mask_prob must be in (0, 1)");
   IMT_CHECK_ARG(a->vocab > a->n_special && a->n_special >= 0, "mass_mask: vocabulary smaller than the special-token block");
-  IMT_CHECK_ARG(a->src_text && a->pad_indices && a->row_offsets && a->src_mask && a->to_recover && a->positions && a->targets,
+  IMT_CHECK_ARG(a->src_text && a->pad_indices && a->row_offsets && a->first && a->src_mask && a->to_recover && a->positions && a->targets,
                 "mass_mask: null tensor");
   hipStream_t st = (hipStream_t)stream;
   ImtProfScope prof("mass_mask", 0, (double)a->n_rows * a->width * 17, st);

@@ -10,6 +10,7 @@ import math
 import random
 from typing import Dict
 
+import numpy as np
 import torch
 from torch.nn.utils.rnn import pad_sequence
 
@@ -365,18 +366,68 @@ def mass_unmask(src_text, src_mask, masked_ids):
 
 
 # ----------------------------------------------------------------------------------------- device batch construction
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(x):
+    """csrc/common.hpp mix32 on uint64 arrays holding 32-bit values (no product leaves 64 bits)."""
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & _U32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & _U32
+    return x ^ (x >> np.uint64(16))
+
+
+def _counter_uniform(seed: int, stream: int, index):
+    """csrc/common.hpp counter_uniform(seed, stream, index) for an array of indices below 2^32: float32 in [0, 1), 24 bits."""
+    index = np.asarray(index).astype(np.uint64)
+    h = _mix32((index ^ np.uint64(seed & 0xFFFFFFFF)) & _U32)
+    h = _mix32((h + np.uint64((stream * 0x9E3779B9 + (seed >> 32)) & 0xFFFFFFFF)) & _U32)
+    return (h >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)   # both factors and the product are exact in float32
+
+
+def mass_span_starts(mask_prob, pad_indices, seed: int):
+    """Span start of every row of a MASS batch (src/utils.py:52-60) on the draws imt_mass_mask's generator gives for
+    (seed, stream 0 / 1, row): int64 [n_rows] on the host, no device work (numpy: a few microseconds per operator at batch
+    sizes).  The bound ceil(pad - (1 - p) * pad) is float32 with TWO roundings like the reference's tensor expression (product,
+    then difference; pad = 50, p = 0.3: 50 - 35.0 = 15, a fused multiply-add gives 15.0000006 and a bound of 16), which
+    separate array operators keep."""
+    pad = pad_indices.detach().cpu().to(torch.int64).numpy()
+    rows = np.arange(pad.size, dtype=np.uint64)
+    padf = pad.astype(np.float32)
+    prod = (np.float32(1.0) - np.float32(mask_prob)) * padf
+    hint = np.ceil(padf - prod).astype(np.int64)
+    u0, u1 = _counter_uniform(int(seed), 0, rows), _counter_uniform(int(seed), 1, rows)
+    drawn = 2 + (u1 * (hint - 1).astype(np.float32)).astype(np.int64)   # float32 product, truncated
+    uniform = np.where(hint >= 2, np.minimum(drawn, hint), 2)
+    first = np.where(u0 > np.float32(0.8), 1, np.where(u0 > np.float32(0.6), hint, uniform))
+    return torch.from_numpy(first.astype(np.int64))
+
+
+def mass_span_sizes(first, pad_indices, width: int):
+    """(span start, number of hidden tokens) of every row as mass_mask_kernel (csrc/batch.hip) reads them -- the host's only
+    copy of the kernel's arithmetic (include/imt_hip.h: f, len, hidden), so change the two together: the start clamped to
+    [1, width], the span length int(pad / 2) clamped to [0, width], the span clipped at the row's end."""
+    first = first.clamp(1, width)
+    length = (pad_indices.detach().cpu().to(torch.int64) // 2).clamp(0, width)
+    return first, torch.clamp(first + length, max=width) - first
+
+
 def mass_mask_device(mask_prob, pad_indices, src_text, text_processor, seed: int) -> Dict:
     """mass_mask on the GPU (imt_mass_mask): same outputs and the same in-place semantics as ``mass_mask`` above, all
     tensors on the device of ``src_text``.  Span starts and the 80/10/10 replacement use the kernel's counter-based
-    generator keyed by ``seed`` instead of Python's ``random`` (same procedure, different stream); only the sizes that
-    follow from ``pad_indices`` are computed on the host."""
+    generator keyed by ``seed`` instead of Python's ``random`` (same procedure, different stream).  The span starts are
+    drawn on the host (``mass_span_starts``) and handed to the kernel: a span is clipped at the row's end like a Python
+    slice, so the number of hidden tokens of a row -- and with it every output size -- depends on where the span starts.
+    Nothing is read back from the device."""
     import ctypes
     from . import _lib as L
     if not src_text.is_cuda:
         raise L.ImtError("mass_mask_device needs src_text on the GPU (use mass_mask on the host)")
     assert 0 < mask_prob < 1
     n_rows, width = src_text.shape
-    span_len = (pad_indices.cpu().to(torch.int64) // 2)
+    pad_host = pad_indices.detach().cpu().to(torch.int64)
+    first, span_len = mass_span_sizes(mass_span_starts(mask_prob, pad_host, seed), pad_host, width)   # hidden tokens per row
     offsets = torch.cumsum(span_len, 0) - span_len
     total, recover_width = int(span_len.sum()), int(span_len.max()) + 1
     dev = src_text.device
@@ -385,13 +436,14 @@ def mass_mask_device(mask_prob, pad_indices, src_text, text_processor, seed: int
            "to_recover": torch.empty((n_rows, recover_width), dtype=torch.int64, device=dev),
            "positions": torch.empty((n_rows, recover_width), dtype=torch.int64, device=dev),
            "targets": torch.empty(total, dtype=torch.int64, device=dev)}
-    pad_dev, off_dev = pad_indices.to(dev, torch.int64).contiguous(), offsets.to(dev)
+    pad_dev, off_dev, first_dev = pad_indices.to(dev, torch.int64).contiguous(), offsets.to(dev), first.to(dev)
     a = L.MassArgs()
     a.n_rows, a.width, a.recover_width = n_rows, width, recover_width
     a.n_special, a.vocab = len(text_processor.special_tokens), text_processor.vocab_size()
     a.mask_prob, a.seed = float(mask_prob), int(seed)
     a.mask_id, a.pad_id = text_processor.mask_token_id(), text_processor.pad_token_id()
     a.src_text, a.pad_indices, a.row_offsets = src_text.data_ptr(), pad_dev.data_ptr(), off_dev.data_ptr()
+    a.first = first_dev.data_ptr()
     a.src_mask, a.to_recover = out["src_mask"].data_ptr(), out["to_recover"].data_ptr()
     a.positions, a.targets = out["positions"].data_ptr(), out["targets"].data_ptr()
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -724,9 +724,16 @@ int imt_sample_step(const imt_sample_args* a, void* stream);
  * uniform in [2, bound] (60%) (src/utils.py:52-60); the decoder input `to_recover` is the span shifted right by one
  * with its ORIGINAL positions; hidden tokens become <mask> (80%), a random non-special id (10%) or stay (10%).
  * The random draws are counter-based on (seed, stream, index) -- NOT Python's generator: the same statistical
- * procedure, reproducible on device.  Sizes that depend only on pad_indices are computed by the caller:
- *   row_offsets[r] = sum_{q<r} int(pad_indices[q]/2)   (exclusive prefix sum; total = number of targets)
- *   recover_width  = max_r int(pad_indices[r]/2) + 1
+ * procedure, reproducible on device.  The span starts are drawn by the CALLER (streams 0 and 1 of the generator, index =
+ * row; utils.mass_span_starts restates the rule on the host without a device read) and handed in as `first`, because a
+ * span is clipped at the row's end like a Python slice and every size below follows from the clipped span:
+ *   f[r]           = first[r] clamped to [1, width]       (a start below 1 is read as 1, one past the row as width)
+ *   len[r]         = int(pad_indices[r]/2) clamped to [0, width]
+ *   hidden[r]      = min(f[r] + len[r], width) - f[r]     (>= 0 after the clamps)
+ *   row_offsets[r] = sum_{q<r} hidden[q]                  (exclusive prefix sum; total = number of targets)
+ *   recover_width  = max_r hidden[r] + 1
+ * The kernel applies the same two clamps, writes hidden[r] targets for row r and nothing else into `targets`: the sizes
+ * and the writes come from the same `first` (utils.mass_span_sizes is the caller's side of this arithmetic).
  * src_text is modified in place (like the reference); imt_mass_unmask restores it from `targets`.
  */
 typedef struct imt_mass_args {
@@ -738,6 +745,7 @@ typedef struct imt_mass_args {
   int64_t* src_text;            /* [n_rows, width] in/out */
   const int64_t* pad_indices;   /* [n_rows] index of the first pad token (width-1 if none) */
   const int64_t* row_offsets;   /* [n_rows] */
+  const int64_t* first;         /* [n_rows] span start of every row, drawn by the caller */
   uint8_t* src_mask;            /* [n_rows, width] out: 1 on hidden positions */
   int64_t* to_recover;          /* [n_rows, recover_width] out, padded with pad_id */
   int64_t* positions;           /* [n_rows, recover_width] out, padded with width-1 */

@@ -34,25 +34,29 @@ def counter_uniform(seed: int, stream: int, index: int) -> np.float32:
     return np.float32(h >> 8) * np.float32(1.0 / 16777216.0)
 
 
+def span_start(mask_prob, pad_index: int, u0, u1) -> int:
+    """The span-start rule (``src/utils.py:52-60``) of one row on the draws (u0, u1)."""
+    pad = np.float32(int(pad_index))
+    bound = pad - np.float32(np.float32(1.0) - np.float32(mask_prob)) * pad  # float32 tensor arithmetic
+    hint = int(math.ceil(float(bound)))
+    if u0 > np.float32(0.8):
+        return 1
+    if u0 > np.float32(0.6):
+        return hint
+    if hint >= 2:
+        return min(hint, 2 + int(np.float32(u1) * np.float32(hint - 1)))
+    return 2
+
+
 def mass_mask_reference(mask_prob, pad_indices, src_text, n_special, vocab, mask_id, pad_id, draw_start, draw_token):
     src_text = src_text.clone()
     n_rows, width = src_text.shape
     src_mask = torch.zeros((n_rows, width), dtype=torch.bool)
     to_recover, to_recover_pos = [], []
     for r in range(n_rows):
-        pad = np.float32(int(pad_indices[r]))
-        bound = pad - np.float32(np.float32(1.0) - np.float32(mask_prob)) * pad  # float32 tensor arithmetic
-        hint = int(math.ceil(float(bound)))
         span_len = int(int(pad_indices[r]) / 2)
         u0, u1 = draw_start(r)
-        if u0 > np.float32(0.8):
-            first = 1
-        elif u0 > np.float32(0.6):
-            first = hint
-        elif hint >= 2:
-            first = min(hint, 2 + int(np.float32(u1) * np.float32(hint - 1)))
-        else:
-            first = 2
+        first = span_start(mask_prob, int(pad_indices[r]), u0, u1)
         last = first + span_len
         src_mask[r, first:last] = True
         to_recover.append(src_text[r, first - 1:last])
