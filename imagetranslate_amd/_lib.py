@@ -179,6 +179,17 @@ class ScoreArgs(Structure):
     ]
 
 
+class KnnArgs(Structure):
+    _fields_ = [
+        ("dtype", c_int32), ("N", c_int32), ("M", c_int32), ("K", c_int32), ("k", c_int32),
+        ("x", c_void_p), ("ldx", c_int64),
+        ("y", c_void_p), ("ldy", c_int64),
+        ("index_base", c_int32), ("splits", c_int32),
+        ("val", c_void_p), ("idx", c_void_p),
+        ("ws", c_void_p), ("ws_bytes", c_int64),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/imt_hip.h declares (tests/test_cabi.py checks)
 _P = c_void_p
 SIGNATURES = {
@@ -213,6 +224,9 @@ SIGNATURES = {
     "imt_score_ws_bytes": (c_int64, [c_int, c_int]),
     "imt_score_supported": (c_int, [c_int, c_int, c_int]),
     "imt_score_rows": (c_int, [POINTER(ScoreArgs), _P]),
+    "imt_knn_ws_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "imt_knn_supported": (c_int, [c_int, c_int]),
+    "imt_knn_rows": (c_int, [POINTER(KnnArgs), _P]),
     "imt_scaled_sum": (c_int, [_P, c_int, c_float, _P, _P]),
     "imt_sumsq": (c_int, [_P, c_int64, _P, _P, _P]),
     "imt_ln_partial_reduce": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
@@ -280,7 +294,8 @@ class ImtError(RuntimeError):
 ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_row": ProfRow, "imt_attn_block": AttnBlock,
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
-               "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs}
+               "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs,
+               "imt_knn_args": KnnArgs}
 
 
 def load():

@@ -427,6 +427,83 @@ def score_rows(x, weight, bias, targets, seg_offsets=None, normalize=True):
     return logprob, lse, seg
 
 
+KNN_MAX_K = 8  # IMT_KNN_MAX_K
+
+
+def _knn_operand(t):
+    """Rows for imt_knn_rows: K zero-padded up to a whole 128-byte K tile (a zero column changes no product), 16-byte rows."""
+    tile = 128 // t.element_size()
+    K = t.shape[1]
+    if K % tile:
+        out = torch.zeros((t.shape[0], (K + tile - 1) // tile * tile), device=t.device, dtype=t.dtype)
+        out[:, :K] = t
+        return out
+    return rows16(t)
+
+
+def _knn_max_rows(t):
+    """Most rows of ``t`` one call may see: (rows + 256) * ld * element size stays below 2 GiB (32-bit DMA offsets)."""
+    ld = max(t.shape[1], t.stride(0))
+    return ((1 << 31) - 1) // (ld * t.element_size()) - 256
+
+
+def knn_rows(x, y, k, *, splits=0, _key_chunk=None, _query_chunk=None):
+    """The k keys of largest inner product for every query, without the [N, M] similarities (include/imt_hip.h:
+    imt_knn_rows).  x [N, K], y [M, K] in one dtype (fp32 / bf16).  Returns (val [N, k] fp32, idx [N, k] int64): by value
+    descending, then index ascending; places past M hold -inf / -1.  Operands beyond the kernel's 2 GiB limit are cut into
+    row chunks; the key chunks' lists are merged by a stable descending sort (chunks arrive in index order, so equal values
+    keep index order).  ``_key_chunk`` / ``_query_chunk``: keys / queries per call, for tests."""
+    _req_cuda(x, y)
+    N, K = x.shape
+    M = y.shape[0]
+    if y.shape[1] != K or y.dtype != x.dtype:
+        raise ValueError("knn_rows: queries %s %s against keys %s %s" % (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype))
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("knn_rows: k = %d outside 1..%d" % (k, KNN_MAX_K))
+    dev = x.device
+    if N == 0 or M == 0:
+        return (torch.full((N, k), float("-inf"), device=dev, dtype=torch.float32),
+                torch.full((N, k), -1, device=dev, dtype=torch.int64))
+    x, y = _knn_operand(x), _knn_operand(y)
+    Kp = x.shape[1]
+    lib = L.load()
+    if not lib.imt_knn_supported(dt(x), Kp):
+        raise L.ImtError("knn_rows: (dtype %s, K %d) is not taken by imt_knn_rows" % (x.dtype, Kp))
+    q_rows = max(1, min(_knn_max_rows(x), int(_query_chunk) if _query_chunk else N))
+    k_rows = max(1, min(_knn_max_rows(y), int(_key_chunk) if _key_chunk else M))
+    val = torch.empty((N, k), device=dev, dtype=torch.float32)
+    idx = torch.empty((N, k), device=dev, dtype=torch.int64)
+    n_chunks = (M + k_rows - 1) // k_rows
+    for r0 in range(0, N, q_rows):
+        r1 = min(N, r0 + q_rows)
+        xs = x[r0:r1]
+        cv = torch.empty((r1 - r0, n_chunks * k), device=dev, dtype=torch.float32)
+        ci = torch.empty((r1 - r0, n_chunks * k), device=dev, dtype=torch.int32)
+        for c, c0 in enumerate(range(0, M, k_rows)):
+            ys = y[c0:min(M, c0 + k_rows)]
+            v = torch.empty((r1 - r0, k), device=dev, dtype=torch.float32)
+            i = torch.empty((r1 - r0, k), device=dev, dtype=torch.int32)
+            nbytes = int(lib.imt_knn_ws_bytes(xs.shape[0], ys.shape[0], k, splits))
+            ws = score_workspace(dev, nbytes)
+            a = L.KnnArgs()
+            a.dtype, a.N, a.M, a.K, a.k = dt(x), xs.shape[0], ys.shape[0], Kp, k
+            a.x, a.ldx = xs.data_ptr(), max(Kp, xs.stride(0))
+            a.y, a.ldy = ys.data_ptr(), max(Kp, ys.stride(0))
+            a.index_base, a.splits = c0, int(splits)
+            a.val, a.idx = v.data_ptr(), i.data_ptr()
+            a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+            L.check(lib.imt_knn_rows(ctypes.byref(a), _stream()), "imt_knn_rows")
+            cv[:, c * k:(c + 1) * k] = v
+            ci[:, c * k:(c + 1) * k] = i
+        if n_chunks == 1:
+            val[r0:r1], idx[r0:r1] = cv, ci.long()
+        else:
+            sv, order = torch.sort(cv, dim=1, descending=True, stable=True)
+            val[r0:r1] = sv[:, :k]
+            idx[r0:r1] = ci.gather(1, order[:, :k]).long()
+    return val, idx
+
+
 def log_softmax_bwd(dlp, lp, out_dtype):
     _req_cuda(dlp, lp)
     N, V = lp.shape

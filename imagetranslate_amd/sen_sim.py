@@ -176,6 +176,21 @@ class SenSim(FlatStoreModel):
         u, _, norm = O.attn_pool_fwd(states.contiguous(), w.view(-1), b, src_mask)
         return (u * (norm.unsqueeze(-1) + 1e-4)).detach()
 
+    @torch.no_grad()
+    def encode_unit(self, inputs, mask, langs):
+        """[rows, d] fp32: the UNIT sentence vectors u = v / (|v| + 1e-4) as ``imt_attn_pool_fwd`` writes them -- what the
+        similarity of ``forward`` and the neighbour search of ``mine_pairs`` work on.  ``langs`` is per sentence [rows] (as
+        ``forward`` takes it) or per position [rows, S] (as ``encode`` does).  No autograd."""
+        device = self._device
+        inputs, mask, langs = inputs.to(device), mask.to(device), langs.to(device)
+        if langs.dim() == 1:
+            langs = langs.unsqueeze(-1).expand(-1, inputs.size(-1))
+        states = self.encoder(inputs, attention_mask=mask, token_type_ids=langs)
+        store = store_of(self).ensure()
+        w, b = store.views(states.dtype, self.input_attention.weight, self.input_attention.bias)
+        u, _, _ = O.attn_pool_fwd(states.contiguous(), w.view(-1), b, mask)
+        return u.detach()
+
     def forward(self, src_inputs, src_mask, src_langs, tgt_inputs, tgt_mask, tgt_langs, src_neg_inputs=None, src_neg_mask=None,
                 src_neg_langs=None, tgt_neg_inputs=None, tgt_neg_mask=None, tgt_neg_langs=None, normalize: bool = False):
         """``normalize=False``: [B] dot products of the pairs' unit vectors.  ``normalize=True``: the contrastive loss (0-d fp32),

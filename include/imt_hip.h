@@ -316,6 +316,38 @@ typedef struct imt_score_args {
 int64_t imt_score_ws_bytes(int N, int V);
 int imt_score_supported(int dtype, int V, int K);
 int imt_score_rows(const imt_score_args* a, void* stream);
+/* ------------------------------------------------------------------ k nearest neighbours by inner product (sentence mining)
+ * For queries x [N, K] and keys y [M, K] of one dtype: s[r, c] = sum_k x[r, k] y[c, k] (fp32 accumulate, imt_gemm's K order).
+ *   val [N, k] fp32, idx [N, k] int32: row r holds the k largest s[r, .], ordered by value descending, then index ascending;
+ *   ties at any place, the k-th included, go to the lowest indices.  idx stores c + index_base (key chunks report global
+ *   indices).  Places j >= M hold val = -inf, idx = -1.
+ * Launch 1 (profiling kind knn_xl_bf16 / knn_xl_f32) is imt_gemm's 256 x 256-tile NT main loop; one workgroup walks the column
+ * tiles of one of `splits` column ranges of a 256-row block and keeps the rows' running lists in LDS; launch 2 (knn_combine)
+ * merges the ranges of a row in column order.  The [N, M] similarities are never stored.  No atomics: two calls on the same
+ * input give the same bits, and so do calls with different `splits`.  splits = 0 lets the host choose (enough workgroups for
+ * the chip when N is small).  ws: caller-owned scratch of imt_knn_ws_bytes(N, M, k, splits) bytes = N x splits x k floats
+ * (rounded up to 256 bytes) + as many int32; contents are undefined afterwards.
+ * imt_knn_supported: 1 where K is a whole number of 128-byte K tiles (64 bf16 / 32 fp32 elements).
+ * Refused before any launch with IMT_ERR_BAD_ARG: null args or tensors, a bad dtype, N, M or K <= 0, k outside
+ * 1..IMT_KNN_MAX_K, splits outside 0..IMT_KNN_MAX_SPLITS, an unsupported K, ldx / ldy (in elements) below K or rows not 16-byte
+ * aligned, (rows + 256) * ld * element size >= 2^31 for either operand (32-bit DMA offsets), a workspace that is misaligned
+ * or too small, index_base < 0 or index_base + M above 2^31 - 1. */
+#define IMT_KNN_MAX_K 8
+#define IMT_KNN_MAX_SPLITS 256
+typedef struct imt_knn_args {
+  int32_t dtype;                 /* IMT_F32 / IMT_BF16: type of x and y */
+  int32_t N, M, K, k;            /* queries, keys, vector length, neighbours per query */
+  const void* x; int64_t ldx;    /* [N, K] queries */
+  const void* y; int64_t ldy;    /* [M, K] keys */
+  int32_t index_base;            /* added to every stored index */
+  int32_t splits;                /* 0: host's choice; else 1..IMT_KNN_MAX_SPLITS column ranges */
+  float* val;                    /* [N, k] out */
+  int32_t* idx;                  /* [N, k] out */
+  void* ws; int64_t ws_bytes;    /* caller-owned workspace, >= imt_knn_ws_bytes(N, M, k, splits) */
+} imt_knn_args;
+int64_t imt_knn_ws_bytes(int N, int M, int k, int splits);
+int imt_knn_supported(int dtype, int K);
+int imt_knn_rows(const imt_knn_args* a, void* stream);
 /* out[0] = scale * sum(x[0..n)), fixed summation order: the `.mean()` of the per-row losses (train_image_mt.py:282). */
 int imt_scaled_sum(const float* x, int n, float scale, float* out, void* stream);
 
