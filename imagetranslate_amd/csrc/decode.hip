@@ -3,66 +3,69 @@
 // Both are HBM/latency-bound byte and index work: no MFMA here, only coalesced 16-byte row reads.
 #include "common.hpp"
 #include "decode_attn.hpp"
+#include "search_step.hpp"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ beam step
-// (score desc, index asc) ordering: better() / wave_best() of common.hpp
+// (score desc, index asc) ordering: better() / wave_best() of common.hpp; sweeps, reductions and bookkeeping: search_step.hpp
 constexpr int BEAM_THREADS = 256;
-constexpr int MAX_BEAM = 32;
+
+// What the two row kernels know of their input row before they read it.
+struct BeamRow {
+  const float* x;
+  float cur, pen;  // the hypothesis' score, its length penalty
+  bool use_pen, finished;
+  float* cs; int* ci;  // the row's `beam` candidates
+  IMT_DEVICE float score(float lp) const { return use_pen ? (cur + lp) / pen : cur + lp; }
+};
+// A finished row's candidates are filled here (all V continuations score the same: lowest indices win); the kernel returns.
+template <int THREADS>
+IMT_DEVICE BeamRow beam_row(const imt_beam_args& a, int r, int tid) {
+  BeamRow row;
+  row.x = a.logits + (int64_t)r * a.ld;
+  row.cur = a.scores_in[r];
+  row.use_pen = a.beam > 1;
+  row.pen = row.use_pen ? powf((a.sizes_in[r] + 6.0f) / 6.0f, a.len_penalty_ratio) : 1.0f;
+  row.finished = row_finished(a, r, r / a.rep);
+  row.cs = a.cand_scores + (int64_t)r * a.beam;
+  row.ci = a.cand_idx + (int64_t)r * a.beam;
+  if (row.finished) {
+    const float s = row.score(0.0f);
+    for (int t = tid; t < a.beam; t += THREADS) { row.cs[t] = s; row.ci[t] = t; }
+  }
+  return row;
+}
 
 // Stage 1: one workgroup per input hypothesis row: log-sum-exp, then the row's `beam` best continuations.
 __global__ __launch_bounds__(BEAM_THREADS) void beam_row_topk_kernel(imt_beam_args a) {
-  __shared__ float red_f[BEAM_THREADS / 64];
-  __shared__ float red_g[BEAM_THREADS / 64];
-  __shared__ int red_i[BEAM_THREADS / 64];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int b = r / a.rep;
-  const float* x = a.logits + (int64_t)r * a.ld;
-  const float cur = a.scores_in[r];
-  const bool use_pen = a.beam > 1;
-  const float pen = use_pen ? powf((a.sizes_in[r] + 6.0f) / 6.0f, a.len_penalty_ratio) : 1.0f;
-  const bool masked = a.eos_in[r] || (a.step > 1 && a.max_lens[b] < (int64_t)a.step + 1);
-  float* cs = a.cand_scores + (int64_t)r * a.beam;
-  int* ci = a.cand_idx + (int64_t)r * a.beam;
-  if (masked) {  // all V continuations score the same: lowest indices win
-    const float s = use_pen ? (cur + 0.0f) / pen : cur + 0.0f;
-    for (int t = tid; t < a.beam; t += BEAM_THREADS) { cs[t] = s; ci[t] = t; }
-    return;
-  }
+  constexpr int WAVES = BEAM_THREADS / 64;
+  __shared__ float red_f[WAVES];
+  __shared__ float red_g[WAVES];
+  __shared__ int red_i[WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const BeamRow row = beam_row<BEAM_THREADS>(a, blockIdx.x, tid);
+  if (row.finished) return;
+  const float* x = row.x;
   // log-sum-exp
   float mx = -INFINITY;
   for (int v = tid; v < a.V; v += BEAM_THREADS) mx = fmaxf(mx, x[v]);
-  mx = wave_max(mx);
-  if (lane == 0) red_f[wv] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
+  mx = block_max<WAVES>(mx, red_f, lane, wv);
   float sum = 0.f;
   for (int v = tid; v < a.V; v += BEAM_THREADS) sum += __expf(x[v] - mx);
-  sum = wave_sum(sum);
-  if (lane == 0) red_g[wv] = sum;
-  __syncthreads();
-  const float lse = mx + logf(red_g[0] + red_g[1] + red_g[2] + red_g[3]);
+  const float lse = mx + logf(block_sum<WAVES>(sum, red_g, lane, wv));
   // `beam` selection rounds; round t admits only elements ordered after the previous pick
   float ps = INFINITY; int pi = -1;
   for (int t = 0; t < a.beam; ++t) {
     float bs = -INFINITY; int bi = 0x7fffffff;
     for (int v = tid; v < a.V; v += BEAM_THREADS) {
-      const float lp = x[v] - lse;
-      const float s = use_pen ? (cur + lp) / pen : cur + lp;
+      const float s = row.score(x[v] - lse);
       const bool eligible = (t == 0) || s < ps || (s == ps && v > pi);
       if (eligible && better(s, v, bs, bi)) { bs = s; bi = v; }
     }
-    wave_best(bs, bi);
-    __syncthreads();  // previous round's reads of red_* are done
-    if (lane == 0) { red_f[wv] = bs; red_i[wv] = bi; }
-    __syncthreads();
-    bs = red_f[0]; bi = red_i[0];
-#pragma unroll
-    for (int k = 1; k < BEAM_THREADS / 64; ++k)
-      if (better(red_f[k], red_i[k], bs, bi)) { bs = red_f[k]; bi = red_i[k]; }
+    block_best<WAVES>(bs, bi, red_f, red_i, lane, wv);
     ps = bs; pi = bi;
-    if (tid == 0) { cs[t] = bs; ci[t] = (bi == 0x7fffffff) ? t : bi; }  // (no finite score left, e.g. NaN logits: a valid index)
+    if (tid == 0) { row.cs[t] = bs; row.ci[t] = (bi == 0x7fffffff) ? t : bi; }  // (no finite score left, e.g. NaN logits: a valid index)
   }
 }
 
@@ -75,65 +78,34 @@ constexpr int FAST_THREADS = 1024;
 // equal scores -- and K rounds of a block arg-best over the threads' list heads pick the row's K best in order.
 template <int K>
 __global__ __launch_bounds__(FAST_THREADS) void beam_row_topk_fast_kernel(imt_beam_args a) {
-  __shared__ float red_f[FAST_THREADS / 64];
-  __shared__ float red_g[FAST_THREADS / 64];
-  __shared__ int red_i[FAST_THREADS / 64];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int b = r / a.rep;
-  const float* x = a.logits + (int64_t)r * a.ld;
-  const float cur = a.scores_in[r];
-  const bool use_pen = a.beam > 1;
-  const float pen = use_pen ? powf((a.sizes_in[r] + 6.0f) / 6.0f, a.len_penalty_ratio) : 1.0f;
-  const bool masked = a.eos_in[r] || (a.step > 1 && a.max_lens[b] < (int64_t)a.step + 1);
-  float* cs = a.cand_scores + (int64_t)r * a.beam;
-  int* ci = a.cand_idx + (int64_t)r * a.beam;
-  if (masked) {
-    const float s = use_pen ? (cur + 0.0f) / pen : cur + 0.0f;
-    for (int t = tid; t < a.beam; t += FAST_THREADS) { cs[t] = s; ci[t] = t; }
-    return;
-  }
-  const int V4 = a.V & ~3;
-  // pass A: online max / sum-exp
-  // NS sweeps of the row are REQUESTED together before the first is consumed (clamped addresses, the value masked where used): one
-  // sweep per loop trip was a chain of ~8 exposed load latencies per pass -- 41 us per row where the row's 120 KB take ~1 us to stream
-  constexpr int NS = 4;
+  constexpr int WAVES = FAST_THREADS / 64;
+  __shared__ float red_f[WAVES];
+  __shared__ float red_g[WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const BeamRow row = beam_row<FAST_THREADS>(a, blockIdx.x, tid);
+  if (row.finished) return;
+  // pass A: online max / sum-exp, a quad's maximum first and then its four exponentials
   float m = -INFINITY, l = 0.f;
-  for (int v0 = tid * 4; v0 < V4; v0 += NS * FAST_THREADS * 4) {
-    f32x4 qs[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) qs[s] = *reinterpret_cast<const f32x4*>(x + min(v0 + s * FAST_THREADS * 4, V4 - 4));
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (v0 + s * FAST_THREADS * 4 < V4) {
-        const f32x4 q = qs[s];
-        const float qm = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3]));
-        if (qm > m) { l *= __expf(m - qm); m = qm; }
-        l += __expf(q[0] - m) + __expf(q[1] - m) + __expf(q[2] - m) + __expf(q[3] - m);
-      }
+  sweep_row<FAST_THREADS, true>(row.x, a.V, tid, [&](f32x4 q, int, bool ok) {
+    if (ok) {
+      const float qm = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3]));
+      if (qm > m) { l *= __expf(m - qm); m = qm; }
+      l += __expf(q[0] - m) + __expf(q[1] - m) + __expf(q[2] - m) + __expf(q[3] - m);
     }
-  }
-  for (int v = V4 + tid; v < a.V; v += FAST_THREADS) {
-    const float q = x[v];
-    if (q > m) { l *= __expf(m - q); m = q; }
-    l += __expf(q - m);
-  }
-  float mx = wave_max(m);
-  if (lane == 0) red_f[wv] = mx;
-  __syncthreads();
-  mx = red_f[0];
-#pragma unroll
-  for (int k = 1; k < FAST_THREADS / 64; ++k) mx = fmaxf(mx, red_f[k]);
-  float sum = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
-  if (lane == 0) red_g[wv] = sum;
-  __syncthreads();
-  float tot = red_g[0];
-#pragma unroll
-  for (int k = 1; k < FAST_THREADS / 64; ++k) tot += red_g[k];
-  const float lse = mx + logf(tot);
+  }, [&](float q, int, bool ok) {
+    if (ok) {
+      if (q > m) { l *= __expf(m - q); m = q; }
+      l += __expf(q - m);
+    }
+  });
+  const float lse = block_lse<WAVES>(m, l, red_f, red_g, lane, wv);
   // pass B: per-thread top-K
   float ls[K]; int li[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) { ls[k] = -INFINITY; li[k] = 0x7fffffff; }
+  const float* x = row.x;
+  const float cur = row.cur, pen = row.pen;
+  const bool use_pen = row.use_pen;
   auto offer = [&](float q, int v) {
     const float lp = q - lse;
     const float sc = use_pen ? (cur + lp) / pen : cur + lp;
@@ -149,12 +121,15 @@ __global__ __launch_bounds__(FAST_THREADS) void beam_row_topk_fast_kernel(imt_be
       if (!placed) { ls[0] = sc; li[0] = v; }
     }
   };
-  for (int v0 = tid * 4; v0 < V4; v0 += NS * FAST_THREADS * 4) {
-    f32x4 qs[NS];
+  // sweep_row's loop, written out: through sweep_row (element or quad functor) this pass measured 40 us per launch against 35 us
+  // (320 rows x 30000, beam 5) with the same loads and waits in the ISA; the cause is not found, so the loop stays as it was
+  const int V4 = a.V & ~3;
+  for (int v0 = tid * 4; v0 < V4; v0 += SWEEP_NS * FAST_THREADS * 4) {
+    f32x4 qs[SWEEP_NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s) qs[s] = *reinterpret_cast<const f32x4*>(x + min(v0 + s * FAST_THREADS * 4, V4 - 4));
+    for (int s = 0; s < SWEEP_NS; ++s) qs[s] = *reinterpret_cast<const f32x4*>(x + min(v0 + s * FAST_THREADS * 4, V4 - 4));
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
+    for (int s = 0; s < SWEEP_NS; ++s) {
       const int v = v0 + s * FAST_THREADS * 4;
       if (v < V4) {
 #pragma unroll
@@ -164,53 +139,31 @@ __global__ __launch_bounds__(FAST_THREADS) void beam_row_topk_fast_kernel(imt_be
   }
   for (int v = V4 + tid; v < a.V; v += FAST_THREADS) offer(x[v], v);
   // The row's K best in two stages without a block-wide round per pick (each cost ~2.4 us on 16 waves: two barriers and a scan of 16
-  // LDS slots): (1) every wave picks ITS K best from its lanes' list heads -- butterfly arg-best, the owning lane pops -- and parks them;
-  // (2) one barrier, then wave 0 holds one parked list per lane and picks the row's K best the same way.  Same order as before:
-  // (score desc, index asc) at every comparison, indices are unique.
-  __shared__ float wl_s[FAST_THREADS / 64][K];
-  __shared__ int wl_i[FAST_THREADS / 64][K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    if (t < a.beam) {
-      float bs = ls[0]; int bi = li[0];
-      wave_best(bs, bi);
-      if (li[0] == bi && bi != 0x7fffffff) {  // this lane owned the winner: pop it
-#pragma unroll
-        for (int k = 0; k < K - 1; ++k) { ls[k] = ls[k + 1]; li[k] = li[k + 1]; }
-        ls[K - 1] = -INFINITY; li[K - 1] = 0x7fffffff;
-      }
-      if (lane == 0) { wl_s[wv][t] = bs; wl_i[wv][t] = bi; }
-    }
-  }
+  // LDS slots): (1) every wave picks ITS K best from its lanes' lists and parks them; (2) one barrier, then wave 0 holds one
+  // parked list per lane and picks the row's K best the same way.  Same order as before: (score desc, index asc) at every
+  // comparison, indices are unique.
+  __shared__ float wl_s[WAVES][K];
+  __shared__ int wl_i[WAVES][K];
+  wave_pop_best<K>(ls, li, a.beam, lane, [&](int t, float bs, int bi) { wl_s[wv][t] = bs; wl_i[wv][t] = bi; });
   __syncthreads();
   if (wv == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const bool have = lane < FAST_THREADS / 64 && k < a.beam;
+      const bool have = lane < WAVES && k < a.beam;
       ls[k] = have ? wl_s[lane][k] : -INFINITY;
       li[k] = have ? wl_i[lane][k] : 0x7fffffff;
     }
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      if (t < a.beam) {
-        float bs = ls[0]; int bi = li[0];
-        wave_best(bs, bi);
-        if (li[0] == bi && bi != 0x7fffffff) {
-#pragma unroll
-          for (int k = 0; k < K - 1; ++k) { ls[k] = ls[k + 1]; li[k] = li[k + 1]; }
-          ls[K - 1] = -INFINITY; li[K - 1] = 0x7fffffff;
-        }
-        if (lane == 0) { cs[t] = bs; ci[t] = (bi == 0x7fffffff) ? t : bi; }  // (no finite score left, e.g. NaN logits: a valid index)
-      }
-    }
+    wave_pop_best<K>(ls, li, a.beam, lane, [&](int t, float bs, int bi) {
+      row.cs[t] = bs; row.ci[t] = (bi == 0x7fffffff) ? t : bi;  // (no finite score left, e.g. NaN logits: a valid index)
+    });
   }
 }
 
 // Stage 2: one wave per sentence merges rep*beam candidates and does the bookkeeping.
 __global__ __launch_bounds__(64) void beam_merge_kernel(imt_beam_args a) {
-  __shared__ float top_s[MAX_BEAM];
-  __shared__ long long top_f[MAX_BEAM];
-  __shared__ int s_parent[MAX_BEAM];
+  __shared__ float top_s[MAX_HYPS];
+  __shared__ long long top_f[MAX_HYPS];
+  __shared__ int s_parent[MAX_HYPS];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int ncand = a.rep * a.beam;
   const float* cs = a.cand_scores + (int64_t)b * ncand;
@@ -238,37 +191,21 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(imt_beam_args a) {
     }
   }
   __syncthreads();
-  const bool over = a.step > 1 && a.max_lens[b] < (int64_t)a.step + 1;
   if (lane < a.beam) {
     const int t = lane;
     long long f = top_f[t];
-    if (a.step > 1) {
-      if (over) f = a.pad_idx;                            // :205-207
-      if (a.eos_in[(int64_t)b * a.rep + t]) f = a.pad_idx;  // :211-212 (old row's flag applied to the new slot)
-    }
+    // :205-207, :211-212 (the old row's flag applied to the new slot)
+    if (a.step > 1 && row_finished(a, b * a.rep + t, b)) f = a.pad_idx;
     const int parent = (a.step > 1) ? (int)(f / a.V) : 0;  // :216 (floor division)
     const long long word = f % a.V;
     const int prow = b * a.rep + parent;
     const int orow = b * a.beam + t;
     s_parent[t] = prow;
-    a.scores_out[orow] = top_s[t];
     if (a.beam > 1) a.sizes_out[orow] = a.sizes_in[prow] + (word != a.pad_idx ? 1.0f : 0.0f);
-    const bool has_eos = a.eos_in[prow] || word == a.eos;
-    a.eos_out[orow] = has_eos ? 1 : 0;
-    a.parent_out[orow] = prow;
-    a.tokens_out[orow] = word;
-    a.hist_out[(int64_t)orow * a.t_max + a.step] = word;
-    if (a.slots_out && a.step < a.t_max) a.slots_out[(int64_t)orow * a.t_max + a.step] = orow;
-    if (a.eos_count && has_eos) atomicAdd(a.eos_count + a.step, 1);
+    commit_hypothesis(a, orow, prow, word, top_s[t], a.eos_in[prow] || word == a.eos);
   }
   __syncthreads();
-  for (int t = 0; t < a.beam; ++t) {
-    const int prow = s_parent[t], orow = b * a.beam + t;
-    for (int j = lane; j < a.step; j += 64) {
-      a.hist_out[(int64_t)orow * a.t_max + j] = a.hist_in[(int64_t)prow * a.t_max + j];
-      if (a.slots_out) a.slots_out[(int64_t)orow * a.t_max + j] = a.slots_in[(int64_t)prow * a.t_max + j];
-    }
-  }
+  for (int t = 0; t < a.beam; ++t) copy_history(a, b * a.beam + t, s_parent[t], lane, 64);
 }
 
 }  // namespace
@@ -300,15 +237,11 @@ extern "C" int imt_attention_decode(const imt_attn_decode_args* a, void* stream)
 
 extern "C" int imt_beam_step(const imt_beam_args* a, void* stream) {
   IMT_CHECK_ARG(a, "beam_step: null args");
-  IMT_CHECK_ARG(a->B > 0 && a->beam > 0 && a->beam <= MAX_BEAM && a->V >= a->beam, "beam_step: beam %d out of range (1..%d, <= V)", a->beam, MAX_BEAM);
-  IMT_CHECK_ARG(a->rep == 1 || a->rep == a->beam, "beam_step: rep must be 1 (first step) or beam");
-  IMT_CHECK_ARG(a->step >= 1 && a->step < a->t_max, "beam_step: step %d outside [1, t_max=%d)", a->step, a->t_max);
-  IMT_CHECK_ARG(a->step == 1 || a->rep == a->beam, "beam_step: only the first step may have rep == 1");
+  IMT_CHECK_ARG(a->B > 0 && a->beam > 0 && a->beam <= MAX_HYPS && a->V >= a->beam, "beam_step: beam %d out of range (1..%d, <= V)", a->beam, MAX_HYPS);
+  if (const int err = check_search_args(a, "beam_step", a->beam, "beam")) return err;
   IMT_CHECK_ARG(a->pad_idx >= 0 && a->pad_idx < (int64_t)a->beam * a->V, "beam_step: pad_idx out of range");
-  IMT_CHECK_ARG(a->logits && a->scores_in && a->eos_in && a->max_lens && a->hist_in && a->cand_scores && a->cand_idx, "beam_step: null input");
+  IMT_CHECK_ARG(a->cand_scores && a->cand_idx, "beam_step: null input");
   IMT_CHECK_ARG(a->beam == 1 || (a->sizes_in && a->sizes_out), "beam_step: sizes required for beam > 1");
-  IMT_CHECK_ARG(a->scores_out && a->eos_out && a->hist_out && a->parent_out && a->tokens_out, "beam_step: null output");
-  IMT_CHECK_ARG((a->slots_in == nullptr) == (a->slots_out == nullptr), "beam_step: slots_in/slots_out must both be given or both NULL");
   hipStream_t st = (hipStream_t)stream;
   const int rows = a->B * a->rep;
   {

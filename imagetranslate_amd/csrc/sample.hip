@@ -12,13 +12,12 @@
 // 2 sweeps without a filter, 5 with one (6 with ties at the k-th place).  No floating-point atomics, no prefix sums over
 // probabilities, nothing crosses workgroups but the integer eos_count: the same input gives the same bits.
 #include "common.hpp"
+#include "search_step.hpp"
 
 namespace {
 
 constexpr int SAMPLE_THREADS = 1024;
 constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
-constexpr int MAX_SAMPLES = 32;  // MAX_BEAM of decode.hip: one search state serves both steps
-constexpr int NS = 4;            // sweeps of the row requested together (decode.hip: beam_row_topk_fast_kernel)
 
 // larger float <=> larger key; -0 is folded into +0 first (they compare equal and must share a key)
 IMT_DEVICE uint32_t order_key(float x) {
@@ -26,44 +25,9 @@ IMT_DEVICE uint32_t order_key(float x) {
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-// f(value, index, valid) for every index of [0, V) exactly once over the workgroup, in increasing index order per thread, from
-// wave-uniform control flow (`valid` is false on the clamped re-reads past the end).  VEC: 16-byte loads (row 16-byte aligned).
-template <bool VEC, typename F>
-IMT_DEVICE void sweep_row(const float* __restrict__ x, int V, int tid, F&& f) {
-  if (VEC) {
-    const int V4 = V & ~3;
-    for (int base = 0; base < V4; base += NS * SAMPLE_THREADS * 4) {
-      f32x4 qs[NS];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) qs[s] = *reinterpret_cast<const f32x4*>(x + min(base + (s * SAMPLE_THREADS + tid) * 4, V4 - 4));
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int v = base + (s * SAMPLE_THREADS + tid) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f(qs[s][e], v + e, v < V4);
-      }
-    }
-    if (V4 < V) {  // up to three elements
-      const int v = V4 + tid;
-      f(x[min(v, V - 1)], v, v < V);
-    }
-  } else {
-    for (int base = 0; base < V; base += NS * SAMPLE_THREADS) {
-      float qs[NS];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) qs[s] = x[min(base + s * SAMPLE_THREADS + tid, V - 1)];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int v = base + s * SAMPLE_THREADS + tid;
-        f(qs[s], v, v < V);
-      }
-    }
-  }
-}
-
 // hist[digit] += 1 for every lane with `active`.  The leading digit of logits is shared by most of a wave (sign and exponent), and
 // 64 lanes adding to one LDS word serialise: two rounds in which the first active lane adds the count of all lanes that hold ITS
-// digit take those off; what is left goes one by one.  Call from wave-uniform control flow.
+// digit take those off; what is left goes one by one.  Lanes that are not in the call count as inactive.
 IMT_DEVICE void hist_add(uint32_t* hist, bool active, uint32_t digit, int lane) {
 #pragma unroll
   for (int round = 0; round < 2; ++round) {
@@ -92,7 +56,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
   const int prow = b * a.rep + (a.rep == 1 ? 0 : k);
   const float* x = a.logits + (int64_t)prow * a.ld;
   const int V = a.V;
-  const bool masked = a.eos_in[prow] || (a.step > 1 && a.max_lens[b] < (int64_t)a.step + 1);
+  const bool masked = row_finished(a, prow, b);
   const bool select = a.topk > 0 && a.topk < V;
 
   int64_t token = a.pad_idx;
@@ -104,26 +68,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
       __syncthreads();
     }
     float m = -INFINITY, l = 0.f;
-    sweep_row<VEC>(x, V, tid, [&](float q, int v, bool ok) {
+    sweep_row<SAMPLE_THREADS, VEC>(x, V, tid, [&](float q, int v, bool ok) {
       if (ok) {
         if (q > m) { l *= __expf(m - q); m = q; }
         l += __expf(q - m);
       }
       if (select) hist_add(hist, ok, order_key(q) >> 24, lane);
     });
-    float mx = wave_max(m);
-    if (lane == 0) red_f[wv] = mx;
-    __syncthreads();
-    mx = red_f[0];
-#pragma unroll
-    for (int w = 1; w < SAMPLE_WAVES; ++w) mx = fmaxf(mx, red_f[w]);
-    const float part = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
-    if (lane == 0) red_g[wv] = part;
-    __syncthreads();
-    float tot = red_g[0];
-#pragma unroll
-    for (int w = 1; w < SAMPLE_WAVES; ++w) tot += red_g[w];
-    const float lse = mx + logf(tot);
+    const float lse = block_lse<SAMPLE_WAVES>(m, l, red_f, red_g, lane, wv);
 
     // ---- select: the key of the topk-th largest logit, and how many of the logits equal to it are kept
     uint32_t thr = 0;          // kept: key > thr, or key == thr and index <= cutoff
@@ -134,7 +86,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
         if (shift < 24) {
           for (int i = tid; i < 256; i += SAMPLE_THREADS) hist[i] = 0;
           __syncthreads();
-          sweep_row<VEC>(x, V, tid, [&](float q, int v, bool ok) {
+          sweep_row<SAMPLE_THREADS, VEC>(x, V, tid, [&](float q, int v, bool ok) {
             const uint32_t key = order_key(q);
             hist_add(hist, ok && (key >> (shift + 8)) == prefix, (key >> shift) & 255u, lane);
           });
@@ -204,7 +156,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
     // ---- draw: Gumbel-max over the kept set
     const uint32_t idx0 = (uint32_t)orow * (uint32_t)V;  // host: B*n*V < 2^32
     float bs = -INFINITY; int bi = 0x7fffffff;
-    sweep_row<VEC>(x, V, tid, [&](float q, int v, bool ok) {
+    sweep_row<SAMPLE_THREADS, VEC>(x, V, tid, [&](float q, int v, bool ok) {
       if (ok && select) {
         const uint32_t key = order_key(q);
         ok = key > thr || (key == thr && v <= cutoff);
@@ -215,34 +167,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
         if (better(val, v, bs, bi)) { bs = val; bi = v; }
       }
     });
-    wave_best(bs, bi);
-    __syncthreads();  // red_f / red_i reads above are done
-    if (lane == 0) { red_f[wv] = bs; red_i[wv] = bi; }
-    __syncthreads();
-    bs = red_f[0]; bi = red_i[0];
-#pragma unroll
-    for (int w = 1; w < SAMPLE_WAVES; ++w)
-      if (better(red_f[w], red_i[w], bs, bi)) { bs = red_f[w]; bi = red_i[w]; }
+    block_best<SAMPLE_WAVES>(bs, bi, red_f, red_i, lane, wv);
     if ((unsigned)bi >= (unsigned)V) bi = 0;  // no comparable value (NaN logits): a valid index, the hypothesis is garbage either way
     token = bi;
     score += x[bi] - lse;
   }
 
-  // ---- bookkeeping, as beam_merge_kernel
-  if (tid == 0) {
-    const bool has_eos = masked ? (a.eos_in[prow] != 0) : (a.eos_in[prow] || token == a.eos);
-    a.scores_out[orow] = score;
-    a.eos_out[orow] = has_eos ? 1 : 0;
-    a.parent_out[orow] = prow;
-    a.tokens_out[orow] = token;
-    a.hist_out[(int64_t)orow * a.t_max + a.step] = token;
-    if (a.slots_out) a.slots_out[(int64_t)orow * a.t_max + a.step] = orow;  // step < t_max (host)
-    if (a.eos_count && has_eos) atomicAdd(a.eos_count + a.step, 1);
-  }
-  for (int j = tid; j < a.step; j += SAMPLE_THREADS) {
-    a.hist_out[(int64_t)orow * a.t_max + j] = a.hist_in[(int64_t)prow * a.t_max + j];
-    if (a.slots_out) a.slots_out[(int64_t)orow * a.t_max + j] = a.slots_in[(int64_t)prow * a.t_max + j];
-  }
+  if (tid == 0) commit_hypothesis(a, orow, prow, token, score, masked ? (a.eos_in[prow] != 0) : (a.eos_in[prow] || token == a.eos));
+  copy_history(a, orow, prow, tid, SAMPLE_THREADS);
 }
 
 }  // namespace
@@ -250,17 +182,12 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_step_kernel(imt_sample_
 extern "C" int imt_sample_step(const imt_sample_args* a, void* stream) {
   IMT_CHECK_ARG(a, "sample_step: null args");
   IMT_CHECK_ARG(a->B > 0 && a->V > 0 && a->V <= (1 << 30), "sample_step: bad sizes (B %d, V %d)", a->B, a->V);
-  IMT_CHECK_ARG(a->n > 0 && a->n <= MAX_SAMPLES, "sample_step: n %d out of range (1..%d)", a->n, MAX_SAMPLES);
-  IMT_CHECK_ARG(a->rep == 1 || a->rep == a->n, "sample_step: rep must be 1 (first step) or n");
-  IMT_CHECK_ARG(a->step >= 1 && a->step < a->t_max, "sample_step: step %d outside [1, t_max=%d)", a->step, a->t_max);
-  IMT_CHECK_ARG(a->step == 1 || a->rep == a->n, "sample_step: only the first step may have rep == 1");
+  IMT_CHECK_ARG(a->n > 0 && a->n <= MAX_HYPS, "sample_step: n %d out of range (1..%d)", a->n, MAX_HYPS);
+  if (const int err = check_search_args(a, "sample_step", a->n, "n")) return err;
   IMT_CHECK_ARG(a->temperature > 0.f && a->temperature <= 3.402823466e+38f, "sample_step: temperature must be positive and finite");
   IMT_CHECK_ARG((int64_t)a->B * a->n * a->V < (1ll << 32), "sample_step: B*n*V must stay below 2^32 (the noise index is 32 bits)");
   IMT_CHECK_ARG(a->ld >= a->V, "sample_step: ld smaller than V");
   IMT_CHECK_ARG(a->pad_idx >= 0 && a->eos >= 0, "sample_step: pad_idx / eos negative");
-  IMT_CHECK_ARG(a->logits && a->scores_in && a->eos_in && a->max_lens && a->hist_in, "sample_step: null input");
-  IMT_CHECK_ARG(a->scores_out && a->eos_out && a->hist_out && a->parent_out && a->tokens_out, "sample_step: null output");
-  IMT_CHECK_ARG((a->slots_in == nullptr) == (a->slots_out == nullptr), "sample_step: slots_in/slots_out must both be given or both NULL");
   hipStream_t st = (hipStream_t)stream;
   const int rows = a->B * a->n;
   const bool select = a->topk > 0 && a->topk < a->V;

@@ -50,40 +50,40 @@ def get_outputs_until_eos(eos, outputs, size_limit=None, remove_first_token: boo
     return cut
 
 
-class _BeamState:
-    """Device-resident ping-pong state of one search (all sizes fixed up front: r_max = B*beam rows), seeded with the first
-    tokens; ``cur`` is the side the next step reads.  ``args``: the ``BeamArgs`` with the sizes and this state's fixed pointers."""
+class _SearchState:
+    """Device-resident state of one search (all sizes fixed up front: r_max = B*width rows), seeded with the first tokens.  The
+    buffers named in ``pingpong`` come in pairs: a step reads side ``cur`` and writes the other.  ``args``: the step's args
+    struct with the sizes and this state's fixed pointers."""
 
-    def __init__(self, first_tokens, eos, beam, t_max, use_slots):
+    def __init__(self, args, first_tokens, eos, width, t_max, use_slots):
         B, device = first_tokens.numel(), first_tokens.device
-        r = B * beam
+        r = B * width
         i64, i32, f32, u8 = torch.int64, torch.int32, torch.float32, torch.uint8
-        z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=device)
-        self.B, self.beam, self.t_max = B, beam, t_max
+        self.zeros = z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=device)
+        self.B, self.beam, self.t_max = B, width, t_max
         self.hist = [z(r, t_max, dtype=i64), z(r, t_max, dtype=i64)]
         self.slots = [z(r, t_max, dtype=i32), z(r, t_max, dtype=i32)] if use_slots else [None, None]
         self.scores = [z(r, dtype=f32), z(r, dtype=f32)]
-        self.sizes = [z(r, dtype=f32), z(r, dtype=f32)]
         self.eos = [z(r, dtype=u8), z(r, dtype=u8)]
-        self.cand_scores, self.cand_idx = z(r, beam, dtype=f32), z(r, beam, dtype=i32)
         self.parent, self.tokens, self.eos_count = z(r, dtype=i32), z(r, dtype=i64), z(t_max, dtype=i32)
+        self.pingpong = ["hist", "slots", "scores", "eos"]
         self.cur = 0
         self.hist[0][:B, 0] = first_tokens
         self.eos[0][:B] = (first_tokens == eos).to(u8)
         if use_slots:
             self.slots[0][:B, 0] = torch.arange(B, dtype=i32, device=device)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self.sides = [[ptr(t[k]) for t in (self.scores, self.sizes, self.eos, self.hist, self.slots)] for k in (0, 1)]
-        self.args = a = L.BeamArgs()
-        a.B, a.beam, a.t_max, a.cand_scores, a.cand_idx = B, beam, t_max, ptr(self.cand_scores), ptr(self.cand_idx)
-        a.parent_out, a.tokens_out, a.eos_count = ptr(self.parent), ptr(self.tokens), ptr(self.eos_count)
+        self.args = a = args
+        a.B, a.t_max = B, t_max
+        a.parent_out, a.tokens_out, a.eos_count = self.parent.data_ptr(), self.tokens.data_ptr(), self.eos_count.data_ptr()
 
     def bind_step(self, rep, step):
         """``args`` for one step: it reads side ``cur`` and writes the other."""
         a = self.args
         a.rep, a.step = rep, step
-        a.scores_in, a.sizes_in, a.eos_in, a.hist_in, a.slots_in = self.sides[self.cur]
-        a.scores_out, a.sizes_out, a.eos_out, a.hist_out, a.slots_out = self.sides[self.cur ^ 1]
+        for name in self.pingpong:
+            src, dst = getattr(self, name)[self.cur], getattr(self, name)[self.cur ^ 1]
+            setattr(a, name + "_in", None if src is None else src.data_ptr())
+            setattr(a, name + "_out", None if dst is None else dst.data_ptr())
         return a
 
     def best(self, n_cols):
@@ -92,24 +92,27 @@ class _BeamState:
         return hist[:self.B, :1] if n_cols == 1 else hist.view(self.B, self.beam, self.t_max)[:, 0, :n_cols]
 
 
-class _SampleState(_BeamState):
-    """The same state with ``nsamples`` for the beam, driven by ``imt_sample_step``: ``args`` is a ``SampleArgs`` (the hypothesis
-    sizes and the candidate workspace of the beam step stay unused)."""
+class _BeamState(_SearchState):
+    """The state ``imt_beam_step`` drives (``args``: a ``BeamArgs``): the hypothesis sizes of the length penalty and the candidate
+    workspace on top."""
+
+    def __init__(self, first_tokens, eos, beam, t_max, use_slots):
+        super().__init__(L.BeamArgs(), first_tokens, eos, beam, t_max, use_slots)
+        r, z = self.B * beam, self.zeros
+        self.sizes = [z(r, dtype=torch.float32), z(r, dtype=torch.float32)]
+        self.pingpong.append("sizes")
+        self.cand_scores, self.cand_idx = z(r, beam, dtype=torch.float32), z(r, beam, dtype=torch.int32)
+        a = self.args
+        a.beam, a.cand_scores, a.cand_idx = beam, self.cand_scores.data_ptr(), self.cand_idx.data_ptr()
+
+
+class _SampleState(_SearchState):
+    """The state ``imt_sample_step`` drives (``args``: a ``SampleArgs``), ``nsamples`` hypotheses per sentence (``beam``)."""
 
     def __init__(self, first_tokens, eos, nsamples, t_max, use_slots, temperature, topk, seed):
-        super().__init__(first_tokens, eos, nsamples, t_max, use_slots)
-        beam_args, self.args = self.args, L.SampleArgs()
+        super().__init__(L.SampleArgs(), first_tokens, eos, nsamples, t_max, use_slots)
         a = self.args
-        a.B, a.n, a.t_max = self.B, nsamples, t_max
-        a.parent_out, a.tokens_out, a.eos_count = beam_args.parent_out, beam_args.tokens_out, beam_args.eos_count
-        a.temperature, a.topk, a.seed = float(temperature), int(topk), int(seed)
-
-    def bind_step(self, rep, step):
-        a = self.args
-        a.rep, a.step = rep, step
-        a.scores_in, _, a.eos_in, a.hist_in, a.slots_in = self.sides[self.cur]
-        a.scores_out, _, a.eos_out, a.hist_out, a.slots_out = self.sides[self.cur ^ 1]
-        return a
+        a.n, a.temperature, a.topk, a.seed = nsamples, float(temperature), int(topk), int(seed)
 
     def all_rows(self, n_cols):
         """Every hypothesis, sentence-major (sample k of sentence b in row b * nsamples + k), ``n_cols`` columns."""

@@ -726,7 +726,8 @@ int imt_beam_step(const imt_beam_args* a, void* stream);
  *   token         argmax over v in K of x[v] / temperature + g(v) by (value descending, index ascending): Gumbel-max, an
  *                 exact draw from softmax(x / temperature) restricted to K;
  *   score         scores_in[p] + x[token] - logsumexp(x): the MODEL's log-probability (temperature 1, whole vocabulary);
- *   bookkeeping   history, eos_out, slots_out, parent_out, tokens_out, eos_count[step] as in imt_beam_step.
+ *   bookkeeping   history, eos_out, slots_out, parent_out, tokens_out, eos_count[step]: commit_hypothesis / copy_history of
+ *                 csrc/search_step.hpp, the functions imt_beam_step calls.
  * Deterministic: no floating-point atomics, nothing crosses workgroups; two calls on the same input give the same bits. */
 typedef struct imt_sample_args {
   int32_t B, n, rep, V;            /* n samples per sentence (1..32); rep = 1 (only at step 1) or n */

@@ -15,46 +15,11 @@ import torch
 
 from tests.sample_oracle import sample_step_reference
 from tests.test_sample_host import FREQ_CAP, FREQ_CASES, FREQ_LOGITS, FREQ_ROWS, freq_case
-from tests.util import rel_err
+from tests.util import call_beam_step, call_sample_step, rel_err
 
 pytestmark = pytest.mark.gpu
 GAP = 1e-4
 PAD, EOS = 0, 4
-
-
-def call_sample_step(logits, scores, eos_in, max_lens, hist, slots_in, step, B, n, rep, V, t_max, temperature, topk, seed,
-                     pad=PAD, eos=EOS, ld=None, offset=0, pad_fill=0.0):
-    """One imt_sample_step through the C ABI on copies of the given CPU tensors (the layout options of tests/util.call_beam_step:
-    rows ``ld`` floats apart starting ``offset`` floats into a 16-byte aligned buffer, columns [V, ld) hold ``pad_fill``)."""
-    import imagetranslate_amd.hip_ops as O
-    from imagetranslate_amd import _lib as L
-    dev = "cuda"
-    rows, r_out = B * rep, B * n
-    ld = V if ld is None else ld
-    assert ld >= V and logits.shape == (rows, V)
-    z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)
-    buf = torch.full((offset + rows * ld,), pad_fill, dtype=torch.float32, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d_logits = buf[offset:].view(rows, ld)
-    d_logits[:, :V] = logits.cuda()
-    d_scores, d_eos, d_max, d_hist = scores.cuda(), eos_in.to(torch.uint8).cuda(), max_lens.cuda(), hist.cuda()
-    d_slots = slots_in.cuda()
-    o_scores, o_eos = z(r_out, dtype=torch.float32), z(r_out, dtype=torch.uint8)
-    o_hist, o_slots = z(r_out, t_max, dtype=torch.int64), z(r_out, t_max, dtype=torch.int32)
-    o_parent, o_tok, cnt = z(r_out, dtype=torch.int32), z(r_out, dtype=torch.int64), z(t_max, dtype=torch.int32)
-    a = L.SampleArgs()
-    a.B, a.n, a.rep, a.V, a.step, a.t_max = B, n, rep, V, step, t_max
-    a.logits, a.ld = d_logits.data_ptr(), ld
-    a.scores_in, a.eos_in, a.max_lens = d_scores.data_ptr(), d_eos.data_ptr(), d_max.data_ptr()
-    a.hist_in, a.slots_in = d_hist.data_ptr(), d_slots.data_ptr()
-    a.temperature, a.topk, a.seed, a.pad_idx, a.eos = temperature, topk, seed, pad, eos
-    a.scores_out, a.eos_out = o_scores.data_ptr(), o_eos.data_ptr()
-    a.hist_out, a.slots_out, a.parent_out, a.tokens_out = o_hist.data_ptr(), o_slots.data_ptr(), o_parent.data_ptr(), o_tok.data_ptr()
-    a.eos_count = cnt.data_ptr()
-    O.sample_step(a)
-    torch.cuda.synchronize()
-    return dict(scores=o_scores.cpu(), eos=o_eos.cpu(), hist=o_hist.cpu(), slots=o_slots.cpu(), parent=o_parent.cpu(),
-                tokens=o_tok.cpu(), eos_count=cnt.cpu())
 
 
 def compare(got, ref, step, what, max_left_out=0.0):
@@ -232,3 +197,54 @@ def test_frequencies(cuda, temperature, topk, seed):
     print("T %.1f topk %d seed %d: largest deviation %.4f" % (temperature, topk, seed, dev))
     assert set(got["tokens"].tolist()) <= set(kept), "a draw outside the kept set"
     assert dev <= FREQ_CAP, dev
+
+
+# ------------------------------------------------------------------------------------------- what the two steps share
+# V = 7: one quad and the tail; 4099 / 16389: the first indices of the scalar / the 16-byte sweep's second trip, and a tail
+@pytest.mark.parametrize("V", [7, 4099, 16389])
+@pytest.mark.parametrize("vec", [False, True])  # rows V apart (odd: the scalar kernels) or padded to 16 bytes (the 16-byte ones)
+@pytest.mark.parametrize("step", [1, 3])
+def test_greedy_sampling_is_beam_one(cuda, step, vec, V):
+    """imt_beam_step with beam = 1 and imt_sample_step with n = 1, topk = 1 are the same greedy step: every integer output
+    equal, the scores within the 1e-5 of compare() (the two kernels round the log-sum-exp differently)."""
+    layout = dict(ld=(V + 3) // 4 * 4 if vec else V, pad_fill=float("nan"))
+    B, t_max = 5, 8
+    logits = torch.randn(B, V, generator=torch.Generator().manual_seed(100 * step + V)) * 3
+    logits[2, EOS] = logits[2].max() + 1.0                      # a row whose argmax is EOS
+    eos_in = torch.tensor([1, 0, 0, 0, 0], dtype=torch.uint8)   # a finished row
+    max_lens = torch.tensor([100, 2, 100, 100, 100])            # sentence 1 is past its limit at step 3 (step 1 does not look)
+    live = [b for b in range(B) if not (eos_in[b] or (step > 1 and max_lens[b] < step + 1))]
+    top2 = logits[live].topk(2, dim=1).values
+    assert bool((top2[:, 0] > top2[:, 1]).all()), "the argmax of every live row must be decided"
+    scores, _, hist, slots = _fresh(B, t_max, step)
+    beam = call_beam_step(logits, scores, torch.zeros(B), eos_in, max_lens, hist, slots, step, B, 1, 1, V, t_max, 0.8, PAD, EOS,
+                          **layout)
+    samp = call_sample_step(logits, scores, eos_in, max_lens, hist, slots, step, B, 1, 1, V, t_max, 0.7, 1, 41, **layout)
+    for key in ("tokens", "eos", "parent", "eos_count"):
+        assert torch.equal(samp[key], beam[key]), key
+    for key in ("hist", "slots"):
+        assert torch.equal(samp[key][:, :step + 1], beam[key][:, :step + 1]), key
+    e = rel_err(samp["scores"], beam["scores"])
+    print("step %d V %d: scores differ by %.3e" % (step, V, e))
+    assert e <= 1e-5, e
+    want = torch.full((B,), PAD, dtype=torch.int64)
+    want[live] = logits[live].argmax(dim=1)
+    assert torch.equal(beam["tokens"], want) and int(beam["tokens"][2]) == EOS
+    want_eos = eos_in.bool() | (want == EOS)
+    assert torch.equal(beam["eos"].bool(), want_eos) and int(beam["eos_count"][step]) == int(want_eos.sum())
+
+
+def test_sample_step_history_past_1024_positions(cuda):
+    """The sampling kernel copies history and slot rows 1024 positions per trip: step 1026 is the first with a second trip.
+    Columns past the step keep what the output buffers held."""
+    n, V, t_max, step, fill = 2, 8, 1030, 1026, -7
+    g = torch.Generator().manual_seed(9)
+    hist, slots = torch.zeros(n, t_max, dtype=torch.int64), torch.zeros(n, t_max, dtype=torch.int32)
+    hist[:, :step] = torch.randint(5, 1000, (n, step), generator=g)
+    slots[:, :step] = torch.randint(0, n, (n, step), generator=g, dtype=torch.int32)
+    got = call_sample_step(torch.randn(n, V, generator=g) * 3, torch.zeros(n), torch.zeros(n, dtype=torch.uint8),
+                           torch.tensor([2000]), hist, slots, step, 1, n, n, V, t_max, 1.0, 0, 5, out_fill=fill)
+    assert got["parent"].tolist() == [0, 1]
+    assert torch.equal(got["hist"][:, :step], hist[:, :step]) and torch.equal(got["slots"][:, :step], slots[:, :step])
+    assert torch.equal(got["hist"][:, step], got["tokens"]) and got["slots"][:, step].tolist() == [0, 1]
+    assert bool((got["hist"][:, step + 1:] == fill).all()) and bool((got["slots"][:, step + 1:] == fill).all())

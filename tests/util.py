@@ -191,15 +191,15 @@ def beam_reference_is_unambiguous(vals, beam, gap=1e-4):
     return ok, smallest
 
 
-def call_beam_step(logits, scores, sizes, eos_in, max_lens, hist, slots_in, step, B, beam, rep, V, t_max, ratio, pad, eos,
-                   ld=None, offset=0, pad_fill=0.0):
-    """One imt_beam_step through the C ABI on copies of the given CPU tensors; returns the output buffers.  The logits rows
-    are laid out ``ld`` (default V) floats apart in a device buffer, starting ``offset`` floats into it (the buffer itself
-    is 16-byte aligned); the columns [V, ld) of every row hold ``pad_fill``."""
-    import imagetranslate_amd.hip_ops as O
-    from imagetranslate_amd import _lib as L
+def bind_search_step(a, logits, scores, eos_in, max_lens, hist, slots_in, step, B, width, rep, V, t_max, pad, eos,
+                     ld=None, offset=0, pad_fill=0.0, out_fill=0):
+    """What imt_beam_args and imt_sample_args share (every field but the hypotheses per sentence -- ``width`` -- bears the same
+    name in both), set in ``a`` from copies of the given CPU tensors.  The logits rows are laid out ``ld`` (default V) floats
+    apart in a device buffer, starting ``offset`` floats into it (the buffer itself is 16-byte aligned); the columns [V, ld) of
+    every row hold ``pad_fill``.  The history and slot outputs start out as ``out_fill``, every other output as zero.  Returns
+    (the output buffers by name, the device inputs: keep them until the step has run)."""
     dev = "cuda"
-    rows, r_out = B * rep, B * beam
+    rows, r_out = B * rep, B * width
     ld = V if ld is None else ld
     assert ld >= V and logits.shape == (rows, V)
     z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)
@@ -207,24 +207,50 @@ def call_beam_step(logits, scores, sizes, eos_in, max_lens, hist, slots_in, step
     assert buf.data_ptr() % 16 == 0
     d_logits = buf[offset:].view(rows, ld)
     d_logits[:, :V] = logits.cuda()
-    d_scores, d_sizes = scores.cuda(), sizes.cuda()
-    d_eos, d_max, d_hist = eos_in.to(torch.uint8).cuda(), max_lens.cuda(), hist.cuda()
-    d_slots = slots_in.cuda()
-    cs, ci = z(rows, beam, dtype=torch.float32), z(rows, beam, dtype=torch.int32)
-    o_scores, o_sizes, o_eos = z(r_out, dtype=torch.float32), z(r_out, dtype=torch.float32), z(r_out, dtype=torch.uint8)
-    o_hist, o_slots = z(r_out, t_max, dtype=torch.int64), z(r_out, t_max, dtype=torch.int32)
-    o_parent, o_tok, cnt = z(r_out, dtype=torch.int32), z(r_out, dtype=torch.int64), z(t_max, dtype=torch.int32)
+    ins = dict(scores_in=scores.cuda(), eos_in=eos_in.to(torch.uint8).cuda(), max_lens=max_lens.cuda(), hist_in=hist.cuda(),
+               slots_in=slots_in.cuda())
+    outs = dict(scores=z(r_out, dtype=torch.float32), eos=z(r_out, dtype=torch.uint8),
+                hist=torch.full((r_out, t_max), out_fill, dtype=torch.int64, device=dev),
+                slots=torch.full((r_out, t_max), out_fill, dtype=torch.int32, device=dev),
+                parent=z(r_out, dtype=torch.int32), tokens=z(r_out, dtype=torch.int64), eos_count=z(t_max, dtype=torch.int32))
+    a.B, a.rep, a.V, a.step, a.t_max = B, rep, V, step, t_max
+    a.logits, a.ld, a.pad_idx, a.eos = d_logits.data_ptr(), ld, pad, eos
+    for name, t in ins.items():
+        setattr(a, name, t.data_ptr())
+    for name, t in outs.items():
+        setattr(a, name if name == "eos_count" else name + "_out", t.data_ptr())
+    return outs, (buf, ins)
+
+
+def call_beam_step(logits, scores, sizes, eos_in, max_lens, hist, slots_in, step, B, beam, rep, V, t_max, ratio, pad, eos,
+                   **layout):
+    """One imt_beam_step through the C ABI on copies of the given CPU tensors; returns the output buffers.  ``layout``: the
+    ``ld`` / ``offset`` / ``pad_fill`` / ``out_fill`` of bind_search_step."""
+    import imagetranslate_amd.hip_ops as O
+    from imagetranslate_amd import _lib as L
     a = L.BeamArgs()
-    a.B, a.beam, a.rep, a.V, a.step, a.t_max = B, beam, rep, V, step, t_max
-    a.logits, a.ld = d_logits.data_ptr(), ld
-    a.scores_in, a.sizes_in, a.eos_in = d_scores.data_ptr(), d_sizes.data_ptr(), d_eos.data_ptr()
-    a.max_lens, a.hist_in, a.slots_in = d_max.data_ptr(), d_hist.data_ptr(), d_slots.data_ptr()
-    a.len_penalty_ratio, a.pad_idx, a.eos = ratio, pad, eos
-    a.cand_scores, a.cand_idx = cs.data_ptr(), ci.data_ptr()
-    a.scores_out, a.sizes_out, a.eos_out = o_scores.data_ptr(), o_sizes.data_ptr(), o_eos.data_ptr()
-    a.hist_out, a.slots_out, a.parent_out, a.tokens_out = o_hist.data_ptr(), o_slots.data_ptr(), o_parent.data_ptr(), o_tok.data_ptr()
-    a.eos_count = cnt.data_ptr()
+    outs, keep = bind_search_step(a, logits, scores, eos_in, max_lens, hist, slots_in, step, B, beam, rep, V, t_max, pad, eos,
+                                  **layout)
+    d_sizes = sizes.cuda()
+    outs["sizes"] = torch.zeros(B * beam, dtype=torch.float32, device="cuda")
+    outs["cand_scores"] = torch.zeros(B * rep, beam, dtype=torch.float32, device="cuda")
+    outs["cand_idx"] = torch.zeros(B * rep, beam, dtype=torch.int32, device="cuda")
+    a.beam, a.len_penalty_ratio = beam, ratio
+    a.sizes_in, a.sizes_out = d_sizes.data_ptr(), outs["sizes"].data_ptr()
+    a.cand_scores, a.cand_idx = outs["cand_scores"].data_ptr(), outs["cand_idx"].data_ptr()
     O.beam_step(a)
     torch.cuda.synchronize()
-    return dict(scores=o_scores.cpu(), sizes=o_sizes.cpu(), eos=o_eos.cpu(), hist=o_hist.cpu(), slots=o_slots.cpu(),
-                parent=o_parent.cpu(), tokens=o_tok.cpu(), eos_count=cnt.cpu(), cand_idx=ci.cpu(), cand_scores=cs.cpu())
+    return {k: t.cpu() for k, t in outs.items()}
+
+
+def call_sample_step(logits, scores, eos_in, max_lens, hist, slots_in, step, B, n, rep, V, t_max, temperature, topk, seed,
+                     pad=0, eos=4, **layout):
+    """One imt_sample_step through the C ABI, as call_beam_step."""
+    import imagetranslate_amd.hip_ops as O
+    from imagetranslate_amd import _lib as L
+    a = L.SampleArgs()
+    outs, keep = bind_search_step(a, logits, scores, eos_in, max_lens, hist, slots_in, step, B, n, rep, V, t_max, pad, eos, **layout)
+    a.n, a.temperature, a.topk, a.seed = n, temperature, topk, seed
+    O.sample_step(a)
+    torch.cuda.synchronize()
+    return {k: t.cpu() for k, t in outs.items()}
