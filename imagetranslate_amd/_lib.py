@@ -166,6 +166,15 @@ class MassArgs(Structure):
     ]
 
 
+class MlmArgs(Structure):
+    _fields_ = [
+        ("n_rows", c_int32), ("width", c_int32), ("n_special", c_int32), ("vocab", c_int32),
+        ("mask_eos", c_int32), ("mask_prob", c_float), ("seed", c_uint64), ("mask_id", c_int64), ("eos_id", c_int64),
+        ("texts", c_void_p), ("pads", c_void_p), ("ld_pads", c_int64),
+        ("mask", c_void_p), ("idx", c_void_p), ("targets", c_void_p), ("count", c_void_p),
+    ]
+
+
 class ScoreArgs(Structure):
     _fields_ = [
         ("dtype", c_int32), ("N", c_int32), ("V", c_int32), ("K", c_int32),
@@ -282,6 +291,7 @@ SIGNATURES = {
     "imt_select_plan": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "imt_mass_mask": (c_int, [POINTER(MassArgs), _P]),
     "imt_mass_unmask": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+    "imt_mlm_mask": (c_int, [POINTER(MlmArgs), _P]),
 }
 
 _lib = None
@@ -295,7 +305,7 @@ ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_r
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
                "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs,
-               "imt_knn_args": KnnArgs}
+               "imt_knn_args": KnnArgs, "imt_mlm_args": MlmArgs}
 
 
 def load():

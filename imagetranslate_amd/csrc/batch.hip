@@ -127,7 +127,94 @@ __global__ __launch_bounds__(1024) void select_plan_kernel(const uint8_t* __rest
   if (tid == 0) count[0] = s_base;
 }
 
+// BERT masking for the masked language model (src/utils.py:19-38, include/imt_hip.h): the Bernoulli draw per token, the
+// 80/10/10 replacement in place and the ordered compaction of the masked positions (the reference's texts[mask]) in one
+// launch, shaped like select_plan_kernel above: one workgroup, chunks of 1024 x SEL_ITEMS positions, every id and pad byte
+// of a thread requested together (clamped), one block-wide exclusive scan per chunk.  A thread reads its own positions
+// before it writes them and the positions of two threads are disjoint, so the in-place update needs no barrier of its own.
+__global__ __launch_bounds__(1024) void mlm_mask_kernel(imt_mlm_args a) {
+  __shared__ int wave_tot[16];
+  __shared__ int s_base;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n = a.n_rows * a.width;
+  const int span = a.vocab - a.n_special;
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  // 64-bit walk: n may be anything below 2^31, so p0 + 16384 and a thread's positions past the end need not fit an int
+  for (int64_t p0 = 0; p0 < n; p0 += 1024 * SEL_ITEMS) {
+    uint8_t pd[SEL_ITEMS];
+    int64_t tok[SEL_ITEMS];
+    const int64_t first = p0 + tid * SEL_ITEMS;
+#pragma unroll
+    for (int k = 0; k < SEL_ITEMS; ++k) {
+      const int p = (int)min(first + k, (int64_t)n - 1);
+      const int b = p / a.width, t = p - b * a.width;
+      pd[k] = a.pads[(int64_t)b * a.ld_pads + t];
+      tok[k] = a.texts[p];
+    }
+    uint32_t sel = 0;
+#pragma unroll
+    for (int k = 0; k < SEL_ITEMS; ++k) {
+      const bool s = first + k < n && pd[k] != 0 && (a.mask_eos || tok[k] != a.eos_id) &&
+                     counter_uniform(a.seed, 4u, (uint32_t)(first + k)) < a.mask_prob;
+      sel |= (s ? 1u : 0u) << k;
+    }
+    const int mine = __popc(sel);
+    // exclusive scan of `mine` over the workgroup: inclusive wave scan by shuffles, wave totals through LDS
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    int off = s_base + incl - mine;
+    for (int k = 0; k < wv; ++k) off += wave_tot[k];
+#pragma unroll
+    for (int k = 0; k < SEL_ITEMS; ++k) {
+      const int64_t p = first + k;
+      if (p < n) a.mask[p] = (uint8_t)((sel >> k) & 1u);
+      if ((sel >> k) & 1u) {
+        a.idx[off] = (int32_t)p;
+        a.targets[off] = tok[k];
+        ++off;
+        const float u = counter_uniform(a.seed, 5u, (uint32_t)p);
+        if (u < 0.8f) a.texts[p] = a.mask_id;
+        else if (u < 0.9f) {
+          int r = (int)(counter_uniform(a.seed, 6u, (uint32_t)p) * (float)span);
+          if (r >= span) r = span - 1;
+          a.texts[p] = (int64_t)(a.n_special + r);
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int tot = s_base;
+      for (int k = 0; k < 16; ++k) tot += wave_tot[k];
+      s_base = tot;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) a.count[0] = s_base;
+}
+
 }  // namespace
+
+extern "C" int imt_mlm_mask(const imt_mlm_args* a, void* stream) {
+  IMT_CHECK_ARG(a, "mlm_mask: null args");
+  IMT_CHECK_ARG(a->n_rows > 0 && a->width > 0, "mlm_mask: bad sizes");
+  IMT_CHECK_ARG((int64_t)a->n_rows * a->width < (1ll << 31), "mlm_mask: too many positions");
+  IMT_CHECK_ARG(a->mask_prob > 0.f && a->mask_prob < 1.f, "mlm_mask: mask_prob must be in (0, 1)");
+  IMT_CHECK_ARG(a->vocab > a->n_special && a->n_special >= 0, "mlm_mask: vocabulary smaller than the special-token block");
+  IMT_CHECK_ARG(a->texts && a->pads && a->mask && a->idx && a->targets && a->count, "mlm_mask: null tensor");
+  IMT_CHECK_ARG(a->ld_pads >= a->width, "mlm_mask: pad rows overlap");
+  hipStream_t st = (hipStream_t)stream;
+  ImtProfScope prof("mlm_mask", 0, (double)a->n_rows * a->width * 18, st);
+  hipLaunchKernelGGL(mlm_mask_kernel, dim3(1), dim3(1024), 0, st, *a);
+  IMT_CHECK_LAUNCH();
+  return IMT_OK;
+}
 
 extern "C" int imt_select_plan(const uint8_t* mask, int64_t ld_mask, const int64_t* ids, int64_t ld_ids, int B, int T1, int col0,
                                int32_t* idx, int64_t* targets, int32_t* count, void* stream) {

@@ -16,6 +16,7 @@ ragged) are what the kernels see in real training.
 """
 import glob
 import marshal
+import os
 import random
 from typing import List, Optional
 
@@ -57,6 +58,50 @@ def get_lex_suggestions(lex_dict, ids, pad_idx: int) -> torch.Tensor:
 
 def _pad_proposals(lex: List[torch.Tensor], pad_idx: int) -> torch.Tensor:
     return pad_sequence(lex, batch_first=True, padding_value=pad_idx)
+
+
+class TextDataset(Dataset):
+    """Rows of the marshal blocks ``create_batches.write`` leaves in ``save_cache_dir`` (src/dataset.py:30-70): item ``i`` is
+    ``(ids, language index)`` from block ``i // block size``.  At most ``max_cache_size`` blocks are held: a row of a block that
+    is not held replaces the cache by that block and the ones after it.  ``load_all`` reads every block up front."""
+
+    def __init__(self, save_cache_dir: str, max_cache_size: int = 100, load_all: bool = False):
+        self.current_cache = {}
+        self.max_cache_size = max_cache_size
+        self.save_cache_dir = save_cache_dir
+        with open(os.path.join(save_cache_dir, "info.txt"), "r") as fr:
+            block, lines, files = fr.read().strip().split("\t")
+        self.sentence_block_size, self.line_num, self.file_count = int(block), int(lines), int(files)
+        if load_all:
+            self.rebuild_cache(0, self.file_count)
+
+    def __len__(self):
+        return self.line_num
+
+    def rebuild_cache(self, start_file_num: int, end_file_num: int):
+        self.current_cache = {}
+        for file_num in range(start_file_num, end_file_num):
+            with open(os.path.join(self.save_cache_dir, str(file_num) + ".pkl"), "rb") as fp:
+                self.current_cache[file_num] = marshal.load(fp)
+
+    def __getitem__(self, item):
+        if not 0 <= item < self.line_num:
+            raise IndexError(item)
+        file_num = item // self.sentence_block_size
+        if file_num not in self.current_cache:
+            self.rebuild_cache(file_num, min(self.file_count, file_num + self.max_cache_size))
+        return self.current_cache[file_num][item]
+
+
+class TextCollator:
+    """Rows of ``TextDataset`` -> {"texts" [B, S], "pad_mask" (True on real tokens), "langs" [B]} (src/dataset.py:479-490)."""
+
+    def __init__(self, pad_idx: int):
+        self.pad_idx = pad_idx
+
+    def __call__(self, batch):
+        texts = pad_sequence([torch.LongTensor(ids) for ids, _ in batch], batch_first=True, padding_value=self.pad_idx)
+        return {"texts": texts, "pad_mask": texts != self.pad_idx, "langs": torch.LongTensor([lang for _, lang in batch])}
 
 
 class MTDataset(Dataset):

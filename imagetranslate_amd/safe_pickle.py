@@ -35,6 +35,40 @@ def load_caption2image_config(path):
     return cfg
 
 
+_CONFIG_TYPES = (bool, int, float, str, type(None))
+
+
+def _check_lm_config(cfg, what):
+    if not isinstance(cfg, dict):
+        raise ValueError("%s: expected a dict of config fields, got %r" % (what, type(cfg)))
+    for k, v in cfg.items():
+        if not isinstance(k, str) or not isinstance(v, _CONFIG_TYPES):
+            raise ValueError("%s: config field %r holds %r; only bool / int / float / str / None values can be written and read "
+                             "back without executing anything" % (what, k, type(v)))
+    return cfg
+
+
+def save_lm_config(cfg: dict, path):
+    """Write the config fields of an LM as a pickled plain dict -- what ``load_lm_config`` reads.  A field whose value is not a
+    scalar is an error, not something to leave out: the file must give back the config it was written from."""
+    with open(path, "wb") as fp:
+        pickle.dump(dict(_check_lm_config(cfg, path)), fp)
+
+
+def load_lm_config(path):
+    """The ``config`` file of an LM directory as a plain dict of config fields.  ``lm.LM.save`` writes a dict; the reference pickles
+    a ``transformers.BertConfig`` instance (src/lm.py:60-61), which cannot be read without importing and running what the file
+    names -- such a file is refused."""
+    with open(path, "rb") as fp:
+        try:
+            cfg = load_plain(fp)
+        except pickle.UnpicklingError as err:
+            raise ValueError("%s holds a pickled object, not a plain dict of config fields (%s); a config pickled as a class "
+                             "instance would have to be executed to be read -- save the fields as a dict "
+                             "(pickle.dump(config.to_dict(), fp))" % (path, err)) from None
+    return _check_lm_config(cfg, path)
+
+
 def load_langs(path):
     with open(path, "rb") as fp:
         langs = load_plain(fp)

@@ -135,8 +135,8 @@ class SenSim(FlatStoreModel):
         return self.encoder.embeddings.word_embeddings.weight.device
 
     def init_from_lm(self, model):
-        """Adopt the encoder weights of a loaded ``Seq2Seq`` (src/sen_sim.py:33-34, what ``train_txt_sim --pretrained`` does).  The
-        values are copied into this model's flat store; the module is not rebound.  An encoder of another shape (layers, widths,
+        """Adopt the encoder weights of a loaded ``LM`` or ``Seq2Seq`` (src/sen_sim.py:33-34, what ``train_txt_sim --pretrained``
+        does): only ``model.encoder`` is read.  The values are copied into this model's flat store; the module is not rebound.  An encoder of another shape (layers, widths,
         vocabulary, positions, ``type_vocab_size``) or another head count is refused."""
         theirs, mine = model.encoder.state_dict(), self.encoder.state_dict()
         a = {k: tuple(v.shape) for k, v in theirs.items()}

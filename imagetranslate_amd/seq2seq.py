@@ -377,7 +377,30 @@ class Seq2Seq(FlatStoreModel):
 
     # ------------------------------------------------------------------ reference API
     def init_from_lm(self, lm):
-        raise NotImplementedError("init_from_lm depends on the reference's broken LM class (SURVEY section 2 #17)")
+        """Start from a masked language model (``lm.LM``; src/seq2seq.py:88-92): its encoder into ``self.encoder`` -- through the
+        existing ties that reaches the decoder's embeddings and, with equal depths, its shared self-attention -- and its
+        vocabulary projection (``masked_lm.layer``) into every output layer.  The rest of the decoder keeps its initialisation.
+        The values are copied into this model's flat store; no module is rebound.  An encoder of another shape (layers, widths,
+        vocabulary, positions, ``type_vocab_size``) or another head count is refused, naming the first differing key."""
+        theirs, mine = lm.encoder.state_dict(), self.encoder.state_dict()
+        a = {k: tuple(v.shape) for k, v in theirs.items()}
+        b = {k: tuple(v.shape) for k, v in mine.items()}
+        if a != b:
+            diff = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+            raise ValueError("Seq2Seq.init_from_lm: the encoder does not match (%s: %s there, %s here)"
+                             % (diff[0], a.get(diff[0]), b.get(diff[0])))
+        heads = int(lm.encoder.config.num_attention_heads)
+        if heads != int(self.config.num_attention_heads):
+            raise ValueError("Seq2Seq.init_from_lm: the encoder has %d attention heads, this model %d"
+                             % (heads, int(self.config.num_attention_heads)))
+        sd = {"encoder." + k: v for k, v in theirs.items()}
+        head = lm.masked_lm.layer
+        for name, mod in self.named_modules():
+            if isinstance(mod, BertOutputLayer):
+                sd[name + ".layer.weight"], sd[name + ".layer.bias"] = head.weight.detach(), head.bias.detach()
+        res = self.load_state_dict(sd, strict=False)
+        assert not res.unexpected_keys, res
+        return self
 
     def encode(self, src_inputs, src_mask, src_langs, images=None):
         device = self._device

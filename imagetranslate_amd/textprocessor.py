@@ -85,11 +85,19 @@ class TextProcessor:
                         if line.strip():
                             yield line.strip()  # no trailing newline: it would be learnt as a symbol
         self.tokenizer.train_from_iterator(lines(), vocab_size=vocab_size, min_frequency=5, special_tokens=self.special_tokens)
-        os.makedirs(to_save_dir, exist_ok=True)
-        self.tokenizer.save_model(to_save_dir)  # vocab.json + merges.txt (the reference's layout)
-        self.tokenizer.save(os.path.join(to_save_dir, "tokenizer.json"))
-        with open(os.path.join(to_save_dir, "langs"), "wb") as fp:
-            pickle.dump(self.languages, fp)
+        self.save(to_save_dir)
+
+    def save(self, directory):
+        """The tokenizer's files (src/textprocessor.py:42-45): vocab.json + merges.txt (the reference's layout), the complete
+        tokenizer as tokenizer.json, and ``langs``.  What ``TextProcessor(directory)`` reads back."""
+        os.makedirs(directory, exist_ok=True)
+        if hasattr(self.tokenizer, "save_model"):
+            self.tokenizer.save_model(directory)
+        else:  # a tokenizers.Tokenizer read from tokenizer.json: its model writes the two files
+            self.tokenizer.model.save(directory)
+        self.tokenizer.save(os.path.join(directory, "tokenizer.json"))
+        with open(os.path.join(directory, "langs"), "wb") as fp:
+            pickle.dump(dict(self.languages), fp)
 
     def pad_token_id(self) -> int: return self.tokenizer.token_to_id(self.pad_token)
     def mask_token_id(self) -> int: return self.tokenizer.token_to_id(self.mask_token)
@@ -114,6 +122,29 @@ class TextProcessor:
     def tokenize_one_sentence_with_langid(self, line, lang_id):
         """ids of ``line`` framed as [lang_id] ... </s> (src/textprocessor.py:74-76), truncated to 512."""
         return ([lang_id] + self.tokenizer.encode(line).ids + [self.token_id(self.sep_token)])[:512]
+
+    def tokenize_lines(self, line, blind_split: bool = True, split_len: int = 512):
+        """One document line -> int array [rows, split_len] (src/textprocessor.py:78-108, the ``blind_split`` branch, which is
+        all ``create_batches`` uses): with languages, every ``</s>``-separated sentence is framed as [language tag] ... </s> --
+        the tag is the line's first word when that begins with '<' --, the ids are concatenated, padded to the next multiple of
+        ``split_len`` and cut into rows wherever they fall.  As in the reference, a length that already is a multiple gets one
+        whole row of pads."""
+        import numpy as np
+        if not blind_split:
+            raise NotImplementedError("tokenize_lines: only blind_split=True is built (what create_batches uses)")
+        if len(self.languages) > 0:
+            sentences = [sen for sen in line.split("</s>") if len(sen.strip()) > 0]
+            tag = []
+            if sentences[0].startswith("<"):
+                words = sentences[0].strip().split(" ")
+                tag, sentences[0] = [self.token_id(words[0])], " ".join(words[1:])
+            ids = []
+            for sen in sentences:
+                ids += tag + self.tokenizer.encode(sen).ids + [self.sep_token_id()]
+        else:
+            ids = list(self.tokenizer.encode(line.strip()).ids)
+        ids += [self.pad_token_id()] * (split_len - len(ids) % split_len)
+        return np.array(ids).reshape((-1, split_len))
 
     def tokenize(self, lines):
         rows = [ln.strip() for ln in lines.strip().split("\n") if ln.strip()]

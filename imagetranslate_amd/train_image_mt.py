@@ -311,8 +311,11 @@ def run_phases(trainer, options, step, mt_train, mass_train, mt_dev=None, img_tr
 
 
 def train(options):
-    reject_off_path(options, dict_supported=True)
+    reject_off_path(options, lm_supported=True, dict_supported=True)
     resume = resume_dir_of(options)  # --resume DIR: the model is built from DIR as --pretrained builds it
+    if options.lm_path and (options.pretrained_path or resume):
+        raise ValueError("--lm %s with %s: a model loaded from a directory already has its weights; --lm initialises a fresh "
+                         "model from a masked language model" % (options.lm_path, "--resume" if resume else "--pretrained"))
     if getattr(options, "image_dir", "") and len([l for l in (options.bt_langs or "").split(",") if l.strip()]) >= 2 \
             and options.finetune_step > 0:
         raise NotImplementedError("--image with --langs / --fstep: back-translation over image batches (src/train_image_mt.py:108-198 "
@@ -333,6 +336,9 @@ def train(options):
                                  enc_layer=options.encoder_layer, dec_layer=options.decoder_layer, embed_dim=options.embed_dim,
                                  intermediate_dim=options.intermediate_layer_dim, num_attention_heads=options.heads,
                                  resnet_depth=options.resnet_depth, image_feat_dim=options.feat_dim)
+        if options.lm_path:  # (the reference builds a FRESH LM here and never reads the path, :449-452: DESIGN section 1)
+            from .lm import LM
+            model.init_from_lm(LM.load(options.lm_path))
     use_lex_dict(model, lex_dict, "train_image_mt")
     model.set_compute_dtype(torch.float32 if options.fp32 else torch.bfloat16)
     model = model.cuda().train()

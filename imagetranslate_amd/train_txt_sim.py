@@ -29,6 +29,15 @@ def draw_negative(seed: int, step: int, side: int, n_batches: int) -> int:
     return random.Random((int(seed) * 1000003 + int(step)) * 2 + int(side)).randrange(n_batches)
 
 
+def load_language_model(directory: str, tok_dir: str):
+    """The model ``--pretrained DIR`` names: a masked language model when DIR holds ``config`` (what ``LM.save`` writes), a
+    ``Seq2Seq`` when it holds ``mt_config``.  ``SenSim.init_from_lm`` reads only its ``.encoder``."""
+    if os.path.isfile(os.path.join(directory, "config")):
+        from .lm import LM
+        return LM.load(directory)
+    return Seq2Seq.load(Seq2Seq, directory, tok_dir=tok_dir)
+
+
 class SenSimTrainer(Trainer):
     unit = "Sentences"
 
@@ -115,7 +124,7 @@ class SenSimTrainer(Trainer):
             raise FileNotFoundError("--resume %s: no train_state.pt there" % options.resume_dir)
         if options.pretrained_path:  # (--pretrained is a language model here, not a SenSim: --resume does not replace it; the
             # model is built from the flags, the snapshot carries its weights and refuses another layout)
-            model.init_from_lm(Seq2Seq.load(Seq2Seq, options.pretrained_path, tok_dir=options.tokenizer_path))
+            model.init_from_lm(load_language_model(options.pretrained_path, options.tokenizer_path))
         return SenSimTrainer.run(options, model, tp)
 
     @staticmethod

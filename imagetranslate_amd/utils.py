@@ -1,7 +1,8 @@
 """Trainer-side pieces of the path -- drop-in for the parts of the reference's ``src/utils.py`` that sit inside the
 timed train step: ``build_optimizer`` (:14-16), ``AdamInverseSqrtWithWarmup`` (:105-156), gradient clipping
 (``train_image_mt.py:291``), plus ``mass_mask`` / ``mass_unmask`` (:41-82, host-side batch construction, kept on the
-host exactly as the reference) and ``backward`` (:85-90).
+host exactly as the reference), ``mask_text`` / ``unmask_text`` (:19-38, BERT masking for the masked LM; on the device
+``mask_text_device`` = ``imt_mlm_mask``) and ``backward`` (:85-90).
 
 The optimizer works on the model's FLAT buffers: global grad-norm = one reduction kernel, clip + Adam + bf16 shadow
 write + grad zeroing = one elementwise kernel (``imt_sumsq`` / ``imt_clip_adam``).
@@ -365,6 +366,34 @@ def mass_unmask(src_text, src_mask, masked_ids):
     src_text[src_mask] = masked_ids
 
 
+def mask_text(mask_prob, pads, texts, text_processor, mask_eos: bool = True):
+    """BERT masking on the host (semantics of src/utils.py:19-33): every real token is chosen with probability ``mask_prob``
+    (never a pad; never ``</s>`` with ``mask_eos=False``); a chosen token becomes <mask> (80%), a random non-special id (10%)
+    or stays (10%).  ``texts`` is modified in place.  Returns (mask, the original ids at the mask in row-major order, texts)."""
+    assert 0 < mask_prob < 1
+    mask = (torch.rand(texts.size()) < mask_prob) & pads.bool()
+    if not mask_eos:
+        mask &= texts != text_processor.sep_token_id()
+    masked_ids = texts[mask]
+    n_special, vocab, mask_id = len(text_processor.special_tokens), text_processor.vocab_size(), text_processor.mask_token_id()
+    replaced = []
+    for k in range(masked_ids.size(0)):
+        draw = random.random()
+        if draw < 0.8:
+            replaced.append(mask_id)
+        elif draw < 0.9:
+            replaced.append(random.randint(n_special, vocab - 1))
+        else:
+            replaced.append(int(masked_ids[k]))
+    texts[mask] = torch.tensor(replaced, dtype=torch.long)
+    return mask, masked_ids, texts
+
+
+def unmask_text(mask, masked_ids, texts):
+    """Undo mask_text in place (src/utils.py:36-38)."""
+    texts[mask] = masked_ids
+
+
 # ----------------------------------------------------------------------------------------- device batch construction
 _U32 = np.uint64(0xFFFFFFFF)
 
@@ -464,3 +493,75 @@ def mass_unmask_device(masked: Dict):
     L.check(L.load().imt_mass_unmask(ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(m.data_ptr()),
                                      ctypes.c_void_p(masked["mask_idx"].data_ptr()), ctypes.c_void_p(masked["_row_offsets"].data_ptr()),
                                      t.shape[0], t.shape[1], st), "imt_mass_unmask")
+
+
+def _mlm_selected(mask_prob, pads, texts, eos_id: int, seed: int, mask_eos: bool = True):
+    """selected(p) of imt_mlm_mask (include/imt_hip.h) for host arrays: bool [B, S].  The comparison is float32 on both sides."""
+    pads, texts = np.asarray(pads).astype(bool), np.asarray(texts)
+    u = _counter_uniform(int(seed), 4, np.arange(texts.size, dtype=np.uint64)).reshape(texts.shape)
+    sel = pads & (u < np.float32(mask_prob))
+    if not mask_eos:
+        sel &= texts != eos_id
+    return sel
+
+
+def mask_text_count(mask_prob, pads, texts, text_processor, seed: int, mask_eos: bool = True) -> int:
+    """How many positions imt_mlm_mask selects for this batch and seed, from the HOST copy of the batch: the kernel's draw
+    restated in numpy (stream 4 of ``_counter_uniform``, index = flat position), the way ``mass_span_starts`` restates the span
+    draws -- so a training step sizes ``idx`` / ``targets`` without reading the device count back."""
+    sel = _mlm_selected(mask_prob, pads.detach().cpu().numpy(), texts.detach().cpu().numpy(), text_processor.sep_token_id(), seed,
+                        mask_eos)
+    return int(sel.sum())
+
+
+def mask_text_device(mask_prob, pads, texts, text_processor, seed: int, mask_eos: bool = True, count=None) -> Dict:
+    """mask_text on the GPU (imt_mlm_mask): the draw, the 80/10/10 replacement in place and the ordered compaction of the masked
+    positions in one launch, on the kernel's counter-based generator keyed by ``seed`` (streams 4-6).  ``texts`` is modified in
+    place and must therefore be a contiguous int64 CUDA tensor.  Returns {"mask" bool [B, S], "targets" int64 [n] (the original
+    ids, == the reference's texts[mask]), "idx" int32 [n] (their flat positions), "texts", "count" (device int32 [1])}.
+    ``count``: the number of selected positions when the caller has it on the host (``mask_text_count``) -- nothing is read
+    back then; without it the count is read once, as ``hip_ops.select_plan`` does.  IMT_CHECK_COUNT=1 verifies a given count."""
+    import ctypes
+    import os
+    from . import _lib as L
+    if not (torch.is_tensor(texts) and texts.is_cuda and texts.dtype == torch.int64 and texts.dim() == 2 and texts.is_contiguous()):
+        raise L.ImtError("mask_text_device modifies texts in place: it needs a contiguous int64 [B, S] tensor on the GPU "
+                         "(use mask_text on the host)")
+    assert 0 < mask_prob < 1
+    n_rows, width = texts.shape
+    dev = texts.device
+    pads = pads.to(dev)
+    if pads.dtype == torch.bool:
+        pads = pads.view(torch.uint8)  # same element size: the strides stay, a column slice of a wider mask is read in place
+    if pads.dtype != torch.uint8 or tuple(pads.shape) != (n_rows, width):
+        raise L.ImtError("mask_text_device: pads must be a bool / uint8 tensor of the shape of texts")
+    if pads.stride(1) != 1:
+        pads = pads.contiguous()
+    n = n_rows * width
+    mask = torch.empty((n_rows, width), dtype=torch.uint8, device=dev)
+    idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    targets = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    count_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return {"mask": mask.bool(), "targets": targets[:0], "idx": idx[:0], "texts": texts, "count": count_dev}
+    a = L.MlmArgs()
+    a.n_rows, a.width = n_rows, width
+    a.n_special, a.vocab = len(text_processor.special_tokens), text_processor.vocab_size()
+    a.mask_eos, a.mask_prob, a.seed = int(bool(mask_eos)), float(mask_prob), int(seed)
+    a.mask_id, a.eos_id = text_processor.mask_token_id(), text_processor.sep_token_id()
+    a.texts, a.pads, a.ld_pads = texts.data_ptr(), pads.data_ptr(), pads.stride(0)
+    a.mask, a.idx, a.targets, a.count = mask.data_ptr(), idx.data_ptr(), targets.data_ptr(), count_dev.data_ptr()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    L.check(L.load().imt_mlm_mask(ctypes.byref(a), st), "imt_mlm_mask")
+    if count is None or os.environ.get("IMT_CHECK_COUNT"):
+        k = int(count_dev.item())
+        if count is not None and int(count) != k:
+            raise L.ImtError("mask_text_device: count hint %d but the kernel selected %d positions" % (int(count), k))
+    else:
+        k = int(count)
+    return {"mask": mask.bool(), "targets": targets[:k], "idx": idx[:k], "texts": texts, "count": count_dev}
+
+
+def unmask_text_device(masked: Dict):
+    """Restore the ids hidden by mask_text_device (in place): the originals scattered back at their flat positions."""
+    masked["texts"].view(-1)[masked["idx"].long()] = masked["targets"]

@@ -788,6 +788,39 @@ int imt_mass_mask(const imt_mass_args* a, void* stream);
 int imt_mass_unmask(int64_t* src_text, const uint8_t* src_mask, const int64_t* originals, const int64_t* row_offsets,
                     int n_rows, int width, void* stream);
 
+/* ------------------------------------------------------------------ masked-LM batch construction on device
+ * mask_text of src/utils.py:19-38 (BERT masking) in ONE launch: the Bernoulli draw per token, the 80/10/10 replacement in
+ * place and the compaction of the masked positions in row-major order (the order of the reference's texts[mask]).  Nothing
+ * is read back.  With p = b*width + t the flat position (uint32) and counter_uniform the generator of imt_mass_mask --
+ * streams 4, 5 and 6 here, so a seed shared with imt_mass_mask never reuses its streams 0-3:
+ *   selected(p) = pads[b, t] != 0 && (mask_eos || texts[p] != eos_id) && counter_uniform(seed, 4, p) < mask_prob  (float32)
+ *   mask[p]     = selected(p), written at EVERY position
+ *   the k-th selected position in row-major order: idx[k] = p, targets[k] = the ORIGINAL id; count[0] = how many
+ *   replacement at a selected position, u = counter_uniform(seed, 5, p):
+ *     u < 0.8f   <mask>
+ *     u < 0.9f   n_special + min((int)(counter_uniform(seed, 6, p) * (float)(vocab - n_special)), vocab - n_special - 1)
+ *     otherwise  the id stays
+ * idx / targets need room for n_rows*width entries; entries at and beyond count[0] are unspecified.  n_rows*width < 2^31.
+ * utils.mask_text_count restates selected(p) on the host, so a training step sizes its buffers without reading count.
+ * texts is modified in place (like the reference); a scatter of targets at idx restores it.
+ */
+typedef struct imt_mlm_args {
+  int32_t n_rows, width;
+  int32_t n_special, vocab;  /* replacement ids are drawn from [n_special, vocab) */
+  int32_t mask_eos;          /* 0: a token equal to eos_id is never selected */
+  float mask_prob;           /* 0 < p < 1 */
+  uint64_t seed;
+  int64_t mask_id, eos_id;
+  int64_t* texts;            /* [n_rows, width] contiguous, in/out */
+  const uint8_t* pads;       /* [n_rows, width], row stride ld_pads: 1 = a real token */
+  int64_t ld_pads;
+  uint8_t* mask;             /* [n_rows, width] out */
+  int32_t* idx;              /* [n_rows*width] out: flat positions of the selected tokens */
+  int64_t* targets;          /* [n_rows*width] out: their original ids */
+  int32_t* count;            /* [1] out */
+} imt_mlm_args;
+int imt_mlm_mask(const imt_mlm_args* a, void* stream);
+
 /* Non-pad target selection (src/seq2seq.py:175-177 `flat[tgt_mask[:, 1:]]`, train_image_mt.py:253-256 targets):
  * idx[k] = flat position b*T1 + t of the k-th set mask[b, col0 + t] (row-major order), targets[k] = ids[b, col0 + t],
  * count[0] = number selected.  idx / targets need room for B*T1 entries. */
