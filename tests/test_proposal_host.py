@@ -182,3 +182,102 @@ def test_proposal_attn_workspace_size(lib):
     floor = 4 * (2 * rows * P + G * P * d)
     assert floor <= n <= floor + 4 * (rows * d + (G + rows // 8 + G) * 3 * d + 2 * G * P) + 16 * 8
     assert n < rows * P * d * 4 // 8
+
+
+# ------------------------------------------------------------------------------------------- the edge cases have their edges
+# tests/test_gpu_proposal_edges.py runs these shapes on the GPU; here the inputs are shown to reach what the table claims.
+from tests import proposal_oracle as PO  # noqa: E402
+
+EDGE_IDS = lambda s: "G%d_r%d_P%d_d%d" % s
+
+
+@pytest.mark.parametrize("shape", list(PO.EDGE_CASES), ids=EDGE_IDS)
+def test_edge_cases_split_p_into_the_listed_tiles(shape):
+    _, _, P, d = shape
+    for name, nbytes in (("fp32", 4), ("bf16", 2)):
+        assert PO.tile_splits(nbytes, d, P) == PO.EDGE_CASES[shape][name], name
+        assert sum(PO.EDGE_CASES[shape][name]) == P
+    want = {(3, 17, 9, 1024): (8, 16), (3, 8, 64, 260): (31, 63), (4, 9, 33, 516): (15, 31)}  # PT before the clip to P
+    if shape in want:
+        assert (32768 // (d * 4), 32768 // (d * 2)) == want[shape]
+
+
+@pytest.mark.parametrize("dtype_name", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", list(PO.EDGE_CASES), ids=EDGE_IDS)
+def test_edge_case_references_are_not_near_zero(shape, dtype_name):
+    """A max-norm relative tolerance says something only about a tensor with a maximum: every reference tensor's is above 0.1."""
+    _, want = PO.edge_case(shape, dtype_name)
+    for k, v in want.items():
+        assert float(v.abs().max()) > 0.1, (k, float(v.abs().max()))
+
+
+def _positions_by_id(c):
+    flat = c["prop"].flatten()
+    pos = {}
+    for i in PO.live_entries(flat, c["table"].shape[0], c["pad_idx"]).nonzero().flatten().tolist():
+        pos.setdefault(int(flat[i]), []).append(i)
+    return pos
+
+
+@pytest.mark.parametrize("shape", PO.CHAIN_CASES, ids=EDGE_IDS)
+def test_chain_cases_cross_chunk_and_workgroup_boundaries(shape):
+    c, _ = PO.edge_case(shape, "fp32")
+    assert c["prop"].numel() > 2 * PO.CHAIN_CHUNK
+    pos = _positions_by_id(c)
+    assert any(len({i // PO.CHAIN_CHUNK for i in p}) >= 3 for p in pos.values()), "no id with entries in three chunks"
+    assert any(len(p) > 1 and p[0] // PO.CHAIN_THREADS != p[1] // PO.CHAIN_THREADS for p in pos.values()), \
+        "no id whose first and next entries are in different workgroups"
+    # an entry of the last workgroup whose chain began in chunk 0, and a link that leaves its chunk
+    last_wg = (c["prop"].numel() - 1) // PO.CHAIN_THREADS
+    assert any(p[0] < PO.CHAIN_CHUNK and p[-1] // PO.CHAIN_THREADS == last_wg for p in pos.values())
+    assert any(a // PO.CHAIN_CHUNK != b // PO.CHAIN_CHUNK for p in pos.values() for a, b in zip(p, p[1:]))
+
+
+def test_chain_emulation_matches_the_oracle_and_a_forgetful_one_does_not():
+    """The chain-and-scatter of the backward restated on the host, applied to the oracle's per-entry gradients: as the kernel
+    forms its links it gives the oracle's dtable; restarting the links with every chunk of 1024 ids misses it by far more than
+    the GPU test's tolerance.  So case (20, 3, 130, 64) tells the two apart, and no broken kernel has to run to show it."""
+    from tests.util import rel_err
+    shape = PO.CHAIN_CASES[0]
+    c, want = PO.edge_case(shape, "fp32")
+    V = c["table"].shape[0]
+    de = PO.proposal_reference(entry_grads=True, **c)["de"].reshape(-1, shape[3])
+    nxt, first = PO.chain_links(c["prop"], V, c["pad_idx"])
+    pos = _positions_by_id(c)
+    assert sorted(first.nonzero().flatten().tolist()) == sorted(p[0] for p in pos.values())
+    assert all(int(nxt[a]) == b for p in pos.values() for a, b in zip(p, p[1:])) and all(int(nxt[p[-1]]) == -1 for p in pos.values())
+    assert rel_err(PO.scatter_chains(c["prop"], de, nxt, first, V), want["dtable"]) < 1e-12
+    nxt, first = PO.chain_links(c["prop"], V, c["pad_idx"], forget_across_chunks=True)
+    assert rel_err(PO.scatter_chains(c["prop"], de, nxt, first, V), want["dtable"]) > 1e-4
+
+
+@pytest.mark.parametrize("shape", PO.CHAIN_CASES, ids=EDGE_IDS)
+def test_one_row_per_entry_problem_sums_to_the_original(shape):
+    """The exact entry-order check of the GPU test, in double: the per-entry problem has the same y and dx, its dtable rows
+    are the per-entry gradients, and their sum per id in entry order is the original dtable."""
+    from tests.util import rel_err
+    c, want = PO.edge_case(shape, "fp32")
+    c2 = PO.one_row_per_entry(c)
+    n = c["prop"].numel()
+    assert c2["table"].shape[0] == n + 1 and torch.equal(c2["table"][c2["prop"]], c["table"][c["prop"]])
+    assert torch.equal(c2["prop"] == 0, c["prop"] == 0)
+    want2 = PO.proposal_reference(entry_grads=True, **c2)
+    assert torch.equal(want2["y"], want["y"]) and torch.equal(want2["dx"], want["dx"])
+    live = (c["prop"].flatten() != 0)
+    assert torch.equal(want2["dtable"][1:][live], want2["de"].reshape(n, -1)[live])
+    assert rel_err(PO.sum_in_entry_order(c["prop"], want2["dtable"], c["table"].shape[0]), want["dtable"]) < 1e-12
+
+
+def test_out_of_range_reference_is_the_plain_one_without_such_ids():
+    c, want = PO.edge_case((3, 5, 7, 128), "fp32")
+    got = PO.out_of_range_reference(c)
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+    # with them: four ids outside [0, V), both groups keep live ids, the table gradient keeps its shape
+    c = PO.with_out_of_range_ids(c)
+    V = c["table"].shape[0]
+    bad = (c["prop"] < 0) | (c["prop"] >= V)
+    assert int(bad.sum()) == 4 and sorted(c["prop"][bad].tolist()) == [-1, V, V + 7, 2 ** 40]
+    assert bool(PO.live_entries(c["prop"], V, 0)[:2].any(-1).all())
+    got = PO.out_of_range_reference(c)
+    assert got["dtable"].shape == c["table"].shape and not torch.equal(got["y"], want["y"])
