@@ -199,6 +199,17 @@ class KnnArgs(Structure):
     ]
 
 
+class AlignArgs(Structure):
+    _fields_ = [
+        ("dtype", c_int32), ("B", c_int32), ("S", c_int32), ("T", c_int32), ("d", c_int32),
+        ("x", c_void_p), ("ldx", c_int64), ("bsx", c_int64),
+        ("y", c_void_p), ("ldy", c_int64), ("bsy", c_int64),
+        ("xr", c_void_p), ("yr", c_void_p),
+        ("min_sim", c_float), ("reserved", c_int32),
+        ("link", c_void_p), ("fwd_idx", c_void_p), ("fwd_val", c_void_p), ("bwd_idx", c_void_p), ("bwd_val", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/imt_hip.h declares (tests/test_cabi.py checks)
 _P = c_void_p
 SIGNATURES = {
@@ -236,6 +247,8 @@ SIGNATURES = {
     "imt_knn_ws_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "imt_knn_supported": (c_int, [c_int, c_int]),
     "imt_knn_rows": (c_int, [POINTER(KnnArgs), _P]),
+    "imt_align_supported": (c_int, [c_int, c_int]),
+    "imt_align_pairs": (c_int, [POINTER(AlignArgs), _P]),
     "imt_scaled_sum": (c_int, [_P, c_int, c_float, _P, _P]),
     "imt_sumsq": (c_int, [_P, c_int64, _P, _P, _P]),
     "imt_ln_partial_reduce": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
@@ -305,7 +318,7 @@ ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_r
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
                "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs,
-               "imt_knn_args": KnnArgs, "imt_mlm_args": MlmArgs}
+               "imt_knn_args": KnnArgs, "imt_mlm_args": MlmArgs, "imt_align_args": AlignArgs}
 
 
 def load():

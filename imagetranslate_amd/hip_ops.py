@@ -504,6 +504,70 @@ def knn_rows(x, y, k, *, splits=0, _key_chunk=None, _query_chunk=None):
     return val, idx
 
 
+ALIGN_MAX_LEN = 512  # IMT_ALIGN_MAX_LEN
+
+
+def _align_operand(t):
+    """[B, rows, d] for imt_align_pairs: d zero-padded up to a whole 128-byte step (a zero column changes neither a product
+    nor a norm); a view is passed as it is where its strides allow (unit inner stride, rows and pairs on 16-byte boundaries,
+    pairs that do not overlap), and copied otherwise."""
+    step = 128 // t.element_size()
+    epv = 16 // t.element_size()
+    B, rows, d = t.shape
+    if d % step:
+        out = torch.zeros((B, rows, (d + step - 1) // step * step), device=t.device, dtype=t.dtype)
+        out[:, :, :d] = t
+        return out
+    ok = t.stride(2) == 1 and t.data_ptr() % 16 == 0
+    ok = ok and (rows == 1 or (t.stride(1) >= d and t.stride(1) % epv == 0))
+    ok = ok and (B == 1 or (t.stride(0) % epv == 0 and t.stride(0) >= (rows - 1) * (t.stride(1) if rows > 1 else 0) + d))
+    return t if ok else t.contiguous()
+
+
+def align_pairs(x, y, x_range, y_range, min_sim=float("-inf")):
+    """Mutual arg-max word alignment of B sentence pairs without the [B, S, T] similarities (include/imt_hip.h:
+    imt_align_pairs).  x [B, S, d], y [B, T, d] in one dtype (fp32 / bf16); x_range / y_range [B, 2] integer (begin, end) of
+    the tokens to align.  Returns (link [B, S], fwd_idx [B, S], fwd_val [B, S], bwd_idx [B, T], bwd_val [B, T]): indices
+    int64 (-1: none), values fp32 cosines (-inf: none)."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2] or x.dtype != y.dtype:
+        raise ValueError("align_pairs: x %s %s against y %s %s" % (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype))
+    B, S, d = x.shape
+    T = y.shape[1]
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("align_pairs: float32 or bfloat16 states, got %s" % x.dtype)
+    for name, rng in (("x_range", x_range), ("y_range", y_range)):
+        if tuple(rng.shape) != (B, 2) or rng.dtype.is_floating_point or rng.dtype == torch.bool:
+            raise ValueError("align_pairs: %s must be integer [%d, 2], got %s %s" % (name, B, tuple(rng.shape), rng.dtype))
+    _req_cuda(x, y, x_range, y_range)
+    dev = x.device
+    link = torch.full((B, S), -1, device=dev, dtype=torch.int32)
+    fwd_idx = torch.full((B, S), -1, device=dev, dtype=torch.int32)
+    fwd_val = torch.full((B, S), float("-inf"), device=dev, dtype=torch.float32)
+    bwd_idx = torch.full((B, T), -1, device=dev, dtype=torch.int32)
+    bwd_val = torch.full((B, T), float("-inf"), device=dev, dtype=torch.float32)
+    if B > 0:
+        x, y = _align_operand(x), _align_operand(y)
+        dp = x.shape[2]
+        lib = L.load()
+        if not lib.imt_align_supported(dt(x), dp):
+            raise L.ImtError("align_pairs: (dtype %s, d %d) is not taken by imt_align_pairs" % (x.dtype, dp))
+        lim = torch.iinfo(torch.int32)
+        xr = x_range.clamp(lim.min, lim.max).to(torch.int32).contiguous()
+        yr = y_range.clamp(lim.min, lim.max).to(torch.int32).contiguous()
+        a = L.AlignArgs()
+        a.dtype, a.B, a.S, a.T, a.d = dt(x), B, S, T, dp
+        a.x, a.ldx = x.data_ptr(), x.stride(1) if S > 1 else dp
+        a.bsx = x.stride(0) if B > 1 else (S - 1) * a.ldx + dp
+        a.y, a.ldy = y.data_ptr(), y.stride(1) if T > 1 else dp
+        a.bsy = y.stride(0) if B > 1 else (T - 1) * a.ldy + dp
+        a.xr, a.yr = xr.data_ptr(), yr.data_ptr()
+        a.min_sim = float(min_sim)
+        a.link, a.fwd_idx, a.fwd_val = link.data_ptr(), fwd_idx.data_ptr(), fwd_val.data_ptr()
+        a.bwd_idx, a.bwd_val = bwd_idx.data_ptr(), bwd_val.data_ptr()
+        L.check(lib.imt_align_pairs(ctypes.byref(a), _stream()), "imt_align_pairs")
+    return link.long(), fwd_idx.long(), fwd_val, bwd_idx.long(), bwd_val
+
+
 def log_softmax_bwd(dlp, lp, out_dtype):
     _req_cuda(dlp, lp)
     N, V = lp.shape

@@ -348,6 +348,37 @@ typedef struct imt_knn_args {
 int64_t imt_knn_ws_bytes(int N, int M, int k, int splits);
 int imt_knn_supported(int dtype, int K);
 int imt_knn_rows(const imt_knn_args* a, void* stream);
+/* ------------------------------------------------------------------ word alignment of sentence pairs (argmax / intersection)
+ * B independent problems: x [B, S, d] and y [B, T, d] of one dtype, token ranges xr [B, 2] / yr [B, 2] (begin, end) int32 on the
+ * device.  For i in xr[b], j in yr[b]:
+ *   sim[b, i, j] = (x[b, i] . y[b, j]) / (max(|x[b, i]|, 1e-12) max(|y[b, j]|, 1e-12))     products and norms in fp32
+ *   fwd_idx[b, i] = the LOWEST j in range of maximal sim, fwd_val[b, i] that value; bwd_idx[b, j] / bwd_val[b, j] likewise over i
+ *   link[b, i]    = fwd_idx[b, i] if bwd_idx[b, fwd_idx[b, i]] == i and fwd_val[b, i] >= min_sim, else -1
+ * Positions outside their range, and all positions of a pair whose other range is empty, hold -1 / -inf.  The kernel clamps
+ * the ranges to [0, S] / [0, T] (end below begin: empty); rows outside them never reach a result, whatever they hold.
+ * One launch (profiling kind align_bf16 / align_f32), one workgroup per pair: it walks 64 x 64 tiles of the pair's ranges
+ * (MFMA, 128 bytes of d per step), takes the norms from the staged operands, keeps the running maxima of both directions in
+ * LDS and finishes with the mutual test.  Neither the similarities nor normalised rows are stored; no workspace; no atomics:
+ * two calls give the same bits, and a pair's outputs do not depend on B or on the other pairs.
+ * imt_align_supported: 1 where d is a whole number of 128-byte steps (64 bf16 / 32 fp32 elements).
+ * Refused before any launch with IMT_ERR_BAD_ARG: null args or tensors, a bad dtype, B <= 0, S or T outside
+ * 1..IMT_ALIGN_MAX_LEN, an unsupported d, row strides (elements) below d, batch strides below (rows - 1) * ld + d, bases or
+ * strides that leave rows off 16-byte boundaries, an operand whose last byte offset does not fit in 63 bits. */
+#define IMT_ALIGN_MAX_LEN 512
+typedef struct imt_align_args {
+  int32_t dtype;                          /* IMT_F32 / IMT_BF16: type of x and y */
+  int32_t B, S, T, d;                     /* pairs, source / target positions, vector length */
+  const void* x; int64_t ldx, bsx;        /* [B, S, d]: row and batch stride in elements */
+  const void* y; int64_t ldy, bsy;        /* [B, T, d] */
+  const int32_t* xr;                      /* [B, 2] (begin, end) of the source tokens to align */
+  const int32_t* yr;                      /* [B, 2] of the target tokens */
+  float min_sim; int32_t reserved;        /* links below min_sim are dropped (-inf: keep all) */
+  int32_t* link;                          /* [B, S] out */
+  int32_t* fwd_idx; float* fwd_val;       /* [B, S] out */
+  int32_t* bwd_idx; float* bwd_val;       /* [B, T] out */
+} imt_align_args;
+int imt_align_supported(int dtype, int d);
+int imt_align_pairs(const imt_align_args* a, void* stream);
 /* out[0] = scale * sum(x[0..n)), fixed summation order: the `.mean()` of the per-row losses (train_image_mt.py:282). */
 int imt_scaled_sum(const float* x, int n, float scale, float* out, void* stream);
 
