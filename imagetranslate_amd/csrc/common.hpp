@@ -42,6 +42,7 @@ void imt_set_error(const char* fmt, ...);
 static inline int imt_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool imt_ok_dtype(int t) { return t == IMT_F32 || t == IMT_BF16; }
 static inline int imt_dtype_bytes(int t) { return t == IMT_BF16 ? 2 : 4; }
+static inline int64_t imt_align256(int64_t bytes) { return (bytes + 255) / 256 * 256; }  // workspace sections start on 256 bytes
 // Host dispatch on a dtype already checked with imt_ok_dtype: returns f(tag), where `typename decltype(tag)::type` is float or
 // bf16_t -- the launch of a dtype-templated kernel is written once, in a generic lambda (two nested calls for two dtypes).
 template <typename T> struct ImtType { typedef T type; };

@@ -8,7 +8,7 @@
 // (mfma(Bfrag, Afrag)) so each lane owns 4 consecutive n of one m: bias / residual / aux accesses and the C
 // store are 8- or 16-byte vectors.
 //
-// Six main loops share the tile product (compute_tile) and the LDS-restaged epilogue.  imt_gemm (host side, at the end of the
+// Five main loops share the tile product (compute_tile) and the LDS-restaged epilogue.  imt_gemm (host side, at the end of the
 // file) validates, then picks a strategy -- ragged-K tail + whole-tile body, split-K slabs on the persistent kernel (splitk_ws) or
 // on the 256-tile kernel (IMT_AUX_SPLITK_WS), else one launch whose loop choose_variant picks from measurements
 // (profiles/r01_v5_gemm_shapes.txt, profiles/r01_gemm_epilogue_study.txt, profiles/r01_gemm_xl_study.txt):
@@ -24,8 +24,6 @@
 //   gemm_sb_kernel         : one 32-KiB LDS buffer + register prefetch, three workgroups per CU overlap each other's
 //                            barriers and epilogues: many short-K tiles, and whatever the LDS-DMA loops cannot run (NT / NN).
 //   gemm_kernel            : register-staged double buffer with predicated (zero-filling) loads: what gemm_sb_kernel takes, for TN.
-//   gemm_pipe_kernel       : LDS-DMA ring (3 or 4 stages) issued by the MFMA waves themselves (superseded by gemm_ws_kernel;
-//                            only by force_general, as a cross-check variant for the tests).
 #include <stdlib.h>
 #include "mma.hpp"
 #include "gemm_xl.hpp"
@@ -78,10 +76,9 @@ template <typename T, bool KCONTIG> struct Dma : TileGeom<T, KCONTIG> {
   int voff[4];    // byte offset of this lane's chunk for k0 = 0
   int kadv;       // byte advance per K tile
   int wv;         // which quarter of the tile's 16 pieces this wave issues
-  IMT_DEVICE void init(const T* base, int64_t ld, int64_t valid_bytes, int row0, int kbeg, int wave = -1) {
+  IMT_DEVICE void init(const T* base, int64_t ld, int64_t valid_bytes, int row0, int kbeg, int wave) {
     rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)valid_bytes, 0x00020000);
     const int lane = threadIdx.x & 63;
-    if (wave < 0) wave = threadIdx.x >> 6;
     wv = wave;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -102,6 +99,14 @@ template <typename T, bool KCONTIG> struct Dma : TileGeom<T, KCONTIG> {
     }
   }
 };
+// A producer wave's counted wait: all of its DMA pieces have landed but those of its `newer` youngest K steps (a step is 8
+// pieces: 4 of the A tile, 4 of the B tile; the rings keep at most 3 steps in flight)
+IMT_DEVICE void dma_wait_newer(int newer) {
+  if (newer >= 3)      asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+  else if (newer == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+  else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 
 struct EpiParams {
   void* C; int64_t ldc; int c_f32; int accumulate;
@@ -577,71 +582,6 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_sb_kernel(const T* __restric
   if (LAYOUT == IMT_TN && do_colsum) cs.flush(smem, ep.a_colsum, m0, M, alpha);
 }
 
-// ------------------------------------------------------------------------------------------------ pipelined kernel
-constexpr int NST = 3;  // LDS ring depth (96 KiB): tile t+2 in flight while tile t is multiplied
-
-template <typename T, int LAYOUT, int NSTG>
-__global__ __launch_bounds__(NTHREADS) void gemm_pipe_kernel(const T* __restrict__ A, int64_t lda, int64_t a_bytes,
-                                                             const T* __restrict__ B, int64_t ldb, int64_t b_bytes, int M, int N,
-                                                             int K, int k_per_split, EpiParams ep) {
-  constexpr bool A_KC = (LAYOUT != IMT_TN), B_KC = (LAYOUT == IMT_NT);
-  constexpr int BK = TileGeom<T, A_KC>::BK;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // ALL LDS in this one array (second-object trap)
-
-  int m0, n0;
-  tile_origin(M, N, m0, n0);
-  const int kbeg = blockIdx.y * k_per_split;
-  const int kend = min(K, kbeg + k_per_split);
-  const int nt = (kend - kbeg) / BK;  // host guarantees (kend - kbeg) % BK == 0
-  const int wave = threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-
-  Dma<T, A_KC> da; Dma<T, B_KC> db;
-  da.init(A, lda, a_bytes, m0, kbeg);
-  db.init(B, ldb, b_bytes, n0, kbeg);
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  ColSum<T> cs;
-  cs.clear();
-  const bool do_colsum = (LAYOUT == IMT_TN) && ep.a_colsum && n0 == 0;
-
-  // K-order rotation: workgroups that run at the same time start at different K offsets, so they do not all hit the
-  // same L2 / memory channels in lock-step (row strides are powers of two).  Summation order differs per block only.
-  const int phase = nt > 0 ? (int)((blockIdx.x * 7u + blockIdx.y * 3u) % (unsigned)nt) : 0;
-  auto ktile = [&](int t) { const int k = t + phase; return k >= nt ? k - nt : k; };
-  // prologue: tiles 0 .. NSTG-2 in flight (8 DMA instructions per wave per tile: 4 for A, 4 for B)
-#pragma unroll
-  for (int s0 = 0; s0 < NSTG - 1; ++s0)
-    if (s0 < nt) { da.issue(smem + s0 * STAGE_BYTES, ktile(s0)); db.issue(smem + s0 * STAGE_BYTES + TILE_BYTES, ktile(s0)); }
-  int cur = 0;
-  for (int t = 0; t < nt; ++t) {
-    // tile t has landed once all but the (NSTG-2) newest tiles' DMAs are done; the barrier then (a) publishes every
-    // wave's pieces of tile t and (b) proves every wave finished reading the buffer the next DMA overwrites.
-    const int newer = min(NSTG - 2, nt - 1 - t);
-    if (newer >= 2)      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    if (t + NSTG - 1 < nt && !(ep.dbg & 2)) {
-      const int nxt = (cur == 0) ? NSTG - 1 : cur - 1;  // (cur + NSTG - 1) % NSTG
-      da.issue(smem + nxt * STAGE_BYTES, ktile(t + NSTG - 1));
-      db.issue(smem + nxt * STAGE_BYTES + TILE_BYTES, ktile(t + NSTG - 1));
-    }
-    const char* ta = smem + cur * STAGE_BYTES;
-    if (!(ep.dbg & 1)) compute_tile<T, LAYOUT>(acc, ta, ta + TILE_BYTES, wm, wn);
-    if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(ta);
-    cur = (cur + 1 == NSTG) ? 0 : cur + 1;
-  }
-  const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
-  epilogue<T>(acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
-  if (LAYOUT == IMT_TN && do_colsum) cs.flush(smem, ep.a_colsum, m0, M, alpha);
-}
-
-
 // ------------------------------------------------------------------------------------------------ persistent wave-specialised kernel
 // The main GEMM loop of the path when K is a whole number of tiles: 512 threads, waves 0-3 multiply (64x64 each),
 // waves 4-7 stream the operand tiles by LDS-DMA into a 3-stage ring and run AHEAD ACROSS OUTPUT TILES (one workgroup
@@ -707,16 +647,10 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
     for (int s0 = 0; s0 < WS_NST - 1; ++s0)
       if (issued < total) { issue_next(s0); ++issued; }
     int cur = 0, t = 0;
-    const auto wait_newer = [](int newer) {  // all of this wave's DMA pieces done but those of the `newer` youngest steps
-      if (newer >= 3)      asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-      else if (newer == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
     int ci = 0, nt_c = 0;  // item being consumed and its K tiles
     if (my_tiles > 0) { int lt, kt0; item(0, lt, kt0, nt_c); }
     for (int q = 0; q < total; ++q) {
-      wait_newer(issued - 1 - q);  // steps issued after step q, which this barrier publishes
+      dma_wait_newer(issued - 1 - q);  // steps issued after step q, which this barrier publishes
       asm volatile("s_barrier" ::: "memory");
       if (issued < total) { issue_next(cur == 0 ? WS_NST - 1 : cur - 1); ++issued; }
       cur = (cur + 1 == WS_NST) ? 0 : cur + 1;
@@ -787,20 +721,20 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
 // DMA the A sub-tiles, waves 4-7 the B sub-tiles of K tile t+1 while everyone multiplies tile t; one barrier per K tile.
 // The epilogue walks the four 128 x 128 quadrants with all 512 threads (the two owning waves restage, everyone stores).
 
-// Epilogue of a FULL 256 x 256 tile straight from the accumulators: lane (lr, lg) owns 4 consecutive n of row 16i + lr in
-// each of its wave's 8 x 4 MFMA tiles, so bias / aux / C accesses are 8-byte (bf16) vectors, 32 B contiguous per row and
+// Epilogue of a FULL 256 x 256 tile straight from the accumulators: a lane owns 4 consecutive n of one row in each of its
+// wave's 8 x 4 MFMA tiles (XlOwn), so bias / aux / C accesses are 8-byte (bf16) vectors, 32 B contiguous per row and
 // instruction, a full 128-B line per row over j = 0..3.  No LDS pass, no barrier, and NO run-time branch: the epilogue
 // kind is a template parameter, because 32 unrolled copies of a body that branches over every option (GELU, GELU',
 // dropout, residual, ...) are ~250 KB of code that a wave walks once, taking an instruction-cache miss at every skipped
 // block -- measured 12-18 us per tile (IMT_GEMM_TRACE), more than the whole K loop.  Kinds outside the table below and
 // ragged edge tiles take the restaged path.
 template <typename T, int AUX, bool C_F32, bool RAGGED_M>
-IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], int mw, int nw, int M, const EpiParams& ep, float alpha) {
+IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], const XlWave w, int m0, int n0, int M, const EpiParams& ep, float alpha) {
   typedef typename Vec4<T>::type raw_t;
-  const int lane = threadIdx.x & 63, lr = lane & 15, lg = lane >> 4;
+  const XlOwn own(w);
   const T* bias = reinterpret_cast<const T*>(ep.bias);
   T* aux = reinterpret_cast<T*>(ep.aux);
-  const int nl = nw + 4 * lg;
+  const int nl = n0 + own.col(0);
   f32x4 bv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) bv[j] = bias ? Vec4<T>::load(bias + nl + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -808,7 +742,7 @@ IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], int mw, int nw, int
   auto fetch = [&](int i, int b) {
     if (AUX == IMT_AUX_DGELU) {
       // ragged M: clamped loads, predicated stores
-      const int64_t m = RAGGED_M ? min((int64_t)(mw + 16 * i + lr), (int64_t)M - 1) : (int64_t)(mw + 16 * i + lr);
+      const int64_t m = RAGGED_M ? min((int64_t)(m0 + own.row(i)), (int64_t)M - 1) : (int64_t)(m0 + own.row(i));
 #pragma unroll
       for (int j = 0; j < 4; ++j) zr[b][j] = Vec4<T>::load_raw(aux + m * ep.ldaux + nl + 16 * j);
     }
@@ -817,7 +751,7 @@ IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], int mw, int nw, int
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (i + 1 < 8) fetch(i + 1, (i + 1) & 1);  // requested before this group's stores: the wait below never covers a store
-    const int64_t m = mw + 16 * i + lr;
+    const int64_t m = m0 + own.row(i);
     const bool live = !RAGGED_M || m < M;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -856,22 +790,16 @@ __global__ __launch_bounds__(XL_THREADS) void gemm_xl_kernel(const T* __restrict
   const int kt0 = (int)blockIdx.y * per;
   const int nt = max(0, min(per, nt_all - kt0));
   if (gridDim.y > 1) ep.C = reinterpret_cast<float*>(ep.C) + (int64_t)blockIdx.y * ep.slab_elems;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wmi = wave >> 2, wni = wave & 3, wn = (wni & 1) * 64;
-  const bool loads_a = wave < 4;
+  const XlWave w;
+  const int wmi = w.wmi, wni = w.wni, wn = w.wn;
 
   IMT_STAMP(ep.trace, 0);
   DmaPair<T> dma;
-  if (loads_a) dma.template init<A_KC>(A, lda, a_bytes, m0, wave);
-  else         dma.template init<B_KC>(B, ldb, b_bytes, n0, wave - 4);
-  auto issue = [&](int slot, int t) { dma.issue(smem + slot * XL_STAGE + (loads_a ? 0 : 2 * TILE_BYTES), kt0 + t); };
+  if (w.loads_a) dma.template init<A_KC>(A, lda, a_bytes, m0, w.wave);
+  else           dma.template init<B_KC>(B, ldb, b_bytes, n0, w.wave - 4);
 
   f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+  xl_zero(acc);
   // (no K-order rotation: measured no gain here, and the same K order keeps results bit-identical to the other kernels)
   // TN weight gradients: the fused bias gradient (column sums of the K-strided A tiles) -- threads 0-255 own the first
   // 128-column sub-tile, 256-511 the second; only the workgroups of the first tile column take part
@@ -879,42 +807,26 @@ __global__ __launch_bounds__(XL_THREADS) void gemm_xl_kernel(const T* __restrict
   cs.clear();
   const bool do_colsum = (LAYOUT == IMT_TN) && ep.a_colsum && n0 == 0;
   const int half = threadIdx.x >> 8, ht = threadIdx.x & 255;
-  if (nt > 0) issue(0, 0);
-  for (int t = 0; t < nt; ++t) {
-    // my eight pieces of tile t have landed; the barrier publishes everyone's and proves that the other stage (read
-    // while multiplying tile t-1) is free for the DMA of tile t+1
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    // Issuing a wave's eight 1-KiB DMA pieces takes it ~0.4 us during which it multiplies nothing (one wave sustains
-    // ~20 GB/s of LDS-DMA, profiles/r01_lds_fill_probe.txt).  Waves w and w+4 share a SIMD: the first issues before its
-    // MFMAs, the second between its two K steps, so each SIMD always has one wave multiplying.
-    const bool issue_now = (t + 1 < nt) && !(ep.dbg & 2);
-    if (issue_now && (wave < 4 || (ep.dbg & 64))) issue((t + 1) & 1, t + 1);
-    if (t == 0) IMT_STAMP(ep.trace, 1);
-    const char* st = smem + (t & 1) * XL_STAGE;
-    if (!(ep.dbg & 1)) compute_tile_xl<T, LAYOUT, 0>(acc, st + wmi * TILE_BYTES, st + (2 + (wni >> 1)) * TILE_BYTES, wn);
-    if (issue_now && wave >= 4 && !(ep.dbg & 64)) issue((t + 1) & 1, t + 1);
-    if (!(ep.dbg & 1)) compute_tile_xl<T, LAYOUT, 1>(acc, st + wmi * TILE_BYTES, st + (2 + (wni >> 1)) * TILE_BYTES, wn);
+  xl_k_loop<T, LAYOUT>(acc, smem, dma, w, kt0, nt, ep.dbg, ep.trace, [&](const char* st) {
     if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(st + half * TILE_BYTES, ht);
-  }
+  });
   const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
   IMT_STAMP(ep.trace, 2);
   if (n0 + 256 <= N && !ep.atomic && !ep.accumulate && !ep.resid && !ep.drop_thresh && !(ep.dbg & 8)) {
-    const int mw = m0 + 128 * wmi, nw = n0 + 64 * wni;
     bool done = true;
     const bool rag = m0 + 256 > M;
     if (ep.aux_mode == IMT_AUX_NONE && !ep.c_f32) {
-      if (rag) epilogue_xl_direct<T, IMT_AUX_NONE, false, true>(acc, mw, nw, M, ep, alpha);
-      else     epilogue_xl_direct<T, IMT_AUX_NONE, false, false>(acc, mw, nw, M, ep, alpha);
+      if (rag) epilogue_xl_direct<T, IMT_AUX_NONE, false, true>(acc, w, m0, n0, M, ep, alpha);
+      else     epilogue_xl_direct<T, IMT_AUX_NONE, false, false>(acc, w, m0, n0, M, ep, alpha);
     } else if (ep.aux_mode == IMT_AUX_NONE) {
-      if (rag) epilogue_xl_direct<T, IMT_AUX_NONE, true, true>(acc, mw, nw, M, ep, alpha);
-      else     epilogue_xl_direct<T, IMT_AUX_NONE, true, false>(acc, mw, nw, M, ep, alpha);
+      if (rag) epilogue_xl_direct<T, IMT_AUX_NONE, true, true>(acc, w, m0, n0, M, ep, alpha);
+      else     epilogue_xl_direct<T, IMT_AUX_NONE, true, false>(acc, w, m0, n0, M, ep, alpha);
     } else if (ep.aux_mode == IMT_AUX_GELU_FWD && !ep.c_f32) {
-      if (rag) epilogue_xl_direct<T, IMT_AUX_GELU_FWD, false, true>(acc, mw, nw, M, ep, alpha);
-      else     epilogue_xl_direct<T, IMT_AUX_GELU_FWD, false, false>(acc, mw, nw, M, ep, alpha);
+      if (rag) epilogue_xl_direct<T, IMT_AUX_GELU_FWD, false, true>(acc, w, m0, n0, M, ep, alpha);
+      else     epilogue_xl_direct<T, IMT_AUX_GELU_FWD, false, false>(acc, w, m0, n0, M, ep, alpha);
     } else if (ep.aux_mode == IMT_AUX_DGELU && !ep.c_f32) {
-      if (rag) epilogue_xl_direct<T, IMT_AUX_DGELU, false, true>(acc, mw, nw, M, ep, alpha);
-      else     epilogue_xl_direct<T, IMT_AUX_DGELU, false, false>(acc, mw, nw, M, ep, alpha);
+      if (rag) epilogue_xl_direct<T, IMT_AUX_DGELU, false, true>(acc, w, m0, n0, M, ep, alpha);
+      else     epilogue_xl_direct<T, IMT_AUX_DGELU, false, false>(acc, w, m0, n0, M, ep, alpha);
     }
     else done = false;
     if (done) {
@@ -1059,19 +971,10 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
     int cur = 0;
     // barrier t tells the consumers that tile t + 1 has landed (they read its first fragments while still multiplying
     // tile t), and the producers that the consumers are done with tile t - 1, whose slot takes tile t + 3
-    {
-      const int newer0 = min(GROUP_NST - 2, nt - 1);
-      if (newer0 >= 3)      asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-      else if (newer0 == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (newer0 == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else                  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_barrier" ::: "memory");  // tile 0 landed
-    }
+    dma_wait_newer(min(GROUP_NST - 2, nt - 1));
+    asm volatile("s_barrier" ::: "memory");  // tile 0 landed
     for (int t = 0; t < nt; ++t) {
-      const int newer = max(0, min(nt - 1, t + GROUP_NST - 2) - (t + 1));  // tiles issued after tile t + 1
-      if (newer >= 2)      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (newer == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      dma_wait_newer(t + 2 < nt ? 1 : 0);  // tiles issued after tile t + 1: tile t + 2 (t + 3 goes out behind this barrier)
       asm volatile("s_barrier" ::: "memory");
       if (t + GROUP_NST - 1 < nt) {
         const int nxt = (cur == 0) ? GROUP_NST - 1 : cur - 1;
@@ -1103,29 +1006,32 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int64_t view_bytes(int rows, int64_t ld, int inner, int es) { return rows > 0 ? ((int64_t)(rows - 1) * ld + inner) * es : 0; }
-template <typename K> bool allow_lds(K kernel, int bytes) {  // opt in to that much dynamic LDS; `static const bool once = allow_lds(...)`
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return true;
-}
+// (view_bytes and allow_lds: gemm_xl.hpp.  A refused LDS opt-in is left to the launch that follows to report.)
 
-// The six main loops, numbered as in imt_gemm_args.force_general (include/imt_hip.h): V_DBUF gemm_kernel, V_DMA3 / V_DMA4 gemm_pipe_kernel
-// with a 3- / 4-stage ring, V_SBUF gemm_sb_kernel, V_WS gemm_ws_kernel, V_XL gemm_xl_kernel
-enum Variant { V_DBUF = 1, V_DMA3 = 2, V_SBUF = 3, V_DMA4 = 4, V_WS = 5, V_XL = 6 };
+// The main loops of imt_gemm, numbered as in imt_gemm_args.force_general (include/imt_hip.h): V_DBUF gemm_kernel, V_SBUF gemm_sb_kernel,
+// V_WS gemm_ws_kernel, V_XL gemm_xl_kernel (2 and 4 were the rings of the retired gemm_pipe_kernel; as codes they run V_DBUF)
+enum Variant { V_DBUF = 1, V_SBUF = 3, V_WS = 5, V_XL = 6 };
 // profiler kind == one kernel symbol: gemm_<variant>_<dtype>_<layout>, so that rocprofv3's per-symbol averages can be compared
-// one to one (both rings of gemm_pipe_kernel report as "dma").  Indexed [variant - 1][bf16][layout].
-const char* const VARIANT_KINDS[6][2][3] = {
+// one to one.  Indexed [variant_row][bf16][layout].
+int variant_row(Variant v) {
+  switch (v) {
+    case V_DBUF: return 0;
+    case V_SBUF: return 1;
+    case V_WS: return 2;
+    case V_XL: return 3;
+  }
+  return 0;
+}
+const char* const VARIANT_KINDS[4][2][3] = {
     {{"gemm_dbuf_f32_nt", "gemm_dbuf_f32_nn", "gemm_dbuf_f32_tn"}, {"gemm_dbuf_bf16_nt", "gemm_dbuf_bf16_nn", "gemm_dbuf_bf16_tn"}},
-    {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
     {{"gemm_sbuf_f32_nt", "gemm_sbuf_f32_nn", "gemm_sbuf_f32_tn"}, {"gemm_sbuf_bf16_nt", "gemm_sbuf_bf16_nn", "gemm_sbuf_bf16_tn"}},
-    {{"gemm_dma_f32_nt", "gemm_dma_f32_nn", "gemm_dma_f32_tn"}, {"gemm_dma_bf16_nt", "gemm_dma_bf16_nn", "gemm_dma_bf16_tn"}},
     {{"gemm_ws_f32_nt", "gemm_ws_f32_nn", "gemm_ws_f32_tn"}, {"gemm_ws_bf16_nt", "gemm_ws_bf16_nn", "gemm_ws_bf16_tn"}},
     {{"gemm_xl_f32_nt", "gemm_xl_f32_nn", "gemm_xl_f32_tn"}, {"gemm_xl_bf16_nt", "gemm_xl_bf16_nn", "gemm_xl_bf16_tn"}}};
 
 // What the policy and launch<> need to know about one product, computed once per imt_gemm_args.
 struct GemmFacts {
   int es, bk, al;            // bytes per element; K elements per tile (128 bytes); elements per 16-byte chunk
-  bool pipe_ok;              // the LDS-DMA kernels (V_DMA3 / V_DMA4 / V_WS / V_XL) can run it
+  bool pipe_ok;              // the LDS-DMA kernels (V_WS / V_XL) can run it
   int64_t tiles, tiles256;   // output tiles of 128 x 128 and of 256 x 256
   int64_t a_bytes, b_bytes;  // extent of the A and B views (the range of their buffer descriptors)
 };
@@ -1147,10 +1053,9 @@ template <typename T, int LAYOUT>
 int launch(const imt_gemm_args* a, const GemmFacts& f, EpiParams ep, int splits, int kps, Variant variant, hipStream_t st) {
   dim3 grid((unsigned)f.tiles, splits);
   auto kern = gemm_kernel<T, LAYOUT>;
-  auto kpipe = gemm_pipe_kernel<T, LAYOUT, 3>, kpipe4 = gemm_pipe_kernel<T, LAYOUT, 4>;
-  static const bool once = allow_lds(kern, 2 * STAGE_BYTES) && allow_lds(kpipe, 3 * STAGE_BYTES) && allow_lds(kpipe4, 4 * STAGE_BYTES);
+  static const bool once = allow_lds(kern, 2 * STAGE_BYTES);
   const double es = sizeof(T), esc = ep.c_f32 ? 4.0 : es;
-  const char* kind = VARIANT_KINDS[variant - 1][sizeof(T) == 2][LAYOUT];
+  const char* kind = VARIANT_KINDS[variant_row(variant)][sizeof(T) == 2][LAYOUT];
   if (imt_prof_enabled() && getenv("IMT_PROF_SHAPES")) kind = imt_prof_intern(kind, a->M, a->N, a->K);
   ImtProfScope prof(kind, 2.0 * a->M * a->N * a->K, ((double)a->M * a->K + (double)a->N * a->K) * es + (double)a->M * a->N * esc, st);
   const T *A = reinterpret_cast<const T*>(a->A), *B = reinterpret_cast<const T*>(a->B);
@@ -1176,8 +1081,6 @@ int launch(const imt_gemm_args* a, const GemmFacts& f, EpiParams ep, int splits,
       break;
     }
     case V_SBUF: hipLaunchKernelGGL((gemm_sb_kernel<T, LAYOUT>), grid, dim3(NTHREADS), STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
-    case V_DMA3: hipLaunchKernelGGL(kpipe, grid, dim3(NTHREADS), 3 * STAGE_BYTES, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, kps, ep); break;
-    case V_DMA4: hipLaunchKernelGGL(kpipe4, grid, dim3(NTHREADS), 4 * STAGE_BYTES, st, A, a->lda, f.a_bytes, B, a->ldb, f.b_bytes, a->M, a->N, a->K, kps, ep); break;
     case V_DBUF: hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
   }
   IMT_CHECK_LAUNCH();
@@ -1523,9 +1426,8 @@ Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, const GemmSwi
   }
   // what a variant cannot run goes to its nearest relative that can
   if (v == V_XL && (!f.pipe_ok || splits > 1 || (a->a_colsum && !tn))) v = V_SBUF;
-  if ((v == V_DMA3 || v == V_DMA4) && !f.pipe_ok) v = V_DBUF;
   if (v == V_WS && (!f.pipe_ok || splits > 1)) v = V_SBUF;
-  return v >= V_DBUF && v <= V_XL ? (Variant)v : V_DBUF;  // (any other code has always meant the register-staged kernel)
+  return (v == V_SBUF || v == V_WS || v == V_XL) ? (Variant)v : V_DBUF;  // (any other code has always meant the register-staged kernel)
 }
 int run_single(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits, int kps, void* stream) {
   const Variant variant = choose_variant(a, f, sw, splits, sw.share_cus >= 0 ? sw.share_cus != 0 : g_share_cus != 0);
@@ -1629,7 +1531,7 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
     bytes += ((double)a.M + a.N) * a.K * es + 4.0 * a.M * a.N;
   }
   g.total_tiles = start;
-  static const bool once = allow_lds(gemm_grouped_tn_kernel<float>, GROUP_NST * STAGE_BYTES) && allow_lds(gemm_grouped_tn_kernel<bf16_t>, GROUP_NST * STAGE_BYTES);
+  static const bool once_f32 = allow_lds(gemm_grouped_tn_kernel<float>, GROUP_NST * STAGE_BYTES), once_bf16 = allow_lds(gemm_grouped_tn_kernel<bf16_t>, GROUP_NST * STAGE_BYTES);
   ImtProfScope prof(dtype == IMT_BF16 ? "gemm_bf16_tn_grouped" : "gemm_f32_tn_grouped", flops, bytes, st);
   auto kern = (dtype == IMT_F32) ? gemm_grouped_tn_kernel<float> : gemm_grouped_tn_kernel<bf16_t>;
   hipLaunchKernelGGL(kern, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);

@@ -2,9 +2,8 @@
 // with logit = x W^T + bias, WITHOUT ever storing the [N, V] logits.
 //
 // score_xl_kernel is gemm_xl_kernel's NT main loop (gemm_xl.hpp: 256 x 256 tile, two 64-KiB LDS-DMA stages, 8 waves as
-// 2 (m) x 4 (n), acc[8][4] per wave) with an epilogue that REDUCES the tile.  Lane (lr, lg) of wave (wmi, wni) owns, for
-// i = 0..7, j = 0..3, the 4 consecutive columns n0 + 64 wni + 16 j + 4 lg + e of row m0 + 128 wmi + 16 i + lr.  Per 16-row
-// group i:
+// 2 (m) x 4 (n), acc[8][4] per wave) with an epilogue that REDUCES the tile.  A lane holds, per 16-row group i = 0..7, four
+// quads j of consecutive columns of one row (XlOwn, gemm_xl.hpp).  Per group i:
 //   1. v = acc + bias (columns >= V of the ragged last tile -> -inf: the DMA zero-filled them, they must not count);
 //      (max, sum exp(v - max)) over the lane's 16 values;
 //   2. the 4 lanes lg of a row combine with two xor-shuffles (16, 32) -> the wave's 64 columns;
@@ -29,10 +28,10 @@ IMT_DEVICE void lse_merge(float& m, float& s, float m2, float s2) {
 constexpr int SCORE_ROWS = 256;  // rows per workgroup of both kernels
 
 template <typename T, bool RAGGED_N>
-IMT_DEVICE void score_tile_reduce(const f32x4 (&acc)[8][4], f32x2* red, int m0, int n0, int wmi, int wni, int N, int V,
+IMT_DEVICE void score_tile_reduce(const f32x4 (&acc)[8][4], f32x2* red, int m0, int n0, const XlWave w, int N, int V,
                                   const T* __restrict__ bias, const int64_t* __restrict__ target, float* __restrict__ tlogit) {
-  const int lane = threadIdx.x & 63, lr = lane & 15, lg = lane >> 4;
-  const int nl = n0 + 64 * wni + 4 * lg;  // first column of this lane's j = 0 quad
+  const XlOwn own(w);
+  const int nl = n0 + own.col(0);  // first column of this lane's j = 0 quad
   f32x4 bv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -46,7 +45,7 @@ IMT_DEVICE void score_tile_reduce(const f32x4 (&acc)[8][4], f32x2* red, int m0, 
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const int rl = 128 * wmi + 16 * i + lr, row = m0 + rl;
+    const int rl = own.row(i), row = m0 + rl;
     const int64_t t = row < N ? target[row] : (int64_t)-1;
     // column of the target relative to this lane's first column: 16 j + e for e < 4, anything else is not mine
     const int tc = (t >= 0 && t < V) ? (int)t - nl : -1;
@@ -89,7 +88,7 @@ IMT_DEVICE void score_tile_reduce(const f32x4 (&acc)[8][4], f32x2* red, int m0, 
       const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(s, o, 64);
       lse_merge(mx, s, mo, so);
     }
-    if (lg == 0) red[rl * 4 + wni] = f32x2{mx, s};
+    if (own.lg == 0) red[rl * 4 + w.wni] = f32x2{mx, s};
   }
 }
 
@@ -106,40 +105,22 @@ __global__ __launch_bounds__(XL_THREADS) void score_xl_kernel(const T* __restric
   const int bx = bid % nbx;
   const int m0 = (bid / nbx) * 256, n0 = bx * 256;
   const int nt = K / BK;  // whole K tiles (host-checked)
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wmi = wave >> 2, wni = wave & 3, wn = (wni & 1) * 64;
-  const bool loads_a = wave < 4;
+  const XlWave w;
 
   IMT_STAMP(trace, 0);
   DmaPair<T> dma;
-  if (loads_a) dma.template init<true>(X, ldx, x_bytes, m0, wave);
-  else         dma.template init<true>(W, ldw, w_bytes, n0, wave - 4);
-  auto issue = [&](int slot, int t) { dma.issue(smem + slot * XL_STAGE + (loads_a ? 0 : 2 * TILE_BYTES), t); };
+  if (w.loads_a) dma.template init<true>(X, ldx, x_bytes, m0, w.wave);
+  else           dma.template init<true>(W, ldw, w_bytes, n0, w.wave - 4);
 
   f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // the main loop of gemm_xl_kernel (same K order: the logits are the ones imt_gemm would have produced in fp32)
-  issue(0, 0);
-  for (int t = 0; t < nt; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    const bool issue_now = t + 1 < nt;
-    if (issue_now && wave < 4) issue((t + 1) & 1, t + 1);
-    if (t == 0) IMT_STAMP(trace, 1);
-    const char* st = smem + (t & 1) * XL_STAGE;
-    compute_tile_xl<T, IMT_NT, 0>(acc, st + wmi * TILE_BYTES, st + (2 + (wni >> 1)) * TILE_BYTES, wn);
-    if (issue_now && wave >= 4) issue((t + 1) & 1, t + 1);
-    compute_tile_xl<T, IMT_NT, 1>(acc, st + wmi * TILE_BYTES, st + (2 + (wni >> 1)) * TILE_BYTES, wn);
-  }
+  xl_zero(acc);
+  // gemm_xl_kernel's own K loop: the logits are the ones imt_gemm would have produced in fp32
+  xl_k_loop<T, IMT_NT>(acc, smem, dma, w, 0, nt, 0, trace, [](const char*) {});
   IMT_STAMP(trace, 2);
   __syncthreads();  // everyone has read the last stage: LDS is free
   f32x2* red = reinterpret_cast<f32x2*>(smem);  // [256 rows][4 waves wni], 8 KiB
-  if (n0 + 256 > V) score_tile_reduce<T, true>(acc, red, m0, n0, wmi, wni, N, V, bias, target, tlogit);
-  else              score_tile_reduce<T, false>(acc, red, m0, n0, wmi, wni, N, V, bias, target, tlogit);
+  if (n0 + 256 > V) score_tile_reduce<T, true>(acc, red, m0, n0, w, N, V, bias, target, tlogit);
+  else              score_tile_reduce<T, false>(acc, red, m0, n0, w, N, V, bias, target, tlogit);
   __syncthreads();
   IMT_STAMP(trace, 3);
   if (threadIdx.x < SCORE_ROWS && m0 + (int)threadIdx.x < N) {
@@ -214,17 +195,14 @@ __global__ __launch_bounds__(SCORE_ROWS) void score_combine_kernel(const f32x2* 
   if (tid == 0) seg_score[seg] = (normalize && sh_cnt[0] > 0) ? sh_sum[0] / (float)sh_cnt[0] : sh_sum[0];
 }
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 template <typename T> int launch_score(const imt_score_args* a, hipStream_t st) {
-  static bool attr = false;
   auto kern = score_xl_kernel<T>;
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, XL_LDS); attr = true; }
+  static const bool lds_ok = allow_lds(kern, XL_LDS);
+  IMT_CHECK_LDS(lds_ok, "score_rows", XL_LDS);
   const int ntile = imt_cdiv(a->V, 256), nrb = imt_cdiv(a->N, 256);
   float* tlogit = reinterpret_cast<float*>(a->ws);
-  f32x2* part = reinterpret_cast<f32x2*>(reinterpret_cast<char*>(a->ws) + align256((int64_t)a->N * 4));
-  const int64_t x_bytes = ((int64_t)(a->N - 1) * a->ldx + a->K) * (int64_t)sizeof(T);
-  const int64_t w_bytes = ((int64_t)(a->V - 1) * a->ldw + a->K) * (int64_t)sizeof(T);
+  f32x2* part = reinterpret_cast<f32x2*>(reinterpret_cast<char*>(a->ws) + imt_align256((int64_t)a->N * 4));
+  const int64_t x_bytes = view_bytes(a->N, a->ldx, a->K, sizeof(T)), w_bytes = view_bytes(a->V, a->ldw, a->K, sizeof(T));
   const double es = sizeof(T);
   {
     const char* kind = sizeof(T) == 2 ? "score_xl_bf16" : "score_xl_f32";
@@ -252,7 +230,7 @@ template <typename T> int launch_score(const imt_score_args* a, hipStream_t st) 
 
 extern "C" int64_t imt_score_ws_bytes(int N, int V) {
   if (N <= 0 || V <= 0) return 0;
-  return align256((int64_t)N * 4) + (int64_t)imt_cdiv(V, 256) * N * 8;
+  return imt_align256((int64_t)N * 4) + (int64_t)imt_cdiv(V, 256) * N * 8;
 }
 
 extern "C" int imt_score_supported(int dtype, int V, int K) {
@@ -277,11 +255,9 @@ extern "C" int imt_score_rows(const imt_score_args* a, void* stream) {
                 (long long)(a->ws ? a->ws_bytes : 0), (long long)imt_score_ws_bytes(a->N, a->V));
   IMT_CHECK_ARG(imt_score_supported(a->dtype, a->V, a->K), "score_rows: (dtype %d, V %d, K %d) is not taken by the fused kernel (K must be a whole "
                 "number of 128-byte K tiles)", a->dtype, a->V, a->K);
-  const int es = imt_dtype_bytes(a->dtype), epv = 16 / es;
-  IMT_CHECK_ARG(a->ldx >= a->K && a->ldx % epv == 0 && (uintptr_t)a->x % 16 == 0, "score_rows: ldx / x must keep rows 16-byte aligned");
-  IMT_CHECK_ARG(a->ldw >= a->K && a->ldw % epv == 0 && (uintptr_t)a->w % 16 == 0, "score_rows: ldw / w must keep rows 16-byte aligned");
-  IMT_CHECK_ARG(((int64_t)(a->N + 256) * a->ldx) * es < ((int64_t)1 << 31) && ((int64_t)(a->V + 256) * a->ldw) * es < ((int64_t)1 << 31),
-                "score_rows: x / w views beyond 2 GiB (32-bit DMA offsets)");
+  const int es = imt_dtype_bytes(a->dtype);
+  if (const int rc = xl_check_rows("score_rows", "x", "ldx", a->x, a->ldx, a->N, a->K, es)) return rc;
+  if (const int rc = xl_check_rows("score_rows", "w", "ldw", a->w, a->ldw, a->V, a->K, es)) return rc;
   IMT_CHECK_ARG(!a->bias || (uintptr_t)a->bias % 16 == 0, "score_rows: bias must be 16-byte aligned");
   IMT_CHECK_ARG((uintptr_t)a->ws % 16 == 0, "score_rows: ws must be 16-byte aligned");
   if (a->seg_offsets) {

@@ -110,10 +110,9 @@ typedef struct imt_gemm_args {
   float* a_colsum;        /* IMT_TN only, nullable: a_colsum[m] += alpha * sum_k A[k,m]  (bias gradient of the same
                              nn.Linear, fused into its weight-gradient GEMM: dy is read once) */
   int32_t force_general;  /* tests / tuning: kernel variant, 0 = auto, 1 = register-staged double buffer (2 blocks/CU),
-                             2 / 4 = LDS-DMA 3- / 4-stage ring (1 block/CU; K a whole number of tiles), 3 = single LDS
-                             buffer + register prefetch (3 blocks/CU), 5 = persistent wave-specialised (LDS-DMA
-                             producer waves, K a whole number of tiles), 6 = 256 x 256 tiles (NT / NN, K a whole
-                             number of tiles) */
+                             2 / 4: retired, run as 1, 3 = single LDS buffer + register prefetch (3 blocks/CU),
+                             5 = persistent wave-specialised (LDS-DMA producer waves, K a whole number of tiles),
+                             6 = 256 x 256 tiles (NT / NN, K a whole number of tiles) */
   int32_t force_pipeline; /* reserved */
   /* LayerNorm of the finished rows of C, in the same call (HF BertSelfOutput / BertOutput, src/bert_seq2seq.py:84-90,
    * 139-143: LayerNorm(dropout(dense(x)) + input) with the bias / dropout / residual epilogue above).  ln_out != NULL:

@@ -88,7 +88,7 @@ CASES = [
     ("TN", 256, 256, 1024, {"split_k": 4}, ["gemm_dbuf_bf16_tn"]),
     ("NT", 512, 512, 136, {"force": 6}, ["gemm_sbuf_bf16_nt"]),
     ("NT", 512, 512, 64, {"force": 2}, ["gemm_dbuf_bf16_nt"]),
-    ("NT", 512, 512, 256, {"force": 4}, ["gemm_dma_bf16_nt"]),
+    ("NT", 512, 512, 256, {"force": 4}, ["gemm_dbuf_bf16_nt"]),
     ("NN", 512, 512, 4104, {"slabs": 4}, ["gemm_sbuf_bf16_nn", "gemm_xl_bf16_nn", "gemm_splitk_reduce"]),
 ]
 

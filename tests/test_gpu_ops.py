@@ -153,17 +153,15 @@ def test_gemm_pipelined_vs_general_kernel(cuda, dtype, layout):
         da = wa.to(dtype).to(cuda)[:, 8:8 + a_in.shape[1]]
         db = wb.to(dtype).to(cuda)[:, 16:16 + b_in.shape[1]]
         outs = []
-        for force in (2, 1, 3, 5, 6):  # LDS-DMA ring, register double buffer, single buffer, persistent wave-specialised, 256-tile
+        for force in (1, 3, 5, 6):  # register double buffer, single buffer, persistent wave-specialised, 256-tile
             out = torch.zeros((M, N), device=cuda, dtype=torch.float32)
             O.gemm(da, db, layout, out=out, split_k=sk if layout == O.IMT_TN else 1,
                    accumulate=False, force_general=force)
             outs.append(out.cpu())
-        assert torch.equal(outs[0], ref), "pipelined kernel wrong: layout %d %s max diff %g" % (
-            layout, (M, N, K), float((outs[0] - ref).abs().max()))
-        assert torch.equal(outs[1], ref), "general kernel wrong"
-        assert torch.equal(outs[2], ref), "single-buffer kernel wrong"
-        assert torch.equal(outs[3], ref), "wave-specialised kernel wrong"
-        assert torch.equal(outs[4], ref), "256 x 256-tile kernel wrong"
+        assert torch.equal(outs[0], ref), "general kernel wrong"
+        assert torch.equal(outs[1], ref), "single-buffer kernel wrong"
+        assert torch.equal(outs[2], ref), "wave-specialised kernel wrong"
+        assert torch.equal(outs[3], ref), "256 x 256-tile kernel wrong"
 
 
 @pytest.mark.parametrize("layout", [0, 1])
