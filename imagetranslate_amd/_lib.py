@@ -217,6 +217,7 @@ SIGNATURES = {
     "imt_last_error": (c_char_p, []),
     "imt_gemm": (c_int, [POINTER(GemmArgs), _P]),
     "imt_gemm_grouped_tn": (c_int, [POINTER(GemmArgs), c_int, _P]),
+    "imt_gemm_grouped_tile_order": (c_int, [POINTER(c_int), POINTER(c_int), c_int, c_int, POINTER(c_int), c_int]),
     "imt_gemm_splitk_ws_bytes": (c_int64, []),
     "imt_gemm_bias_residual_ln_supported": (c_int, [c_int, c_int, c_int]),
     "imt_gemm_bias_residual_ln": (c_int, [c_int, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int,
@@ -285,6 +286,7 @@ SIGNATURES = {
     "imt_comm_broadcast": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
     "imt_comm_destroy": (c_int, [_P]),
     "imt_set_gemm_share_cus": (c_int, [c_int]),
+    "imt_set_gemm_grouped_tall_min_tiles": (c_int, [c_int]),
     "imt_debug_spin": (c_int, [c_int, c_int, c_int, c_int64, _P]),
     "imt_abi_sizeof": (c_int, [ctypes.c_char_p]),
     "imt_prof_enable": (c_int, [c_int]),

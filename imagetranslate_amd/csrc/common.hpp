@@ -50,6 +50,10 @@ template <typename F> static inline int imt_by_dtype(int dtype, F&& f) {
   return dtype == IMT_F32 ? f(ImtType<float>()) : f(ImtType<bf16_t>());
 }
 
+// imt_gemm_grouped_tn's choice of instance for a list it can group (gemm.hip): true = 256 x 128 tiles.  The stack's backward asks
+// it whether a pair of layers is worth one launch (model.hip).
+bool imt_gemm_grouped_tall(const imt_gemm_args* list, int count);
+
 // ---------------------------------------------------------------- optional launch profiler (core.hip)
 bool imt_prof_enabled();
 const char* imt_prof_intern(const char* kind, int M, int N, int K);

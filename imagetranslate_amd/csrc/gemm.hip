@@ -850,14 +850,36 @@ __global__ __launch_bounds__(XL_THREADS) void gemm_xl_kernel(const T* __restrict
 // ------------------------------------------------------------------------------------------------ grouped weight gradients
 // All weight-gradient GEMMs of one transformer layer (dW = dy^T x, K = tokens) in ONE launch: each has only 16-64
 // output tiles, so separately they either idle most CUs or need split-K atomics; together they are ~one tile per
-// CU with the full K per block (long steady-state LDS-DMA pipeline, direct fp32 accumulate, no atomics).
-constexpr int MAX_GROUP = 8;
+// CU with the full K per block (long steady-state LDS-DMA pipeline, direct fp32 accumulate, no atomics).  Two layers in one
+// launch (model.hip) have enough tiles for 256 x 128 ones (grouped_tall_tile): same writer-per-tile scheme, same bits.
+constexpr int MAX_GROUP = 16;
 struct GroupProblem {
   const void* A; const void* B; float* C; float* a_colsum;
   int64_t lda, ldb, ldc, a_bytes, b_bytes;
-  int M, N, K, tile_start;
+  int M, N, K;
 };
-struct GroupArgs { int count; int total_tiles; float alpha; int alpha_pad_order /* tuning: 1 = plain workgroup order */; GroupProblem p[MAX_GROUP]; };
+struct GroupGrid { int rows, cols, tile_start; };  // tile grid of one problem; its tiles are tile_start .. of the group's list
+struct GroupTile { int problem, row, col; };
+struct GroupArgs { int count; int total_tiles; float alpha; int plain_order /* tuning: 1 = plain workgroup order */; GroupGrid grid[MAX_GROUP]; GroupProblem p[MAX_GROUP]; };
+
+// Hardware workgroup id -> output tile, for the kernel and for imt_gemm_grouped_tile_order.  Workgroup w runs on XCD w % 8;
+// XCD x takes the x-th of eight CONTIGUOUS runs of the group's tile list (row-major per problem; imt_xcd_block's split: the
+// first total % 8 runs are one longer), i.e. a few whole tile rows -- its workgroups then share dy / x operand strips through
+// that XCD's L2.  plain: workgroup w takes tile w.  (Walking each problem in bands, so that an XCD's share is a compact block
+// with fewer strips, moves fewer bytes and is no faster: DESIGN.md section 5.)
+__host__ __device__ inline GroupTile grouped_tile(int wg, int total, int count, const GroupGrid* grid, bool plain) {
+  int pos = wg;
+  if (!plain) {
+    const int q = total >> 3, r = total & 7, xcd = wg & 7, idx = wg >> 3;
+    pos = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < MAX_GROUP; ++i)
+    if (i < count && pos >= grid[i].tile_start) pi = i;
+  const int local = pos - grid[pi].tile_start, cols = grid[pi].cols;
+  return GroupTile{pi, local / cols, local % cols};
+}
 
 // Wave-specialised: waves 0-3 multiply (one per SIMD), waves 4-7 only issue the LDS-DMA of the tiles ahead.  Issuing
 // a 1-KiB DMA piece costs a wave ~100-200 cycles (MI355X_MICROARCH "LDS-DMA piece issue cost"); done by the MFMA waves
@@ -929,24 +951,176 @@ IMT_DEVICE void grouped_consumer_loop(f32x4 (&acc)[4][4], f32x4 (&bacc)[2], cons
   }
 }
 
+// ---- the 256 x 128 instance (TM = 256): 0.75 of the operand bytes per flop.  Its ring holds K slabs of ONE k-step (half a K
+// tile: 8 KiB of dy columns m0.., 8 KiB of m0 + 128.., 8 KiB of x), six of them: one being multiplied, one landed, four in
+// flight -- a K slab is landed ~1.1 us after its issue whatever its size, so what a CU streams is what it keeps in flight.
+constexpr int SLAB_PART = TILE_BYTES / 2;
+constexpr int TALL_SLAB = 3 * SLAB_PART;
+constexpr int TALL_NST = 6;  // 144 KiB
+
+// One producer wave's quarter of a K slab: pieces wave and wave + 4 of each of the three parts (Dma's piece order and swizzle).
+template <typename T> struct SlabDma {
+  typedef TileGeom<T, false> G;
+  __amdgpu_buffer_rsrc_t ra, rb;
+  int va[2], vb[2], kadv_a, kadv_b, wv;
+  IMT_DEVICE void init(const GroupProblem& P, int m0, int n0, int wave) {
+    ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(P.A), 0, (int)P.a_bytes, 0x00020000);
+    rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(P.B), 0, (int)P.b_bytes, 0x00020000);
+    const int lane = threadIdx.x & 63;
+    wv = wave;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int q = 64 * (4 * i + wave) + lane;
+      const int tr = q / G::CPR, pc = q % G::CPR;
+      const int c = pc ^ swz<G::RB>(tr);
+      va[i] = (int)((((int64_t)tr) * P.lda + m0 + c * G::EPC) * (int64_t)sizeof(T));
+      vb[i] = (int)((((int64_t)tr) * P.ldb + n0 + c * G::EPC) * (int64_t)sizeof(T));
+    }
+    kadv_a = (int)(Frag<T>::KSTEP * P.lda * (int64_t)sizeof(T));
+    kadv_b = (int)(Frag<T>::KSTEP * P.ldb * (int64_t)sizeof(T));
+  }
+  // (every part of the source offset in the VECTOR offset: the descriptor's range check covers nothing else, DmaPair)
+  IMT_DEVICE void issue(char* slab, int t) const {
+    const int wave = __builtin_amdgcn_readfirstlane(wv);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      char* dst = slab + (4 * i + wave) * 1024;
+      const int oa = va[i] + t * kadv_a, ob = vb[i] + t * kadv_b;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, oa, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(dst + SLAB_PART), 16, oa + 128 * (int)sizeof(T), 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void*)(dst + 2 * SLAB_PART), 16, ob, 0, 0, 0);
+    }
+  }
+};
+// all of this wave's pieces have landed but those of its `newer` youngest slabs (six pieces each, at most four slabs)
+IMT_DEVICE void slab_wait_newer(int newer) {
+  if (newer >= 4)      asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+  else if (newer == 3) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+  else if (newer == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+  else if (newer == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// Consumer wave (wmi, wn): rows 128 wmi .. +127 by columns wn .. +63 of the tile, acc[8][4] as in compute_tile_xl.  While the
+// 32 products of slab t run, the twelve fragments of slab t + 1 are read one by one under them: x fragments into a second
+// set, the dy fragment i into the registers of this slab's fragment i once its four products (and its bias-gradient
+// product: CS, the half of the fragments LO selects) are issued.
+template <typename T, bool CS, bool LO>
+IMT_DEVICE void grouped_consumer_loop_tall(f32x4 (&acc)[8][4], f32x4 (&bacc)[4], const char* smem, int ns, int wmi, int wn) {
+  typedef typename Frag<T>::type frag_t;
+  typedef TileGeom<T, false> G;
+  constexpr int MPF = sizeof(T) == 2 ? 1 : 4;  // MFMA instructions per fragment pair
+  constexpr int RPF = sizeof(T) == 2 ? 2 : 4;  // LDS reads per fragment
+  frag_t fa[8], fb[4];
+  const frag_t ones = ones_frag<T>();
+  asm volatile("s_barrier" ::: "memory");  // slab 0 landed
+#pragma unroll
+  for (int j = 0; j < 4; ++j) fb[j] = KStrided<T, G::RB>::load(smem + 2 * SLAB_PART, 0, wn + 16 * j);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) fa[i] = KStrided<T, G::RB>::load(smem + wmi * SLAB_PART, 0, 16 * i);
+  int cur = 0;
+  for (int t = 0; t < ns; ++t) {
+    asm volatile("s_barrier" ::: "memory");  // slab t + 1 landed
+    const int nxt = (cur + 1 == TALL_NST) ? 0 : cur + 1;
+    const char* sn = smem + nxt * TALL_SLAB;  // past the last slab: read and never used
+    frag_t nb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nb[j] = KStrided<T, G::RB>::load(sn + 2 * SLAB_PART, 0, wn + 16 * j);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mma16(acc[i][j], fb[j], fa[i]);
+      if (CS && (LO ? i < 4 : i >= 4)) mma16(bacc[i & 3], ones, fa[i]);
+      fa[i] = KStrided<T, G::RB>::load(sn + wmi * SLAB_PART, 0, 16 * i);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) fb[j] = nb[j];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, (CS && LO ? 5 : 4) * MPF, 0);  // MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, 3 * RPF / 2, 0);                // DS reads
+    }
+#pragma unroll
+    for (int i = 4; i < 8; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, (CS && !LO ? 5 : 4) * MPF, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 3 * RPF / 2, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    cur = nxt;
+  }
+}
+
 template <typename T>
+IMT_DEVICE void grouped_tall_tile(const GroupArgs& g, const GroupProblem& P, int m0, int n0, char* smem) {
+  const int M = P.M, N = P.N, K = P.K;
+  const int ns = (K + Frag<T>::KSTEP - 1) / Frag<T>::KSTEP;  // a ragged last slab reads zeros past the operands' valid bytes
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool consumer = wave < 4;
+  const int wmi = (wave & 3) >> 1, wn = (wave & 1) * 64;
+  f32x4 acc[8][4];
+  xl_zero(acc);
+  f32x4 bacc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bacc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_colsum = P.a_colsum && n0 == 0;
+  if (!consumer) {
+    SlabDma<T> dma;
+    dma.init(P, m0, n0, wave - 4);
+#pragma unroll
+    for (int s0 = 0; s0 < TALL_NST - 1; ++s0)
+      if (s0 < ns) dma.issue(smem + s0 * TALL_SLAB, s0);
+    // barrier t tells the consumers that slab t + 1 has landed, and the producers that slab t - 1 has been multiplied: its
+    // slot takes slab t + 5 (the fragments of slab t may still be on their way to the registers)
+    slab_wait_newer(min(TALL_NST - 2, ns - 1));
+    asm volatile("s_barrier" ::: "memory");  // slab 0 landed
+    int cur = 0;
+    for (int t = 0; t < ns; ++t) {
+      slab_wait_newer(max(0, min(TALL_NST - 3, ns - 2 - t)));  // slabs issued after slab t + 1
+      asm volatile("s_barrier" ::: "memory");
+      if (t + TALL_NST - 1 < ns) dma.issue(smem + ((cur == 0) ? TALL_NST - 1 : cur - 1) * TALL_SLAB, t + TALL_NST - 1);
+      cur = (cur + 1 == TALL_NST) ? 0 : cur + 1;
+    }
+  } else {
+    if (!do_colsum)   grouped_consumer_loop_tall<T, false, false>(acc, bacc, smem, ns, wmi, wn);
+    else if (wn == 0) grouped_consumer_loop_tall<T, true, true>(acc, bacc, smem, ns, wmi, wn);
+    else              grouped_consumer_loop_tall<T, true, false>(acc, bacc, smem, ns, wmi, wn);
+  }
+  EpiParams ep;
+  ep.C = P.C; ep.ldc = P.ldc; ep.c_f32 = 1; ep.accumulate = 1;
+  ep.bias = nullptr; ep.resid = nullptr; ep.ldr = 0; ep.aux = nullptr; ep.ldaux = 0; ep.aux_mode = IMT_AUX_NONE;
+  ep.atomic = 0; ep.alpha = g.alpha; ep.alpha_dev = nullptr; ep.inv_keep = 1.f; ep.drop_thresh = 0; ep.seed = 0;
+  ep.a_colsum = P.a_colsum; ep.dbg = 0; ep.trace = nullptr;
+  // two 128-row halves through the restaged epilogue, all 8 waves each (the ring is free: every DMA has landed and been read)
+#pragma unroll 1
+  for (int q = 0; q < 2; ++q) {
+    const int mq = m0 + 128 * q;
+    if (mq >= M) continue;  // uniform over the workgroup
+    if (consumer && wmi == q) epilogue<T, 512, true, 128>(acc, smem, mq, n0, 0, wn, M, N, ep, g.alpha);
+    else                      epilogue<T, 512, false, 128>(acc, smem, mq, n0, 0, wn, M, N, ep, g.alpha);
+  }
+  if (do_colsum && consumer && (threadIdx.x & 63) < 16) {
+    const int mb = m0 + 128 * wmi + ((wn == 0) ? 0 : 64) + (threadIdx.x & 15);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (mb + 16 * k < M) atomicAdd(P.a_colsum + mb + 16 * k, bacc[k][0] * g.alpha);
+  }
+}
+
+template <typename T, int TM>
 __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArgs g) {
   constexpr int BK = TileGeom<T, false>::BK;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // XCD-affine tile order: hardware workgroup b runs on XCD b % 8; give each XCD a CONTIGUOUS run of the group's tile list
-  // (row-major per problem), i.e. a few whole tile rows -- its workgroups then share dy / x operand strips through that
-  // XCD's L2.  With the plain order every XCD saw one column and ~24 different rows: 549 MB of fabric traffic per launch
-  // against 160 MB algorithmic, and the kernel ran at the fabric's ~6 TB/s.
-  const int bid = (g.alpha_pad_order == 0) ? imt_xcd_block(blockIdx.x, g.total_tiles) : (int)blockIdx.x;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_GROUP; ++i)
-    if (i < g.count && bid >= g.p[i].tile_start) pi = i;
-  const GroupProblem& P = g.p[pi];
+  if constexpr (TM == 256) {
+    const GroupTile tile = grouped_tile(blockIdx.x, g.total_tiles, g.count, g.grid, g.plain_order != 0);
+    grouped_tall_tile<T>(g, g.p[tile.problem], tile.row * 256, tile.col * BN, smem);
+    return;
+  }
+  // XCD-affine tile order (grouped_tile).  With the plain order every XCD saw one column and ~24 different rows: 549 MB of
+  // fabric traffic per launch against 160 MB algorithmic, and the kernel ran at the fabric's ~6 TB/s.
+  const GroupTile tile = grouped_tile(blockIdx.x, g.total_tiles, g.count, g.grid, g.plain_order != 0);
+  const GroupProblem& P = g.p[tile.problem];
   const int M = P.M, N = P.N, K = P.K;
-  const int nbx = (N + BN - 1) / BN;
-  const int local = bid - P.tile_start;
-  const int m0 = (local / nbx) * BM, n0 = (local % nbx) * BN;
+  const int m0 = tile.row * BM, n0 = tile.col * BN;
   const int nt = (K + BK - 1) / BK;  // a ragged last K tile (token counts are arbitrary) reads zeros past the operands' valid bytes
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool consumer = wave < 4;
@@ -1489,6 +1663,54 @@ extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
   return run_single(a, f, sw, splits, kps, stream);
 }
 
+// Which instance a group takes -- a pure function of the problem list and the CU count: 256 x 128 tiles when every row count
+// is a multiple of 256 and those tiles still give three quarters of the CUs one each (a pair of layers of the flagship
+// model, a single layer of a wider one), 128 x 128 otherwise.  imt_set_gemm_grouped_tall_min_tiles (tests / tuning) replaces
+// the three quarters.  A list of more than GROUP_MAX_TILES 128 x 128 tiles is not grouped at all, whatever the instance.
+constexpr int GROUP_CUS = 256;        // MI355X
+constexpr int GROUP_MAX_TILES = 640;  // counted in 128 x 128 tiles; beyond: one imt_gemm per product
+static int g_tall_min_tiles = 0;
+static bool grouped_tall(const imt_gemm_args* list, int count, int cus) {
+  int tiles = 0;
+  for (int i = 0; i < count; ++i) {
+    if (list[i].M % 256 != 0) return false;
+    tiles += (list[i].M / 256) * imt_cdiv(list[i].N, BN);
+  }
+  return 2 * tiles <= GROUP_MAX_TILES && (g_tall_min_tiles > 0 ? tiles >= g_tall_min_tiles : 4 * tiles >= 3 * cus);
+}
+extern "C" int imt_set_gemm_grouped_tall_min_tiles(int min_tiles) {
+  const int prev = g_tall_min_tiles;
+  return g_tall_min_tiles = min_tiles > 0 ? min_tiles : 0, prev;
+}
+bool imt_gemm_grouped_tall(const imt_gemm_args* list, int count) { return count >= 1 && count <= MAX_GROUP && grouped_tall(list, count, GROUP_CUS); }
+
+// The grids of a group with rows[i] x cols[i] tiles and their places in the tile list; returns the tile count.
+static int grouped_grids(const int* rows, const int* cols, int count, GroupGrid* grid) {
+  int start = 0;
+  for (int i = 0; i < count; ++i) {
+    grid[i] = GroupGrid{rows[i], cols[i], start};
+    start += rows[i] * cols[i];
+  }
+  return start;
+}
+
+extern "C" int imt_gemm_grouped_tile_order(const int* tile_rows, const int* tile_cols, int count, int plain, int* order, int order_tiles) {
+  IMT_CHECK_ARG(tile_rows && tile_cols && order && count >= 1 && count <= MAX_GROUP, "imt_gemm_grouped_tile_order: bad args");
+  int64_t total = 0;
+  for (int i = 0; i < count; ++i) {
+    IMT_CHECK_ARG(tile_rows[i] >= 1 && tile_cols[i] >= 1 && tile_rows[i] <= 640 && tile_cols[i] <= 640, "imt_gemm_grouped_tile_order: bad tile grid");
+    total += (int64_t)tile_rows[i] * tile_cols[i];
+  }
+  IMT_CHECK_ARG(total <= GROUP_MAX_TILES && total == order_tiles, "imt_gemm_grouped_tile_order: the group has %d tiles (at most 640), order_tiles is %d", (int)total, order_tiles);
+  GroupGrid grid[MAX_GROUP];
+  grouped_grids(tile_rows, tile_cols, count, grid);
+  for (int w = 0; w < order_tiles; ++w) {
+    const GroupTile t = grouped_tile(w, order_tiles, count, grid, plain != 0);
+    order[3 * w] = t.problem; order[3 * w + 1] = t.row; order[3 * w + 2] = t.col;
+  }
+  return IMT_OK;
+}
+
 extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* stream) {
   IMT_CHECK_ARG(list && count >= 0, "imt_gemm_grouped_tn: bad args");
   if (count == 0) return IMT_OK;
@@ -1506,7 +1728,7 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
          (int64_t)a.K * a.ldb * es < (1ll << 31);
     tiles += imt_cdiv(a.M, BM) * imt_cdiv(a.N, BN);
   }
-  if (!ok || tiles > 640) {
+  if (!ok || tiles > GROUP_MAX_TILES) {
     // not groupable (ragged K, too many problems, ...): individual launches with their own split-K choice
     for (int i = 0; i < count; ++i) {
       int rc = imt_gemm(&list[i], stream);
@@ -1514,10 +1736,12 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
     }
     return IMT_OK;
   }
+  const bool tall = grouped_tall(list, count, GROUP_CUS);
+  const int tm = tall ? 256 : BM;
   GroupArgs g;
   memset(&g, 0, sizeof(g));
-  g.count = count; g.alpha = list[0].alpha; g.alpha_pad_order = gemm_switches().grouped_plain_order ? 1 : 0;
-  int start = 0;
+  g.count = count; g.alpha = list[0].alpha; g.plain_order = gemm_switches().grouped_plain_order ? 1 : 0;
+  int rows[MAX_GROUP], cols[MAX_GROUP];
   double flops = 0, bytes = 0;
   for (int i = 0; i < count; ++i) {
     const imt_gemm_args& a = list[i];
@@ -1525,16 +1749,22 @@ extern "C" int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* s
     P.A = a.A; P.B = a.B; P.C = reinterpret_cast<float*>(a.C); P.a_colsum = a.a_colsum;
     P.lda = a.lda; P.ldb = a.ldb; P.ldc = a.ldc;
     P.a_bytes = view_bytes(a.K, a.lda, a.M, es); P.b_bytes = view_bytes(a.K, a.ldb, a.N, es);
-    P.M = a.M; P.N = a.N; P.K = a.K; P.tile_start = start;
-    start += imt_cdiv(a.M, BM) * imt_cdiv(a.N, BN);
+    P.M = a.M; P.N = a.N; P.K = a.K;
+    rows[i] = imt_cdiv(a.M, tm); cols[i] = imt_cdiv(a.N, BN);
     flops += 2.0 * a.M * a.N * a.K;
     bytes += ((double)a.M + a.N) * a.K * es + 4.0 * a.M * a.N;
   }
-  g.total_tiles = start;
-  static const bool once_f32 = allow_lds(gemm_grouped_tn_kernel<float>, GROUP_NST * STAGE_BYTES), once_bf16 = allow_lds(gemm_grouped_tn_kernel<bf16_t>, GROUP_NST * STAGE_BYTES);
+  const int start = g.total_tiles = grouped_grids(rows, cols, count, g.grid);
+  static const bool once_f32 = allow_lds(gemm_grouped_tn_kernel<float, 128>, GROUP_NST * STAGE_BYTES), once_bf16 = allow_lds(gemm_grouped_tn_kernel<bf16_t, 128>, GROUP_NST * STAGE_BYTES);
+  static const bool tall_f32 = allow_lds(gemm_grouped_tn_kernel<float, 256>, TALL_NST * TALL_SLAB), tall_bf16 = allow_lds(gemm_grouped_tn_kernel<bf16_t, 256>, TALL_NST * TALL_SLAB);
   ImtProfScope prof(dtype == IMT_BF16 ? "gemm_bf16_tn_grouped" : "gemm_f32_tn_grouped", flops, bytes, st);
-  auto kern = (dtype == IMT_F32) ? gemm_grouped_tn_kernel<float> : gemm_grouped_tn_kernel<bf16_t>;
-  hipLaunchKernelGGL(kern, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);
+  if (tall) {
+    auto kern = (dtype == IMT_F32) ? gemm_grouped_tn_kernel<float, 256> : gemm_grouped_tn_kernel<bf16_t, 256>;
+    hipLaunchKernelGGL(kern, dim3(start), dim3(GROUP_THREADS), TALL_NST * TALL_SLAB, st, g);
+  } else {
+    auto kern = (dtype == IMT_F32) ? gemm_grouped_tn_kernel<float, 128> : gemm_grouped_tn_kernel<bf16_t, 128>;
+    hipLaunchKernelGGL(kern, dim3(start), dim3(GROUP_THREADS), GROUP_NST * STAGE_BYTES, st, g);
+  }
   IMT_CHECK_LAUNCH();
   return IMT_OK;
 }

@@ -48,12 +48,13 @@ struct StackWs {
   void* d_q;                         // [N,d]   cross-attention query gradient
   void* d_kv;                        // [Nk,2d]
   void* d_emb;                       // [N,d]  gradient w.r.t. the embedding sum (its own buffer: see below)
-  // The seven kinds of buffer above exist TWICE (even / odd layers): the weight-gradient launch of layer l may run on
-  // the side stream while layer l-1 already writes its own dy operands (imt_stack_backward); use_scratch(l) points the
-  // fields above at the set of layer l.
-  struct Scratch { void* dpre[3]; void* ddrop[3]; void* d_ctx; void* d_ff; void* d_qkv; void* d_q; void* d_kv; } scr[2];
+  // The seven kinds of buffer above exist FOUR times (layer l uses set l % 4): the weight-gradient launch of the layer pair
+  // (l + 1, l) reads both layers' dy operands and may run on the side stream while layers l - 1 and l - 2 already write
+  // their own (imt_stack_backward); use_scratch(l) points the fields above at the set of layer l.
+  static constexpr int N_SCRATCH = 4;
+  struct Scratch { void* dpre[3]; void* ddrop[3]; void* d_ctx; void* d_ff; void* d_qkv; void* d_q; void* d_kv; } scr[N_SCRATCH];
   void use_scratch(int l) {
-    const Scratch& z = scr[l & 1];
+    const Scratch& z = scr[l % N_SCRATCH];
     for (int i = 0; i < 3; ++i) { dpre[i] = z.dpre[i]; ddrop[i] = z.ddrop[i]; }
     d_ctx = z.d_ctx; d_ff = z.d_ff; d_qkv = z.d_qkv; d_q = z.d_q; d_kv = z.d_kv;
   }
@@ -118,7 +119,7 @@ void carve(const imt_stack_desc* m, int B, int T, int Tk, void* ws, StackWs& w, 
     L.out = c.take(N * d * es);
   }
   w.d_run = c.take(N * d * es);
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < StackWs::N_SCRATCH; ++k) {
     StackWs::Scratch& z = w.scr[k];
     for (int i = 0; i < 3; ++i) { z.dpre[i] = c.take(N * d * es); z.ddrop[i] = c.take(N * d * es); }
     z.d_ctx = c.take(N * d * es);
@@ -205,10 +206,18 @@ int dense_resid_ln(const Ctx& c, const void* x, int64_t ldx, int M, int K, int64
 }
 
 // Weight-gradient GEMMs of one layer are collected here and issued as ONE grouped launch at the end of the layer's
-// backward (dW[N,K] += dy[M,N]^T x[M,K] ; db[N] += colsum(dy), fused).
+// backward (dW[N,K] += dy[M,N]^T x[M,K] ; db[N] += colsum(dy), fused) -- or, where imt_gemm_grouped_tn then multiplies
+// 256 x 128 tiles, those of TWO layers at the end of the second one's (hold_for_pair).
 struct DeferredDW {
-  imt_gemm_args list[8];
+  imt_gemm_args list[16];
   int n = 0;
+  // the products collected so far are one layer's: would they and the same again, the next layer's, take the 256 x 128 instance?
+  bool hold_for_pair() const {
+    if (n == 0 || 2 * n > 16) return false;
+    imt_gemm_args two[16];
+    for (int i = 0; i < n; ++i) two[i] = two[n + i] = list[i];
+    return imt_gemm_grouped_tall(two, 2 * n);
+  }
   void add(const Ctx& c, const void* dy, int64_t lddy, const void* x, int64_t ldx, int M, int N, int K, int64_t w_off, int64_t b_off) {
     imt_gemm_args& a = list[n++];
     memset(&a, 0, sizeof(a));
@@ -464,14 +473,20 @@ extern "C" int imt_stack_backward(const imt_stack_desc* m, const imt_stack_io* i
   // and hands each layer's gradients to its all-reduce bucket as soon as the call returns) and IMT_DW_SIDE_STREAM != 0
   static const bool side_env = !(getenv("IMT_DW_SIDE_STREAM") && atoi(getenv("IMT_DW_SIDE_STREAM")) == 0);
   // (not while the per-launch event profiler is on: a launch timed next to a concurrent one is not that kernel's time)
-  const bool side = side_env && !imt_prof_enabled() && layer_lo == 0 && layer_hi == m->n_layers && m->n_layers >= 2 && g_side.init();
+  const bool whole = layer_lo == 0 && layer_hi == m->n_layers && m->n_layers >= 2;
+  const bool side = side_env && !imt_prof_enabled() && whole && g_side.init();
+  // layer pairs per launch: only over the whole stack too, and not under the per-launch event profiler (one launch per layer
+  // is what it reports)
+  const bool pairs = whole && !imt_prof_enabled();
   int last_side = -1;
+  int held = -1;  // the layer whose weight-gradient products wait in dw for those of the layer below
   for (int l = layer_hi - 1; l >= layer_lo; --l) {
     const imt_layer_desc& p = m->layers[l];
     LayerWs& L = layers[l];
     w.use_scratch(l);
-    // this layer writes the scratch set dW(l+2) read from: that launch must be over (it is, by a layer's worth of time)
-    if (side && l + 2 < layer_hi) (void)hipStreamWaitEvent(c.st, g_side.done[l + 2], 0);
+    // this layer writes the scratch set layer l + 4 used: the launch that read it (done[l + 4]: that layer's own or its
+    // pair's) must be over (it is, by two layers' worth of time)
+    if (side && l + StackWs::N_SCRATCH < layer_hi) (void)hipStreamWaitEvent(c.st, g_side.done[l + StackWs::N_SCRATCH], 0);
     if (l == m->n_layers - 1) L.out = io->out;
     const bool has_cross = m->is_decoder && p.cross_attn.qkv_w >= 0;
     const void* x_in = (l == 0) ? w.x0 : (const void*)layers[l - 1].out;
@@ -485,15 +500,22 @@ extern "C" int imt_stack_backward(const imt_stack_desc* m, const imt_stack_io* i
                         io->d_enc_states, first_cross ? 0 : 1, kv_w_off(m, p), kv_b_off(m, p), dkv_l));
     }
     RC(attn_block_bwd(c, p.self_attn, L.self_attn, w, dw, 2, x_in, B, T, nullptr, 0, self_ms, training, seed, l, 0, w.d_run, nullptr, 0));
-    // all 4 (encoder) / 7 (decoder) weight-gradient GEMMs of this layer: one launch
-    if (side) {
+    // all 4 (encoder) / 7 (decoder) weight-gradient GEMMs of this layer: one launch -- with those of the layer above, if this
+    // is the second layer of a pair; held back for the layer below, if it is the first of one
+    const bool first_of_pair = pairs && held < 0 && l > layer_lo && dw.hold_for_pair();
+    if (first_of_pair) {
+      held = l;
+    } else if (side) {
       (void)hipEventRecord(g_side.ready[l], c.st);
       (void)hipStreamWaitEvent(g_side.st, g_side.ready[l], 0);
       RC(dw.flush(g_side.st));
       (void)hipEventRecord(g_side.done[l], g_side.st);
+      if (held >= 0) (void)hipEventRecord(g_side.done[held], g_side.st);
+      held = -1;
       last_side = l;
     } else {
       RC(dw.flush(c.st));
+      held = -1;
     }
     dy = w.d_run;
   }

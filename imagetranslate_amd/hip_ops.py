@@ -2,6 +2,7 @@
 raw device pointers / sizes / the current HIP stream to ``libimt_hip.so`` and returns torch tensors that own
 the outputs.  PyTorch supplies memory and streams only.
 """
+import contextlib
 import ctypes
 import os
 import math
@@ -127,12 +128,36 @@ def dw_split_k(rows: int, N: int, K: int, rows_per_split: int) -> int:
     return max(1, min(rows // rows_per_split, 512 // max(1, ((N + 127) // 128) * ((K + 127) // 128))))
 
 
-def gemm_grouped_tn(problems):
-    """problems: list of dicts(A=dy[K,M], B=x[K,N], out=fp32 grad [M,N], a_colsum=optional) -> one launch."""
+@contextlib.contextmanager
+def grouped_tall_min_tiles(min_tiles):
+    """Tests / tuning: while the block runs, groups (and layer pairs of a stack's backward) take 256 x 128 tiles from
+    ``min_tiles`` of them on, where every row count allows; 1 = always, 1 << 30 = never."""
+    prev = L.load().imt_set_gemm_grouped_tall_min_tiles(int(min_tiles))
+    try:
+        yield
+    finally:
+        L.load().imt_set_gemm_grouped_tall_min_tiles(prev)
+
+
+def gemm_grouped_tn(problems, tile_rows=0):
+    """problems: list of dicts(A=dy[K,M], B=x[K,N], out=fp32 grad [M,N], a_colsum=optional) -> one launch.
+    tile_rows (tests / tuning): 256 = the 256 x 128 instance whenever every row count allows it, 128 = never, 0 = the policy."""
     arr = (L.GemmArgs * len(problems))()
     for i, pr in enumerate(problems):
         arr[i] = gemm(pr["A"], pr["B"], IMT_TN, out=pr["out"], accumulate=True, a_colsum=pr.get("a_colsum"), _launch=False)
-    L.check(L.load().imt_gemm_grouped_tn(arr, len(problems), _stream()), "imt_gemm_grouped_tn")
+    with grouped_tall_min_tiles({128: 1 << 30, 256: 1}[tile_rows]) if tile_rows else contextlib.nullcontext():
+        L.check(L.load().imt_gemm_grouped_tn(arr, len(problems), _stream()), "imt_gemm_grouped_tn")
+
+
+def grouped_tile_order(grids, plain=False):
+    """Tile order of the grouped launch for a group whose problems have ``grids[i] = (tile rows, tile columns)``: a list
+    with (problem, tile row, tile column) of every hardware workgroup (workgroup w runs on XCD w % 8).  Host only."""
+    n = len(grids)
+    total = sum(r * c for r, c in grids)
+    rows, cols = (ctypes.c_int * n)(*[g[0] for g in grids]), (ctypes.c_int * n)(*[g[1] for g in grids])
+    order = (ctypes.c_int * (3 * total))()
+    L.check(L.load().imt_gemm_grouped_tile_order(rows, cols, n, int(plain), order, total), "imt_gemm_grouped_tile_order")
+    return [(order[3 * w], order[3 * w + 1], order[3 * w + 2]) for w in range(total)]
 
 
 def gemm_bias_residual_ln(x, w, bias, resid, gamma, beta, eps=1e-12, dropout_p=0.0, dropout_seed=0, want_pre_ln=True):

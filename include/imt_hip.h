@@ -138,8 +138,15 @@ typedef struct imt_gemm_args {
 int64_t imt_gemm_splitk_ws_bytes(void);
 int imt_gemm(const imt_gemm_args* a, void* stream);
 /* All weight-gradient GEMMs (IMT_TN, fp32 C += alpha * A^T B, optional a_colsum) of one transformer layer in ONE
- * launch (HOST array of `count` descriptors).  Problems that cannot be grouped fall back to imt_gemm each. */
+ * launch (HOST array of `count` descriptors), or of two layers (up to 16 problems).  128 x 128 output tiles; 256 x 128 when
+ * every M is a multiple of 256 and those tiles still give three quarters of the CUs one each (same bits either way: one
+ * writer per tile, the whole K in ascending order).  Problems that cannot be grouped fall back to imt_gemm each. */
 int imt_gemm_grouped_tn(const imt_gemm_args* list, int count, void* stream);
+/* The tile order of that launch, evaluated on the host (no GPU needed): for a group of `count` (1..16) problems with
+ * tile_rows[i] x tile_cols[i] output tiles, order[3w .. 3w+2] = {problem, tile row, tile column} of hardware workgroup w,
+ * w < order_tiles == the group's tile count (at most 640).  Workgroup w runs on XCD w % 8.  plain != 0: the order under
+ * IMT_GROUPED_PLAIN_ORDER. */
+int imt_gemm_grouped_tile_order(const int* tile_rows, const int* tile_cols, int count, int plain, int* order, int order_tiles);
 
 /* Dense + bias + dropout + residual + LayerNorm in ONE launch -- HF BertSelfOutput / BertOutput as instantiated by
  * src/bert_seq2seq.py:84-90,139-143: out = LayerNorm(dropout(x W^T + bias) + resid; eps), row-complete 32 x N tiles
@@ -401,6 +408,10 @@ int imt_comm_destroy(void* comm);
  * as soon as a collective's resident kernels hold a few CUs.  Returns the previous setting.
  * The environment variable IMT_GEMM_SHARE_CUS (0 / 1), when set, overrides this call. */
 int imt_set_gemm_share_cus(int share_cus);
+/* Tests / tuning: the fewest 256 x 128 tiles with which imt_gemm_grouped_tn takes them (and the stack's backward launches
+ * the weight gradients of two layers at once) where every row count allows; 0 = the default, three quarters of the CUs.
+ * Returns the previous setting. */
+int imt_set_gemm_grouped_tall_min_tiles(int min_tiles);
 
 /* ------------------------------------------------------------------ optimizer
  * (clip_grad_norm_ train_image_mt.py:291 ; AdamInverseSqrtWithWarmup src/utils.py:105-156)
