@@ -52,6 +52,16 @@ template <typename T, bool KCONTIG> struct Stage : TileGeom<T, KCONTIG> {
       else         { grow = k0 + tr;   gcol = row0 + c * G::EPC; ok = (grow < K) && (gcol < nrows); }
       u32x4 v = {0u, 0u, 0u, 0u};
       if (ok) v = *reinterpret_cast<const u32x4*>(base + grow * ld + gcol);
+      // K that is not a whole number of chunks (the K-contiguous A of NN over a vocabulary of 193 entries): the last chunk of a
+      // row brings in the row's pad elements, which meet the zero-filled rows of the other operand -- and NaN * 0 is NaN.  The
+      // elements at or past K become zeros here; K is uniform over the kernel, so whole-chunk K pays one scalar branch.
+      if (KCONTIG && (K % G::EPC) != 0) {
+        const int left = (K - (int)gcol) * (int)sizeof(T);  // bytes of this chunk in front of K
+        if (ok && left < 16) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) v[w] = (left >= 4 * w + 4) ? v[w] : (left <= 4 * w) ? 0u : (v[w] & 0xffffu);
+        }
+      }
       r[i] = v;
     }
   }
@@ -1219,7 +1229,12 @@ GemmFacts gemm_facts(const imt_gemm_args* a) {
   f.pipe_ok = (a->K % f.bk == 0 || tn) && (a->K / f.bk >= 2) && ((int64_t)a_rows * a->lda * f.es < (1ll << 31)) &&
               ((int64_t)b_rows * a->ldb * f.es < (1ll << 31));
   f.tiles = (int64_t)imt_cdiv(a->M, BM) * imt_cdiv(a->N, BN); f.tiles256 = (int64_t)imt_cdiv(a->M, 256) * imt_cdiv(a->N, 256);
-  f.a_bytes = view_bytes(a_rows, a->lda, tn ? a->M : a->K, f.es); f.b_bytes = view_bytes(b_rows, a->ldb, nt ? a->K : a->N, f.es);
+  // The descriptors' range ends on a whole 16-byte chunk: the range check works on dwords, so a bf16 view whose last row ends on
+  // an odd element (N = 133, a vocabulary of 193 entries as the M of a weight gradient) would lose that element -- it shares its
+  // dword with the first one past the view.  imt_gemm's extent rule keeps the rounded-up last chunk inside the row's storage,
+  // and what it brings in beside the view belongs to output rows / columns past M / N, which the epilogue masks.
+  const auto chunks = [&f](int inner) { return (inner + f.al - 1) / f.al * f.al; };
+  f.a_bytes = view_bytes(a_rows, a->lda, chunks(tn ? a->M : a->K), f.es); f.b_bytes = view_bytes(b_rows, a->ldb, chunks(nt ? a->K : a->N), f.es);
   return f;
 }
 
@@ -1635,9 +1650,9 @@ extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
   const int a_inner = (a->layout == IMT_TN) ? a->M : a->K, b_inner = (a->layout == IMT_NT) ? a->K : a->N;
   // A contiguous extent that is not a whole number of 16-byte chunks (a vocabulary of 193 entries ...) is accepted when
   // the leading dimension covers the rounded-up extent (the last chunk of a row then stays inside the row's storage)
-  // and what the overhang reads cannot reach the result: output rows/columns past M/N are masked by the epilogue, and
-  // the K overhang of the K-contiguous A of NN meets zero-filled B rows.  Both operands of NT share the K overhang,
-  // so NT keeps the strict rule.
+  // and what the overhang reads cannot reach the result, whatever the pad holds (NaN included): output rows/columns past
+  // M/N are masked by the epilogue, and the K overhang of the K-contiguous A of NN is zeroed as it is staged (Stage::load;
+  // the B rows it would meet are zero-filled too).  Both operands of NT share the K overhang, so NT keeps the strict rule.
   const auto extent_ok = [al](int inner, int64_t ld, bool strict) {
     return inner % al == 0 || (!strict && ld >= (int64_t)((inner + al - 1) / al) * al);
   };

@@ -78,6 +78,10 @@ int imt_prof_report(imt_prof_row* rows, int max_kinds);
  *   accumulate: v += C[m,n]
  *   store as c_dtype (T or IMT_F32).  split_k > 1: fp32 atomicAdd of the raw partial products into C
  *   (c_dtype must be IMT_F32; no other epilogue; C pre-initialised by the caller).
+ * Views: every matrix is a view with its own leading dimension (lda / ldb multiples of a 16-byte chunk, ldc a multiple of 4);
+ * a contiguous extent of A or B that is not a whole number of chunks (NN / TN only) needs a leading dimension that covers
+ * the rounded-up extent.  Results do not depend on memory outside the views: pad elements may hold anything, NaN included,
+ * and nothing outside the views of C, aux (IMT_AUX_GELU_FWD) and a_colsum is written.
  */
 #define IMT_NT 0
 #define IMT_NN 1
