@@ -15,7 +15,7 @@ void imt_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int imt_version(void) { return 100; }
+extern "C" int imt_version(void) { return 101; }  // 101: imt_gemm_args lost its three reserved fields
 extern "C" const char* imt_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------------ profiler

@@ -8,7 +8,7 @@
 // (mfma(Bfrag, Afrag)) so each lane owns 4 consecutive n of one m: bias / residual / aux accesses and the C
 // store are 8- or 16-byte vectors.
 //
-// Five main loops share the tile product (compute_tile) and the LDS-restaged epilogue.  imt_gemm (host side, at the end of the
+// Four main loops share the tile product (compute_tile) and the LDS-restaged epilogue.  imt_gemm (host side, at the end of the
 // file) validates, then picks a strategy -- ragged-K tail + whole-tile body, split-K slabs on the persistent kernel (splitk_ws) or
 // on the 256-tile kernel (IMT_AUX_SPLITK_WS), else one launch whose loop choose_variant picks from measurements
 // (profiles/r01_v5_gemm_shapes.txt, profiles/r01_gemm_epilogue_study.txt, profiles/r01_gemm_xl_study.txt):
@@ -21,9 +21,10 @@
 //                            tiles and K >= 2048, and the IMT_AUX_SPLITK_WS slabs.
 //   gemm_grouped_tn_kernel : the wave-specialised split for ALL weight-gradient products of a layer in one launch (full K per
 //                            tile, fp32 accumulate, fused bias gradients): imt_gemm_grouped_tn.
-//   gemm_sb_kernel         : one 32-KiB LDS buffer + register prefetch, three workgroups per CU overlap each other's
-//                            barriers and epilogues: many short-K tiles, and whatever the LDS-DMA loops cannot run (NT / NN).
-//   gemm_kernel            : register-staged double buffer with predicated (zero-filling) loads: what gemm_sb_kernel takes, for TN.
+//   gemm_reg_kernel        : register-staged with predicated (zero-filling) loads, in two instances.  NBUF = 1: one 32-KiB LDS
+//                            buffer + register prefetch, three workgroups per CU overlap each other's barriers and epilogues:
+//                            many short-K tiles, and whatever the LDS-DMA loops cannot run (NT / NN).  NBUF = 2: double
+//                            buffer, one barrier per K tile: the same, for TN.
 #include <stdlib.h>
 #include "mma.hpp"
 #include "gemm_xl.hpp"
@@ -126,7 +127,7 @@ struct EpiParams {
   float alpha; const float* alpha_dev;
   float inv_keep; uint32_t drop_thresh; uint64_t seed;
   float* a_colsum;  // TN only: a_colsum[m] += alpha * sum_k A[k][m]   (bias gradient fused into the dW GEMM)
-  int dbg;          // tuning only (tools/gemm_shapes.py): bit0 skip the tile products, bit1 skip the in-loop DMA
+  int dbg;          // 256-tile K loop only (IMT_GEMM_DBG, xl_k_loop): bit0 skip the tile products, bit1 skip the in-loop DMA, bit6 all waves issue first
   unsigned long long* trace;  // tuning only (IMT_TRACE=gemm_ws | gemm_xl): per-workgroup phase time stamps
   int64_t slab_elems;         // split-K slab mode: C of K split y = C + y * slab_elems (fp32 slabs)
   int splits = 1;             // persistent kernel, split-K slab mode: K ranges per output tile (imt_gemm_args.splitk_ws)
@@ -287,7 +288,7 @@ IMT_DEVICE int epi_off(int row, int c4) { return row * 512 + ((c4 ^ (row & 31)) 
 // CODE SIZE is a first-order cost here: the group loop is unrolled (4-8 bodies per pass), and a body that branches over
 // every option at run time (GELU, GELU', dropout, residual, fp32 / accumulate, ragged-N scalar tail) is > 1000
 // instructions of which a launch executes a few dozen -- the wave then takes an instruction-cache miss at every
-// skipped block (measured with IMT_GEMM_TRACE on the 256-tile kernel: 12-18 us per tile for what is 3 us of work).
+// skipped block (measured with IMT_TRACE=gemm_xl on the 256-tile kernel: 12-18 us per tile for what is 3 us of work).
 // So the epilogue KIND is resolved once per tile (uniform) into a straight-line template instance for the kinds the
 // train step uses on full tiles; everything else (edge tiles, split-K atomics, rare combinations) runs ONE rolled,
 // fully general body.
@@ -475,7 +476,7 @@ template <typename T, int NTHR = NTHREADS, bool HAS_ACC = true, int WROWS = 64>
 IMT_DEVICE void epilogue(const f32x4 (*acc)[4], char* smem, int m0, int n0, int wm, int wn, int M, int N, const EpiParams& ep,
                          float alpha) {
   const int kind = (n0 + BN <= N) ? epi_kind(ep) : EM_GENERIC;  // uniform over the workgroup
-  if (kind == EM_GENERIC || ((ep.dbg & 16) && m0 + BM > M)) epilogue_general<T, NTHR, HAS_ACC, WROWS>(acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
+  if (kind == EM_GENERIC) epilogue_general<T, NTHR, HAS_ACC, WROWS>(acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
   else if (m0 + BM <= M)  epilogue_fast_kinds<T, NTHR, HAS_ACC, WROWS, false>(kind, acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
   else                    epilogue_fast_kinds<T, NTHR, HAS_ACC, WROWS, true>(kind, acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
 }
@@ -489,10 +490,18 @@ IMT_DEVICE void tile_origin(int M, int N, int& m0, int& n0) {
   n0 = (bid % nbx) * BN;
 }
 
-// ------------------------------------------------------------------------------------------------ general kernel
-template <typename T, int LAYOUT>
-__global__ __launch_bounds__(NTHREADS) void gemm_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__ B,
-                                                        int64_t ldb, int M, int N, int K, int k_per_split, EpiParams ep) {
+// ------------------------------------------------------------------------------------------------ register-staged kernel
+// Operand tiles go global -> registers (predicated, zero-filling loads: any shape) -> LDS, the loads of K tile t + 1 in flight
+// under the products of tile t.  Two K loops around one prologue and epilogue:
+//   NBUF = 2 (V_DBUF): double buffer -- tile t + 1 is stored behind the products of tile t, one barrier per K tile.
+//   NBUF = 1 (V_SBUF): a single 32-KiB buffer -- two barriers per K tile, but three workgroups (12 waves) per CU, i.e. three
+//                      tiles of loads in flight per CU and other blocks' MFMAs to fill every barrier / latency bubble.
+// (a second launch bound of 0 is none at all: the double-buffer instance keeps the compiler's default occupancy target)
+template <typename T, int LAYOUT, int NBUF>
+__global__ __launch_bounds__(NTHREADS, NBUF == 1 ? 3 : 0) void gemm_reg_kernel(const T* __restrict__ A, int64_t lda,
+                                                                               const T* __restrict__ B, int64_t ldb, int M, int N,
+                                                                               int K, int k_per_split, EpiParams ep) {
+  static_assert(NBUF == 1 || NBUF == 2, "one LDS buffer or two");
   constexpr bool A_KC = (LAYOUT != IMT_TN), B_KC = (LAYOUT == IMT_NT);
   typedef Stage<T, A_KC> SA;
   typedef Stage<T, B_KC> SB;
@@ -520,72 +529,41 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const T* __restrict__ A,
   if (nt > 0) {
     sa.load(A, lda, m0, M, kbeg, kend);
     sb.load(B, ldb, n0, N, kbeg, kend);
-    sa.store(smem);
-    sb.store(smem + TILE_BYTES);
   }
-  __syncthreads();
-  for (int t = 0; t < nt; ++t) {
-    const int cur = t & 1;
+  const auto load_next = [&](int t) {
     if (t + 1 < nt) {
       sa.load(A, lda, m0, M, kbeg + (t + 1) * BK, kend);
       sb.load(B, ldb, n0, N, kbeg + (t + 1) * BK, kend);
     }
-    const char* ta = smem + cur * STAGE_BYTES;
-    compute_tile<T, LAYOUT>(acc, ta, ta + TILE_BYTES, wm, wn);
-    if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(ta);
-    if (t + 1 < nt) {
-      sa.store(smem + (cur ^ 1) * STAGE_BYTES);
-      sb.store(smem + (cur ^ 1) * STAGE_BYTES + TILE_BYTES);
+  };
+  if constexpr (NBUF == 2) {
+    if (nt > 0) {
+      sa.store(smem);
+      sb.store(smem + TILE_BYTES);
     }
     __syncthreads();
-  }
-  const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
-  epilogue<T>(acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
-  if (LAYOUT == IMT_TN && do_colsum) cs.flush(smem, ep.a_colsum, m0, M, alpha);
-}
-
-// ------------------------------------------------------------------------------------------------ high-occupancy kernel
-// Single 32-KiB LDS buffer + register prefetch: two barriers per K tile, but three workgroups (12 waves) per CU,
-// i.e. three tiles of loads in flight per CU and other blocks' MFMAs to fill every barrier / latency bubble.
-template <typename T, int LAYOUT>
-__global__ __launch_bounds__(NTHREADS, 3) void gemm_sb_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__ B,
-                                                              int64_t ldb, int M, int N, int K, int k_per_split, EpiParams ep) {
-  constexpr bool A_KC = (LAYOUT != IMT_TN), B_KC = (LAYOUT == IMT_NT);
-  typedef Stage<T, A_KC> SA;
-  typedef Stage<T, B_KC> SB;
-  constexpr int BK = SA::BK;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int m0, n0;
-  tile_origin(M, N, m0, n0);
-  const int kbeg = blockIdx.y * k_per_split;
-  const int kend = min(K, kbeg + k_per_split);
-  const int wave = threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  ColSum<T> cs;
-  cs.clear();
-  const bool do_colsum = (LAYOUT == IMT_TN) && ep.a_colsum && n0 == 0;
-  SA sa; SB sb;
-  const int nt = (kend - kbeg + BK - 1) / BK;
-  if (nt > 0) {
-    sa.load(A, lda, m0, M, kbeg, kend);
-    sb.load(B, ldb, n0, N, kbeg, kend);
-  }
-  for (int t = 0; t < nt; ++t) {
-    sa.store(smem);
-    sb.store(smem + TILE_BYTES);
-    __syncthreads();
-    if (t + 1 < nt) {
-      sa.load(A, lda, m0, M, kbeg + (t + 1) * BK, kend);
-      sb.load(B, ldb, n0, N, kbeg + (t + 1) * BK, kend);
+    for (int t = 0; t < nt; ++t) {
+      const int cur = t & 1;
+      load_next(t);
+      const char* ta = smem + cur * STAGE_BYTES;
+      compute_tile<T, LAYOUT>(acc, ta, ta + TILE_BYTES, wm, wn);
+      if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(ta);
+      if (t + 1 < nt) {
+        sa.store(smem + (cur ^ 1) * STAGE_BYTES);
+        sb.store(smem + (cur ^ 1) * STAGE_BYTES + TILE_BYTES);
+      }
+      __syncthreads();
     }
-    compute_tile<T, LAYOUT>(acc, smem, smem + TILE_BYTES, wm, wn);
-    if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(smem);
-    __syncthreads();
+  } else {
+    for (int t = 0; t < nt; ++t) {
+      sa.store(smem);
+      sb.store(smem + TILE_BYTES);
+      __syncthreads();
+      load_next(t);
+      compute_tile<T, LAYOUT>(acc, smem, smem + TILE_BYTES, wm, wn);
+      if (LAYOUT == IMT_TN && do_colsum) cs.add_tile(smem);
+      __syncthreads();
+    }
   }
   const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
   epilogue<T>(acc, smem, m0, n0, wm, wn, M, N, ep, alpha);
@@ -736,7 +714,7 @@ __global__ __launch_bounds__(WS_THREADS) void gemm_ws_kernel(const T* __restrict
 // instruction, a full 128-B line per row over j = 0..3.  No LDS pass, no barrier, and NO run-time branch: the epilogue
 // kind is a template parameter, because 32 unrolled copies of a body that branches over every option (GELU, GELU',
 // dropout, residual, ...) are ~250 KB of code that a wave walks once, taking an instruction-cache miss at every skipped
-// block -- measured 12-18 us per tile (IMT_GEMM_TRACE), more than the whole K loop.  Kinds outside the table below and
+// block -- measured 12-18 us per tile (IMT_TRACE=gemm_xl), more than the whole K loop.  Kinds outside the table below and
 // ragged edge tiles take the restaged path.
 template <typename T, int AUX, bool C_F32, bool RAGGED_M>
 IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], const XlWave w, int m0, int n0, int M, const EpiParams& ep, float alpha) {
@@ -774,9 +752,8 @@ IMT_DEVICE void epilogue_xl_direct(const f32x4 (&acc)[8][4], const XlWave w, int
         const f32x4 z = Vec4<T>::cvt(zr[i & 1][j]);
         v *= gelu_erf_grad4(z);
       }
-      if (live && !(ep.dbg & 128)) {  // dbg bit 7 (tuning only): no output stores -- what the stores and their write-back cost
+      if (live) {
         if (C_F32) Vec4<float>::store(reinterpret_cast<float*>(ep.C) + m * ep.ldc + n, v);
-        else if (ep.dbg & 256) Vec4<T>::store_wt(reinterpret_cast<T*>(ep.C) + m * ep.ldc + n, v);  // bit 8: write-through stores
         else       Vec4<T>::store(reinterpret_cast<T*>(ep.C) + m * ep.ldc + n, v);
       }
     }
@@ -822,7 +799,7 @@ __global__ __launch_bounds__(XL_THREADS) void gemm_xl_kernel(const T* __restrict
   });
   const float alpha = ep.alpha_dev ? ep.alpha * ep.alpha_dev[0] : ep.alpha;
   IMT_STAMP(ep.trace, 2);
-  if (n0 + 256 <= N && !ep.atomic && !ep.accumulate && !ep.resid && !ep.drop_thresh && !(ep.dbg & 8)) {
+  if (n0 + 256 <= N && !ep.atomic && !ep.accumulate && !ep.resid && !ep.drop_thresh) {
     bool done = true;
     const bool rag = m0 + 256 > M;
     if (ep.aux_mode == IMT_AUX_NONE && !ep.c_f32) {
@@ -871,6 +848,13 @@ struct GroupProblem {
 struct GroupGrid { int rows, cols, tile_start; };  // tile grid of one problem; its tiles are tile_start .. of the group's list
 struct GroupTile { int problem, row, col; };
 struct GroupArgs { int count; int total_tiles; float alpha; int plain_order /* tuning: 1 = plain workgroup order */; GroupGrid grid[MAX_GROUP]; GroupProblem p[MAX_GROUP]; };
+// the epilogue of every grouped tile: fp32 C += alpha * product, nothing else
+IMT_DEVICE EpiParams grouped_epi_params(const GroupProblem& P, float alpha) {
+  EpiParams ep{};
+  ep.C = P.C; ep.ldc = P.ldc; ep.c_f32 = 1; ep.accumulate = 1;
+  ep.aux_mode = IMT_AUX_NONE; ep.alpha = alpha; ep.inv_keep = 1.f; ep.a_colsum = P.a_colsum;
+  return ep;
+}
 
 // Hardware workgroup id -> output tile, for the kernel and for imt_gemm_grouped_tile_order.  Workgroup w runs on XCD w % 8;
 // XCD x takes the x-th of eight CONTIGUOUS runs of the group's tile list (row-major per problem; imt_xcd_block's split: the
@@ -1095,11 +1079,7 @@ IMT_DEVICE void grouped_tall_tile(const GroupArgs& g, const GroupProblem& P, int
     else if (wn == 0) grouped_consumer_loop_tall<T, true, true>(acc, bacc, smem, ns, wmi, wn);
     else              grouped_consumer_loop_tall<T, true, false>(acc, bacc, smem, ns, wmi, wn);
   }
-  EpiParams ep;
-  ep.C = P.C; ep.ldc = P.ldc; ep.c_f32 = 1; ep.accumulate = 1;
-  ep.bias = nullptr; ep.resid = nullptr; ep.ldr = 0; ep.aux = nullptr; ep.ldaux = 0; ep.aux_mode = IMT_AUX_NONE;
-  ep.atomic = 0; ep.alpha = g.alpha; ep.alpha_dev = nullptr; ep.inv_keep = 1.f; ep.drop_thresh = 0; ep.seed = 0;
-  ep.a_colsum = P.a_colsum; ep.dbg = 0; ep.trace = nullptr;
+  const EpiParams ep = grouped_epi_params(P, g.alpha);
   // two 128-row halves through the restaged epilogue, all 8 waves each (the ring is free: every DMA has landed and been read)
 #pragma unroll 1
   for (int q = 0; q < 2; ++q) {
@@ -1120,15 +1100,14 @@ template <typename T, int TM>
 __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArgs g) {
   constexpr int BK = TileGeom<T, false>::BK;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if constexpr (TM == 256) {
-    const GroupTile tile = grouped_tile(blockIdx.x, g.total_tiles, g.count, g.grid, g.plain_order != 0);
-    grouped_tall_tile<T>(g, g.p[tile.problem], tile.row * 256, tile.col * BN, smem);
-    return;
-  }
   // XCD-affine tile order (grouped_tile).  With the plain order every XCD saw one column and ~24 different rows: 549 MB of
   // fabric traffic per launch against 160 MB algorithmic, and the kernel ran at the fabric's ~6 TB/s.
   const GroupTile tile = grouped_tile(blockIdx.x, g.total_tiles, g.count, g.grid, g.plain_order != 0);
   const GroupProblem& P = g.p[tile.problem];
+  if constexpr (TM == 256) {
+    grouped_tall_tile<T>(g, P, tile.row * 256, tile.col * BN, smem);
+    return;
+  }
   const int M = P.M, N = P.N, K = P.K;
   const int m0 = tile.row * BM, n0 = tile.col * BN;
   const int nt = (K + BK - 1) / BK;  // a ragged last K tile (token counts are arbitrary) reads zeros past the operands' valid bytes
@@ -1173,11 +1152,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
     else if (wn == 0) grouped_consumer_loop<T, true, true>(acc, bacc, smem, nt, wm, wn);
     else              grouped_consumer_loop<T, true, false>(acc, bacc, smem, nt, wm, wn);
   }
-  EpiParams ep;
-  ep.C = P.C; ep.ldc = P.ldc; ep.c_f32 = 1; ep.accumulate = 1;
-  ep.bias = nullptr; ep.resid = nullptr; ep.ldr = 0; ep.aux = nullptr; ep.ldaux = 0; ep.aux_mode = IMT_AUX_NONE;
-  ep.atomic = 0; ep.alpha = g.alpha; ep.alpha_dev = nullptr; ep.inv_keep = 1.f; ep.drop_thresh = 0; ep.seed = 0;
-  ep.a_colsum = P.a_colsum; ep.dbg = 0; ep.trace = nullptr;
+  const EpiParams ep = grouped_epi_params(P, g.alpha);
   // one tile per workgroup: the epilogue is fully exposed, so all 8 waves share it (the producers have nothing left to do)
   if (consumer) epilogue<T, 512, true>(acc, smem, m0, n0, wm, wn, M, N, ep, g.alpha);
   else epilogue<T, 512, false>(acc, smem, m0, n0, wm, wn, M, N, ep, g.alpha);
@@ -1192,8 +1167,9 @@ __global__ __launch_bounds__(GROUP_THREADS) void gemm_grouped_tn_kernel(GroupArg
 // ------------------------------------------------------------------------------------------------ host side
 // (view_bytes and allow_lds: gemm_xl.hpp.  A refused LDS opt-in is left to the launch that follows to report.)
 
-// The main loops of imt_gemm, numbered as in imt_gemm_args.force_general (include/imt_hip.h): V_DBUF gemm_kernel, V_SBUF gemm_sb_kernel,
-// V_WS gemm_ws_kernel, V_XL gemm_xl_kernel (2 and 4 were the rings of the retired gemm_pipe_kernel; as codes they run V_DBUF)
+// The main loops of imt_gemm, numbered as in imt_gemm_args.force_general (include/imt_hip.h): V_DBUF gemm_reg_kernel<.., 2>, V_SBUF
+// gemm_reg_kernel<.., 1>, V_WS gemm_ws_kernel, V_XL gemm_xl_kernel (2 and 4 were the rings of the retired gemm_pipe_kernel; as codes
+// they run V_DBUF)
 enum Variant { V_DBUF = 1, V_SBUF = 3, V_WS = 5, V_XL = 6 };
 // profiler kind == one kernel symbol: gemm_<variant>_<dtype>_<layout>, so that rocprofv3's per-symbol averages can be compared
 // one to one.  Indexed [variant_row][bf16][layout].
@@ -1241,8 +1217,8 @@ GemmFacts gemm_facts(const imt_gemm_args* a) {
 template <typename T, int LAYOUT>
 int launch(const imt_gemm_args* a, const GemmFacts& f, EpiParams ep, int splits, int kps, Variant variant, hipStream_t st) {
   dim3 grid((unsigned)f.tiles, splits);
-  auto kern = gemm_kernel<T, LAYOUT>;
-  static const bool once = allow_lds(kern, 2 * STAGE_BYTES);
+  auto kdbuf = gemm_reg_kernel<T, LAYOUT, 2>;
+  static const bool once = allow_lds(kdbuf, 2 * STAGE_BYTES);
   const double es = sizeof(T), esc = ep.c_f32 ? 4.0 : es;
   const char* kind = VARIANT_KINDS[variant_row(variant)][sizeof(T) == 2][LAYOUT];
   if (imt_prof_enabled() && getenv("IMT_PROF_SHAPES")) kind = imt_prof_intern(kind, a->M, a->N, a->K);
@@ -1269,8 +1245,8 @@ int launch(const imt_gemm_args* a, const GemmFacts& f, EpiParams ep, int splits,
       if (tr.dev) fprintf(stderr, "[gemm_ws %s %dx%dx%d bias %d resid %d drop %d aux %d acc %d]\n", kind, a->M, a->N, a->K, ep.bias != nullptr, ep.resid != nullptr, ep.drop_thresh != 0, ep.aux_mode, ep.accumulate);
       break;
     }
-    case V_SBUF: hipLaunchKernelGGL((gemm_sb_kernel<T, LAYOUT>), grid, dim3(NTHREADS), STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
-    case V_DBUF: hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
+    case V_SBUF: hipLaunchKernelGGL((gemm_reg_kernel<T, LAYOUT, 1>), grid, dim3(NTHREADS), STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
+    case V_DBUF: hipLaunchKernelGGL(kdbuf, grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, A, a->lda, B, a->ldb, a->M, a->N, a->K, kps, ep); break;
   }
   IMT_CHECK_LAUNCH();
   return IMT_OK;
@@ -1419,30 +1395,21 @@ int launch_splitk_epilogue_ln(const float* slabs, int64_t slab_elems, int S, int
 }
 
 // Every environment switch this file reads, parsed once on first use (IMT_PROF_SHAPES alone is read per launch, in launch<>).
-// All but IMT_GEMM_SHARE_CUS are tuning / test aids; the defaults are the measured choices.
 struct GemmSwitches {
-  int dbg;                   // IMT_GEMM_DBG=<bits> (atoi): or-ed into EpiParams.dbg of every single launch
-  bool no_xl;                // IMT_GEMM_NO_XL (presence): never choose the 256-tile kernel
-  bool no_xl_gelu;           // IMT_GEMM_NO_XL_GELU (presence): a GELU-forward epilogue alone does not choose it
-  bool no_xl_tn;             // IMT_GEMM_NO_XL_TN (presence): weight gradients do not choose it
-  bool no_small_splitk;      // IMT_GEMM_NO_SMALL_SPLITK (presence): imt_gemm_args.splitk_ws is never used
-  int splitk_ln_min_nt;      // IMT_GEMM_SPLITK_LN_MIN_NT=<K tiles> (atoi, default 8): shortest K split when the epilogue launch normalises
+  int dbg;                   // IMT_GEMM_DBG=<bits> (atoi): EpiParams.dbg of every single launch -- the 256-tile K loop's ablation bits, kept because
+                             // the loop measured 5 % slower on bf16 TN once its never-taken branches were gone
   int share_cus;             // IMT_GEMM_SHARE_CUS (atoi, an empty string means 1): overrides imt_set_gemm_share_cus; -1 when unset
-  bool grouped_plain_order;  // IMT_GROUPED_PLAIN_ORDER (presence): grouped weight gradients in plain workgroup order
+  bool grouped_plain_order;  // IMT_GROUPED_PLAIN_ORDER (presence): grouped weight gradients in plain workgroup order (test aid)
 };
 const GemmSwitches& gemm_switches() {
-  static const auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
-  static const auto has = [](const char* name) { return getenv(name) != nullptr; };
   static const auto share = [] { const char* v = getenv("IMT_GEMM_SHARE_CUS"); return !v ? -1 : (atoi(v) != 0 || v[0] == '\0') ? 1 : 0; };
-  static const GemmSwitches sw = {num("IMT_GEMM_DBG", 0), has("IMT_GEMM_NO_XL"), has("IMT_GEMM_NO_XL_GELU"), has("IMT_GEMM_NO_XL_TN"),
-                                  has("IMT_GEMM_NO_SMALL_SPLITK"), num("IMT_GEMM_SPLITK_LN_MIN_NT", 8),
-                                  share(), has("IMT_GROUPED_PLAIN_ORDER")};  // (in the order of the fields)
+  static const GemmSwitches sw = {getenv("IMT_GEMM_DBG") ? atoi(getenv("IMT_GEMM_DBG")) : 0, share(), getenv("IMT_GROUPED_PLAIN_ORDER") != nullptr};
   return sw;
 }
 
 int g_share_cus = 0;  // imt_set_gemm_share_cus
 // The epilogue that `a` asks for, as the kernels take it; every field not named here is zero.  Launches that differ
-// (atomic split-K, dbg, LayerNorm in the launch) override those fields.
+// (atomic split-K, LayerNorm in the launch) override those fields.
 EpiParams epi_params(const imt_gemm_args* a) {
   EpiParams ep{};
   ep.C = a->C; ep.ldc = a->ldc; ep.c_f32 = (a->c_dtype == IMT_F32); ep.accumulate = a->accumulate;
@@ -1481,11 +1448,12 @@ int layernorm_behind(const imt_gemm_args* a, void* stream) {
 }
 
 // how many K ranges for a product with `tiles` output tiles of 128 x 128 and `nt` K tiles; 1 = do not split
-int splitk_choice(int64_t tiles, int nt, bool ln_fused, const GemmSwitches& sw) {
+int splitk_choice(int64_t tiles, int nt, bool ln_fused) {
   // with the LayerNorm in the epilogue launch the split costs no extra launch (it replaces the LayerNorm's), so a
   // shorter K pays already when the product has only a handful of tiles (decoding: 320 rows)
-  const bool short_ok = ln_fused && tiles <= 32 && nt >= sw.splitk_ln_min_nt;
-  if (sw.no_small_splitk || tiles > 128 || (nt < 16 && !short_ok)) return 1;
+  constexpr int SPLITK_LN_MIN_NT = 8;  // shortest K, in tiles, that is split when the epilogue launch normalises
+  const bool short_ok = ln_fused && tiles <= 32 && nt >= SPLITK_LN_MIN_NT;
+  if (tiles > 128 || (nt < 16 && !short_ok)) return 1;
   int s = (int)(256 / tiles);
   if (s > 8) s = 8;
   const int per_min = (nt < 16) ? 2 : 4;  // K tiles per range: below that the ramp of a range costs more than it saves
@@ -1556,9 +1524,9 @@ int run_slabs(const imt_gemm_args* a, const GemmFacts& f, void* stream) {
 // normalises its rows itself
 bool splitk_ws_ln_fused(const imt_gemm_args* a) { return a->ln_out && a->aux_mode == IMT_AUX_NONE && a->N <= 1024 && a->c_dtype != IMT_F32; }
 // the number of K ranges; 1 = the strategy does not apply
-int splitk_ws_splits(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits) {
+int splitk_ws_splits(const imt_gemm_args* a, const GemmFacts& f, int splits) {
   if (a->force_general != 0 || !a->splitk_ws || splits != 1 || a->layout == IMT_TN || !f.pipe_ok || a->N % 4 != 0 || a->a_colsum) return 1;
-  const int S = splitk_choice(f.tiles, a->K / f.bk, splitk_ws_ln_fused(a), sw);
+  const int S = splitk_choice(f.tiles, a->K / f.bk, splitk_ws_ln_fused(a));
   // (edge tiles store only rows < M, slabs are addressed [m][n] with ld N)
   return ((int64_t)S * a->M * a->N * 4 <= a->splitk_ws_bytes && ((uintptr_t)a->splitk_ws & 15) == 0) ? S : 1;
 }
@@ -1587,11 +1555,10 @@ int run_splitk_ws(const imt_gemm_args* a, const GemmFacts& f, int S, void* strea
 }
 
 // ---- strategy: one launch.  choose_variant: which main loop it runs (splits: atomic split-K ranges, 1 = none); no side effects, a
-// function of the product's facts, the arguments, the switches and the share-CUs knob.
-Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits, bool share_cus) {
+// function of the product's facts, the arguments and the share-CUs knob.
+Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, int splits, bool share_cus) {
   const bool tn = a->layout == IMT_TN;
-  // a->force_general carries a variant code for tests / tuning (and dbg bits in its hundreds)
-  int v = a->force_general % 100;
+  int v = a->force_general;  // a variant code for tests / tuning, 0..6 (imt_gemm checks)
   if (v == 0) {
     // measured on MI355X (profiles/r01_v3_gemm_shapes.txt): about one wave of blocks -> the LDS-DMA ring (its long
     // steady state wins when K >= 1024, a tie otherwise); larger grids -> three single-buffer blocks per CU.
@@ -1604,11 +1571,11 @@ Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, const GemmSwi
     else v = tn ? V_DBUF : V_SBUF;
     // 256 x 256 tiles (profiles/r01_gemm_xl_study.txt): several rounds of short-K tiles (vocabulary projection 797 vs 681
     // TFLOP/s, batched cross K/V), or one round whose epilogue touches a second matrix (GELU / GELU' / residual: 500 vs 430)
-    const bool second_matrix = (a->aux_mode != IMT_AUX_NONE && !(a->aux_mode == IMT_AUX_GELU_FWD && sw.no_xl_gelu)) || a->resid;
-    if (!sw.no_xl && f.pipe_ok && splits == 1 && !tn && !a->a_colsum && a->K < 1024 && (f.tiles256 >= 512 || (f.tiles256 >= 224 && second_matrix)))
+    const bool second_matrix = a->aux_mode != IMT_AUX_NONE || a->resid;
+    if (f.pipe_ok && splits == 1 && !tn && !a->a_colsum && a->K < 1024 && (f.tiles256 >= 512 || (f.tiles256 >= 224 && second_matrix)))
       v = V_XL;
     // a weight gradient with about one 256-tile per CU and a long K (the vocabulary projection's dW: 30000 x 512 x 8128)
-    if (!sw.no_xl && !sw.no_xl_tn && f.pipe_ok && splits == 1 && tn && f.tiles256 >= 224 && f.tiles256 <= 256 && a->K >= 2048) v = V_XL;
+    if (f.pipe_ok && splits == 1 && tn && f.tiles256 >= 224 && f.tiles256 <= 256 && a->K >= 2048) v = V_XL;
     // data-parallel knob (off by default): when a collective's kernels hold some CUs, a persistent
     // launch of exactly one tile per CU needs a full second round; three small workgroups per CU degrade gracefully
     if (share_cus && v == V_WS && !tn && f.tiles > 192 && f.tiles <= 256 && a->K < 1024) v = V_SBUF;
@@ -1616,12 +1583,13 @@ Variant choose_variant(const imt_gemm_args* a, const GemmFacts& f, const GemmSwi
   // what a variant cannot run goes to its nearest relative that can
   if (v == V_XL && (!f.pipe_ok || splits > 1 || (a->a_colsum && !tn))) v = V_SBUF;
   if (v == V_WS && (!f.pipe_ok || splits > 1)) v = V_SBUF;
-  return (v == V_SBUF || v == V_WS || v == V_XL) ? (Variant)v : V_DBUF;  // (any other code has always meant the register-staged kernel)
+  return (v == V_SBUF || v == V_WS || v == V_XL) ? (Variant)v : V_DBUF;  // (1, and the retired 2 and 4)
 }
-int run_single(const imt_gemm_args* a, const GemmFacts& f, const GemmSwitches& sw, int splits, int kps, void* stream) {
-  const Variant variant = choose_variant(a, f, sw, splits, sw.share_cus >= 0 ? sw.share_cus != 0 : g_share_cus != 0);
+int run_single(const imt_gemm_args* a, const GemmFacts& f, int splits, int kps, void* stream) {
+  const GemmSwitches& sw = gemm_switches();
+  const Variant variant = choose_variant(a, f, splits, sw.share_cus >= 0 ? sw.share_cus != 0 : g_share_cus != 0);
   EpiParams ep = epi_params(a);
-  ep.atomic = (splits > 1); ep.dbg = a->force_general / 100 | sw.dbg;
+  ep.atomic = (splits > 1); ep.dbg = sw.dbg;
   int rc = check_ln_out(a, LN_SINGLE, splits, true);  // LayerNorm of the finished rows: a launch behind the GEMM
   if (rc == IMT_OK) rc = dispatch(a, f, ep, splits, kps, variant, reinterpret_cast<hipStream_t>(stream));
   return (rc == IMT_OK && a->ln_out) ? layernorm_behind(a, stream) : rc;
@@ -1640,6 +1608,7 @@ extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
   IMT_CHECK_ARG(a != nullptr, "imt_gemm: null args");
   IMT_CHECK_ARG(imt_ok_dtype(a->dtype), "imt_gemm: bad dtype %d", a->dtype);
   IMT_CHECK_ARG(a->M >= 0 && a->N >= 0 && a->K >= 0, "imt_gemm: negative dims");
+  IMT_CHECK_ARG(a->force_general >= 0 && a->force_general <= 6, "imt_gemm: force_general %d is not a variant code (0..6)", a->force_general);
   if (a->M == 0 || a->N == 0) return IMT_OK;
   IMT_CHECK_ARG(a->A && a->B && a->C, "imt_gemm: null operand");
   const GemmFacts f = gemm_facts(a);
@@ -1671,11 +1640,10 @@ extern "C" int imt_gemm(const imt_gemm_args* a, void* stream) {
     splits = imt_cdiv(a->K, kps);
   }
   if (a->aux_mode != IMT_AUX_NONE) IMT_CHECK_ARG(a->aux != nullptr, "imt_gemm: aux_mode needs aux");
-  const GemmSwitches& sw = gemm_switches();
   const bool linear_epilogue = a->aux_mode == IMT_AUX_NONE && a->dropout_p == 0.f && !a->a_colsum;
   if (a->force_general == 0 && splits == 1 && a->layout != IMT_TN && a->K % f.bk != 0 && a->K / f.bk >= 16 && linear_epilogue) return run_ragged_k(a, f, stream);
-  if (const int S = splitk_ws_splits(a, f, sw, splits); S > 1) return run_splitk_ws(a, f, S, stream);
-  return run_single(a, f, sw, splits, kps, stream);
+  if (const int S = splitk_ws_splits(a, f, splits); S > 1) return run_splitk_ws(a, f, S, stream);
+  return run_single(a, f, splits, kps, stream);
 }
 
 // Which instance a group takes -- a pure function of the problem list and the CU count: 256 x 128 tiles when every row count

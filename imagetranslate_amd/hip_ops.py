@@ -62,7 +62,7 @@ def _rowmajor(t):
 
 def gemm(A, B, layout, *, out=None, out_dtype=None, bias=None, resid=None, aux=None, aux_mode=IMT_AUX_NONE,
          accumulate=False, split_k=1, alpha=1.0, dropout_p=0.0, dropout_seed=0, alpha_dev=None, a_colsum=None,
-         force_general=False, force_pipeline=False, ln=None, splitk_ws=None, _launch=True):
+         force_general=False, ln=None, splitk_ws=None, _launch=True):
     """C = epilogue(op(A) op(B)); see include/imt_hip.h:imt_gemm.  ``splitk_ws``: fp32 scratch (``splitk_workspace(device)``)
     that lets a product with few output tiles and a long K run as K ranges + one epilogue launch."""
     _req_cuda(A, B, out, bias, resid, aux)
@@ -91,13 +91,11 @@ def gemm(A, B, layout, *, out=None, out_dtype=None, bias=None, resid=None, aux=N
     a.alpha_dev = alpha_dev.data_ptr() if alpha_dev is not None else None
     a.a_colsum = a_colsum.data_ptr() if a_colsum is not None else None
     a.force_general = int(force_general)
-    a.force_pipeline = int(force_pipeline)
     if splitk_ws is not None:
         _req_cuda(splitk_ws)
         a.splitk_ws, a.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel() * splitk_ws.element_size()
     if ln is not None:
-        # ln = dict(gamma, beta, out, mean, rstd, eps): LayerNorm of the rows of `out` in the same call (a "tickets" entry
-        # is accepted and ignored: imt_gemm_args.ln_tickets is reserved)
+        # ln = dict(gamma, beta, out, mean, rstd, eps): LayerNorm of the rows of `out` in the same call
         _req_cuda(ln["gamma"], ln["beta"], ln["out"], ln["mean"], ln["rstd"])
         a.ln_gamma, a.ln_beta = ln["gamma"].data_ptr(), ln["beta"].data_ptr()
         a.ln_out, a.ld_ln = ln["out"].data_ptr(), _rowmajor(ln["out"])

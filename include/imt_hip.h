@@ -116,20 +116,18 @@ typedef struct imt_gemm_args {
   int32_t force_general;  /* tests / tuning: kernel variant, 0 = auto, 1 = register-staged double buffer (2 blocks/CU),
                              2 / 4: retired, run as 1, 3 = single LDS buffer + register prefetch (3 blocks/CU),
                              5 = persistent wave-specialised (LDS-DMA producer waves, K a whole number of tiles),
-                             6 = 256 x 256 tiles (NT / NN, K a whole number of tiles) */
-  int32_t force_pipeline; /* reserved */
+                             6 = 256 x 256 tiles (NT / NN, K a whole number of tiles); any other value is refused
+                             (IMT_ERR_BAD_ARG) */
   /* LayerNorm of the finished rows of C, in the same call (HF BertSelfOutput / BertOutput, src/bert_seq2seq.py:84-90,
    * 139-143: LayerNorm(dropout(dense(x)) + input) with the bias / dropout / residual epilogue above).  ln_out != NULL:
    * ln_out[M,N] (ld_ln, type c_dtype) = LayerNorm(C rows; ln_gamma, ln_beta, ln_eps), ln_mean / ln_rstd fp32 [M] (what
    * imt_layernorm_bwd takes).  C still receives the LayerNorm INPUT.  imt_layernorm_fwd runs behind the GEMM (C and ln_out
-   * contiguous), or the split-K epilogue launch (splitk_ws below) normalises its rows itself.  ln_tickets is reserved and
-   * ignored (it keeps the layout of the struct). */
+   * contiguous), or the split-K epilogue launch (splitk_ws below) normalises its rows itself.  (Three reserved
+   * fields of the retired ring GEMM and ticket LayerNorm left this struct with library version 101.) */
   const void* ln_gamma; const void* ln_beta;
   void* ln_out; int64_t ld_ln;
   float* ln_mean; float* ln_rstd;
-  int32_t* ln_tickets;
   float ln_eps;
-  int32_t reserved_ln;
   /* Few output tiles and a long K (the reference's inference and captioning callers: src/seq_gen.py:164-194 decodes
    * batch x beam = 320 rows per step, src/train_captioning.py:51-72 trains on 32 x 31 caption tokens; 128-row tiles then
    * occupy 12-52 of the 256 CUs and each walks the whole K alone).  With a caller-owned fp32 workspace here, imt_gemm may run

@@ -75,6 +75,20 @@ def test_gemm_argument_checks(lib):
     assert lib.imt_gemm_grouped_tn(ctypes.byref(z), 0, None) == 0
 
 
+def test_gemm_variant_code_outside_0_to_6_is_refused(lib):
+    """imt_gemm_args.force_general is a variant code 0..6 and nothing else: any other value (106 once carried tuning bits
+    in its hundreds) is a bad argument before any launch, for a well-formed product and for an empty one."""
+    a = L.GemmArgs()
+    a.dtype, a.M, a.N, a.K = 1, 8, 8, 8
+    a.A, a.B, a.C = 0x1000, 0x2000, 0x3000
+    a.lda, a.ldb, a.ldc, a.c_dtype = 8, 8, 8, 1
+    for code in (7, 106, -1):
+        a.force_general, a.M = code, 8
+        assert lib.imt_gemm(ctypes.byref(a), None) == ERR and b"force_general" in lib.imt_last_error(), code
+        a.M = 0
+        assert lib.imt_gemm(ctypes.byref(a), None) == ERR and b"force_general" in lib.imt_last_error(), code
+
+
 def test_stack_descriptor_checks(lib):
     s, io = _stack(), _io()
     assert lib.imt_stack_forward(None, ctypes.byref(io), None, 0, None) == ERR

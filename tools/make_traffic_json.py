@@ -5,13 +5,16 @@ import json, re, sys
 
 raw = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc_traffic.json"))
 ROUND = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-VAR = {"gemm_kernel": "dbuf", "gemm_sb_kernel": "sbuf", "gemm_ws_kernel": "ws", "gemm_xl_kernel": "xl"}
+VAR = {"gemm_kernel": "dbuf", "gemm_sb_kernel": "sbuf", "gemm_ws_kernel": "ws", "gemm_xl_kernel": "xl"}  # (the first two: traces taken before gemm_reg_kernel)
 LAY = {"0": "nt", "1": "nn", "2": "tn"}
 OTHER = [("gemm_grouped_tn_kernel", "gemm_bf16_tn_grouped"), ("attn_bwd_fused_kernel", "attn_bwd_fused_bf16"), ("attn_fwd_kernel", "attn_fwd_bf16"), ("attn_fwd_short_kernel", "attn_fwd_bf16"),
          ("ln_bwd_kernel", "layernorm_bwd"), ("ln_fwd_kernel", "layernorm_fwd"), ("gemm_ln_kernel", "gemm_ln_bf16"), ("clip_adam_kernel", "clip_adam"),
          ("xent_fused", "xent_fused"), ("sumsq_kernel", "grad_sumsq"), ("embed_bwd_kernel", "embed_bwd"), ("embed_fwd_kernel", "embed_fwd")]
 
 def kind_of(sym):
+    m = re.search(r"gemm_reg_kernelI(DF16b|f)Li([012])ELi([12])E", sym)  # one template, NBUF = 2 / 1: the double- / single-buffer kinds
+    if m:
+        return "gemm_%s_%s_%s" % ("dbuf" if m.group(3) == "2" else "sbuf", "bf16" if m.group(1) == "DF16b" else "f32", LAY[m.group(2)])
     for k, var in VAR.items():
         if k in sym and "grouped" not in sym:
             m = re.search(k + r"I(DF16b|f)Li([012])", sym)  # mangled: element type and layout are visible

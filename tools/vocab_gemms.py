@@ -1,5 +1,5 @@
 """The three vocabulary GEMMs of the C1 step on HBM-cold operands (the logits / d(logits) matrix is 487 MB: it never stays in the
-Infinity Cache), per-launch device time; IMT_GEMM_DBG=128 switches the 256-tile kernel's A operand to non-temporal LDS-DMA loads."""
+Infinity Cache), per-launch device time."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,7 +21,6 @@ def prof(fn, reps=6):
     return {rows[i].kind.decode(): rows[i].total_ms * 1e3 / reps for i in range(m)}
 slabs = torch.empty((4 * n, K), device=dev, dtype=torch.float32)
 dx = O.alloc_rows(n, K, torch.bfloat16, dev)
-print("env IMT_GEMM_DBG =", os.environ.get("IMT_GEMM_DBG", ""))
 print("fwd logits  ", prof(lambda i: O.gemm(x, w, O.IMT_NT, bias=b, out=dl[i % 2])))
 print("dX (slabs)  ", prof(lambda i: O.gemm(dl[i % 2], w, O.IMT_NN, out=dx, aux=slabs, aux_mode=O.IMT_AUX_SPLITK_WS, split_k=4, alpha_dev=g)))
 print("dW          ", prof(lambda i: O.gemm(dl[i % 2], x, O.IMT_TN, out=gw, accumulate=True, alpha_dev=g, a_colsum=gb)))
