@@ -209,6 +209,16 @@ class AlignArgs(Structure):
     ]
 
 
+class ConvArgs(Structure):
+    _fields_ = [
+        ("dtype", c_int32),
+        ("B", c_int32), ("H", c_int32), ("W", c_int32), ("Cin", c_int32), ("Cout", c_int32), ("KH", c_int32), ("KW", c_int32),
+        ("stride", c_int32), ("pad_h", c_int32), ("pad_w", c_int32), ("relu", c_int32),
+        ("x", c_void_p), ("w", c_void_p), ("y", c_void_p),
+        ("scale", c_void_p), ("shift", c_void_p), ("residual", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/imt_hip.h declares (tests/test_cabi.py checks)
 _P = c_void_p
 SIGNATURES = {
@@ -250,6 +260,10 @@ SIGNATURES = {
     "imt_align_supported": (c_int, [c_int, c_int]),
     "imt_align_pairs": (c_int, [POINTER(AlignArgs), _P]),
     "imt_scaled_sum": (c_int, [_P, c_int, c_float, _P, _P]),
+    "imt_conv2d_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "imt_conv2d": (c_int, [POINTER(ConvArgs), _P]),
+    "imt_maxpool2d_3x3s2": (c_int, [c_int, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "imt_image_nhwc": (c_int, [c_int, _P, _P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _P]),
     "imt_sumsq": (c_int, [_P, c_int64, _P, _P, _P]),
     "imt_ln_partial_reduce": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
     "imt_clip_adam": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, c_float, c_float, c_float, c_float, c_float, c_float,
@@ -319,7 +333,8 @@ ABI_STRUCTS = {"imt_gemm_args": GemmArgs, "imt_attn_args": AttnArgs, "imt_prof_r
                "imt_layer_desc": LayerDesc, "imt_stack_desc": StackDesc, "imt_stack_io": StackIO,
                "imt_attn_decode_args": AttnDecodeArgs, "imt_decode_io": DecodeIO, "imt_beam_args": BeamArgs,
                "imt_mass_args": MassArgs, "imt_score_args": ScoreArgs, "imt_sample_args": SampleArgs,
-               "imt_knn_args": KnnArgs, "imt_mlm_args": MlmArgs, "imt_align_args": AlignArgs}
+               "imt_knn_args": KnnArgs, "imt_mlm_args": MlmArgs, "imt_align_args": AlignArgs,
+               "imt_conv_args": ConvArgs}
 
 
 def load():

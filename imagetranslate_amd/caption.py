@@ -1,6 +1,7 @@
 """Caption a directory of images with beam search -- counterpart of src/caption.py (``build_model`` ``:62-73``,
 ``build_data_loader`` ``:49-59``, ``caption_batch`` ``:32-46``; same flags).  The image directory holds pre-extracted
-region features (``features.pt``, dataset.RegionFeatures) in place of pixels: the CNN trunk is outside the hot path.
+region features (``features.pt``, dataset.RegionFeatures) in place of pixels: ``python -m imagetranslate_amd.extract_features
+--images DIR --model MODEL --output DIR/features.pt`` writes them from a folder of JPEGs with the frozen CNN trunk.
 With ``--obj`` the detector output stored beside them (``obj_feats`` / ``obj_boxes`` / ``obj_labels``) feeds the object stream.
 ``--sampling`` (build extension) draws ``--nsamples`` N captions per image instead: sample k of image i is output line i*N + k."""
 import datetime

@@ -124,7 +124,7 @@ extern "C" int imt_abi_sizeof(const char* name) {
   IMT_SZ(imt_gemm_args); IMT_SZ(imt_attn_args); IMT_SZ(imt_prof_row); IMT_SZ(imt_attn_block); IMT_SZ(imt_layer_desc);
   IMT_SZ(imt_stack_desc); IMT_SZ(imt_stack_io); IMT_SZ(imt_attn_decode_args); IMT_SZ(imt_decode_io); IMT_SZ(imt_beam_args);
   IMT_SZ(imt_mass_args); IMT_SZ(imt_score_args); IMT_SZ(imt_sample_args); IMT_SZ(imt_knn_args);
-  IMT_SZ(imt_mlm_args); IMT_SZ(imt_align_args);
+  IMT_SZ(imt_mlm_args); IMT_SZ(imt_align_args); IMT_SZ(imt_conv_args);
 #undef IMT_SZ
   return -1;
 }

@@ -212,8 +212,9 @@ class MassDataset(Dataset):
 
 
 # ------------------------------------------------------------------------------------------- image / caption data
-# The CNN trunk is outside the hot path: what the reference computes from pixels with a frozen
-# torchvision ResNet (``ModifiedResnet`` up to ``x8.view().permute()``, src/image_model.py:24-36) enters here as
+# What the reference computes from pixels on every batch with a frozen torchvision ResNet (``ModifiedResnet`` up to
+# ``x8.view().permute()``, src/image_model.py:24-36) is a constant of the image: it is computed once, by
+# ``python -m imagetranslate_amd.extract_features`` (resnet.ResNetTrunk on the MFMA convolution kernels), and enters here as
 # pre-extracted region features.  A feature directory holds ``features.pt`` = torch.save({"paths": [str, ...],
 # "feats": Tensor[n_images, regions, C]}) (read with ``weights_only=True``).  The caption file is the reference's own:
 # marshal of (unique_images: {image id: path}, captions: [(image id, caption ids), ...]) (src/dataset.py:301-306).

@@ -591,6 +591,69 @@ def align_pairs(x, y, x_range, y_range, min_sim=float("-inf")):
     return link.long(), fwd_idx.long(), fwd_val, bwd_idx.long(), bwd_val
 
 
+def conv_out_size(size, kernel, stride, pad):
+    return (size + 2 * pad - kernel) // stride + 1
+
+
+def conv2d_nhwc(x, w, *, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False, out=None):
+    """y [B, Ho, Wo, Cout] = epilogue(conv(x [B, H, W, Cin], w [Cout, KH, KW, Cin])) on MFMA (include/imt_hip.h: imt_conv2d):
+    ``acc * scale + shift`` (fp32 [Cout]), ``+ residual`` (y's shape and type), ReLU.  ``pad``: int or (pad_h, pad_w).  x, w,
+    residual and ``out`` are dense (contiguous) tensors of one dtype."""
+    if x.dim() != 4 or w.dim() != 4 or x.shape[3] != w.shape[3] or x.dtype != w.dtype:
+        raise ValueError("conv2d_nhwc: x %s %s against w %s %s" % (tuple(x.shape), x.dtype, tuple(w.shape), w.dtype))
+    _req_cuda(x, w, scale, shift, residual, out)
+    B, H, W, Cin = x.shape
+    Cout, KH, KW, _ = w.shape
+    pad_h, pad_w = (pad, pad) if isinstance(pad, int) else pad
+    Ho, Wo = conv_out_size(H, KH, stride, pad_h), conv_out_size(W, KW, stride, pad_w)
+    shape = (B, max(Ho, 0), max(Wo, 0), Cout)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=x.dtype)
+    for name, t, want, dtype in (("x", x, tuple(x.shape), x.dtype), ("w", w, tuple(w.shape), x.dtype), ("out", out, shape, x.dtype),
+                                 ("residual", residual, shape, x.dtype), ("scale", scale, (Cout,), torch.float32),
+                                 ("shift", shift, (Cout,), torch.float32)):
+        if t is not None and (tuple(t.shape) != want or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError("conv2d_nhwc: %s must be contiguous %s %s, got %s %s" % (name, want, dtype, tuple(t.shape), t.dtype))
+    a = L.ConvArgs()
+    a.dtype = dt(x)
+    a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = B, H, W, Cin, Cout, KH, KW
+    a.stride, a.pad_h, a.pad_w, a.relu = stride, pad_h, pad_w, int(bool(relu))
+    a.x, a.w, a.y = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.scale = scale.data_ptr() if scale is not None else None
+    a.shift = shift.data_ptr() if shift is not None else None
+    a.residual = residual.data_ptr() if residual is not None else None
+    L.check(L.load().imt_conv2d(ctypes.byref(a), _stream()), "imt_conv2d")
+    return out
+
+
+def maxpool2d_nhwc(x):
+    """3 x 3, stride 2, padding 1 max pool of x [B, H, W, C] (NHWC, C % 8 == 0); padding counts as -inf."""
+    if x.dim() != 4:
+        raise ValueError("maxpool2d_nhwc: x must be [B, H, W, C], got %s" % (tuple(x.shape),))
+    _req_cuda(x)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), device=x.device, dtype=x.dtype)
+    L.check(L.load().imt_maxpool2d_3x3s2(dt(x), _p(x), _p(out), B, H, W, C, _stream()), "imt_maxpool2d_3x3s2")
+    return out
+
+
+IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)  # transforms.Normalize of src/dataset.py:286-288
+
+
+def image_to_nhwc(img, dtype=torch.float32, mean=IMAGE_MEAN, std=IMAGE_STD):
+    """uint8 [B, H, W, 3] decoded images -> [B, H, W, 8] network input: (v / 255 - mean) / std in channels 0-2, zeros in 3-7."""
+    if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8:
+        raise ValueError("image_to_nhwc: uint8 [B, H, W, 3] expected, got %s %s" % (tuple(img.shape), img.dtype))
+    _req_cuda(img)
+    img = img.contiguous()
+    B, H, W, _ = img.shape
+    out = torch.empty((B, H, W, 8), device=img.device, dtype=dtype)
+    m, s = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    L.check(L.load().imt_image_nhwc(dt(out), _p(img), _p(out), B, H, W, m, s, _stream()), "imt_image_nhwc")
+    return out
+
+
 def log_softmax_bwd(dlp, lp, out_dtype):
     _req_cuda(dlp, lp)
     N, V = lp.shape

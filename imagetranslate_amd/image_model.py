@@ -2,9 +2,12 @@
 ``ImageMassSeq2Seq`` (text branch ``:157-183``, gated text + image branch ``:185-230``, contrastive branch ``:231-264``),
 ``ImageCaptioning`` (``:267-377``) and ``Caption2Image`` (``:380-464``).
 
-The CNN trunk (torchvision ResNet / Faster-RCNN, ``:14-124``) is OUT of scope (frozen
-feature extractor whose pretrained weights need a network fetch); region features ``[B, 49, C]`` enter at the
-``fc`` layer: ``ImageHead`` = dropout -> fc (no bias) -> + location_embedding -> dropout (``:35-41,77-78``).
+The frozen ResNet trunk (``:24-36``) is ``resnet.ResNetTrunk`` on the MFMA convolution kernels (csrc/conv.hip): attached to
+the head with ``ImageHead.attach_trunk`` it turns 4-D pixel inputs into region features, and
+``python -m imagetranslate_amd.extract_features`` writes them to the ``features.pt`` the trainers read.  It is never trained
+(DESIGN.md section 1), so region features ``[B, 49, C]`` may as well enter pre-extracted at the ``fc`` layer:
+``ImageHead`` = dropout -> fc (no bias) -> + location_embedding -> dropout (``:35-41,77-78``).  The Faster-RCNN detector
+(``:42-124``) stays out of scope.
 The detector's output (box features, boxes, labels) enters pre-extracted as ``batch["objects"]``: ``ImageCaptioning``
 then runs its object stream (object rows ``:58-78``, ``obj_decoder`` and ``multistream_attention_gate`` ``:357-366``).
 ``ImageMassSeq2Seq`` with ``batch=`` runs its decoder over the text states and over the image regions and mixes the two with
@@ -175,8 +178,36 @@ class ImageHead(nn.Module):
         self.layer_norm = nn.LayerNorm(embed_dim, eps=1e-12)  # present (unused) in the reference, :103
         self.fcnn = None
 
+    def attach_trunk(self, trunk):
+        """Keep a frozen ``resnet.ResNetTrunk`` for pixel inputs.  It is not a registered submodule: it has no gradients, so it
+        stays out of the flat parameter store, of ``parameters()`` and of ``state_dict()`` (``save`` writes its tensors itself)."""
+        if trunk is not None and trunk.out_channels != self.fc.in_features:
+            raise ValueError("image head: the trunk gives %d channels, fc was built for %d" % (trunk.out_channels, self.fc.in_features))
+        self.__dict__["_imt_trunk"] = trunk
+        return self
+
+    @property
+    def trunk(self):
+        return self.__dict__.get("_imt_trunk")
+
+    def region_features(self, pixels, compute_dtype=torch.float32):
+        """Pixels (4-D: ``[B, H, W, 8]`` from ``hip_ops.image_to_nhwc``, uint8 ``[B, H, W, 3]`` or normalised NCHW) through the
+        attached trunk: ``[B, regions, feat_dim]`` (src/image_model.py:24-36)."""
+        trunk = self.trunk
+        if trunk is None:
+            raise ValueError("image head: a 4-D input is pixels and needs the CNN trunk -- attach one with "
+                             "image_model.attach_trunk(ResNetTrunk(depth).load_state_dict(weights)), or pass region features "
+                             "[B, regions, %d] (python -m imagetranslate_amd.extract_features writes them)" % self.fc.in_features)
+        dev = self.fc.weight.device
+        if trunk.device != dev:
+            trunk.to(dev)
+        return trunk.set_compute_dtype(compute_dtype)(pixels)
+
     def forward(self, grid_hidden, compute_dtype=torch.float32):
-        """grid_hidden: region features [B, regions, feat_dim] (the reference's x8.view().permute(), :35-36)."""
+        """grid_hidden: region features [B, regions, feat_dim] (the reference's x8.view().permute(), :35-36), or 4-D pixels,
+        which run the attached trunk first."""
+        if grid_hidden.dim() == 4:
+            grid_hidden = self.region_features(grid_hidden, compute_dtype)
         x = grid_hidden.to(self.fc.weight.device)
         p = float(self.dropout) if self.training else 0.0
         seed = dropout_seed(self, p > 0)
@@ -253,8 +284,8 @@ class ImageMassSeq2Seq(MassSeq2Seq):
                                                num_attention_heads=num_attention_heads)
         if image_feat_dim is None:
             image_feat_dim = 512 if resnet_depth <= 2 else 2048  # fc.in_features of resnet18/34 vs 50+ (:87-97)
-        # the reference builds a pretrained torchvision trunk here unconditionally (:136-138, network fetch);
-        # the build keeps only the trainable head -- region features enter at `fc`.
+        # the reference builds a pretrained torchvision trunk here unconditionally (:136-138, network fetch); here the head is
+        # built alone and a trunk (resnet.ResNetTrunk) is attached by `load` or by the caller when pixels are to be read.
         self.image_model = ImageHead(image_feat_dim, self.config.hidden_size, self.config.hidden_dropout_prob)
         self.multimodal_attention_gate = nn.Parameter(torch.zeros(1, self.config.hidden_size).fill_(0.1),
                                                       requires_grad=True)

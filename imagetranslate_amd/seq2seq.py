@@ -627,11 +627,14 @@ class Seq2Seq(FlatStoreModel):
         with open(os.path.join(out_dir, "mt_config"), "wb") as fp:
             pickle.dump((self.lang_dec, self.use_proposals, self.enc_layer, self.dec_layer, self.embed_dim,
                          self.intermediate_dim, self.tie_embed, self.resnet_depth, self.freeze_image), fp)
-        torch.save({k: v.detach().cpu() for k, v in self.state_dict().items()},
-                   os.path.join(out_dir, "mt_model.state_dict"))
+        sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
+        img = self.__dict__.get("_modules", {}).get("image_model")
+        trunk = getattr(img, "trunk", None)
+        if trunk is not None:  # the frozen trunk's tensors under the reference's names (image_model.conv1.weight, ...)
+            sd.update(trunk.state_dict(prefix="image_model."))
+        torch.save(sd, os.path.join(out_dir, "mt_model.state_dict"))
         # build extension (the reference hard-codes 12 heads, src/seq2seq.py:37): remembered beside the reference files
         extra = {"num_attention_heads": int(self.config.num_attention_heads)}
-        img = self.__dict__.get("_modules", {}).get("image_model")
         if img is not None and hasattr(img, "fc"):  # channels of the region features the `fc` layer was built for
             extra["image_feat_dim"] = int(img.fc.in_features)
         with open(os.path.join(out_dir, "imt_config.json"), "w") as fp:
@@ -660,4 +663,8 @@ class Seq2Seq(FlatStoreModel):
                        freeze_image=freeze_image, resnet_depth=resnet_depth, use_obj=use_obj, **kw)
         sd = torch.load(os.path.join(out_dir, "mt_model.state_dict"), map_location="cpu", weights_only=True)
         mt_model.load_state_dict(sd, strict=False)
+        img = mt_model.__dict__.get("_modules", {}).get("image_model")
+        if img is not None and "image_model.conv1.weight" in sd:  # a checkpoint that carries the frozen CNN trunk
+            from .resnet import ResNetTrunk
+            img.attach_trunk(ResNetTrunk(resnet_depth).load_state_dict(sd, prefix="image_model."))
         return mt_model.to(device)

@@ -47,7 +47,7 @@ const char* imt_last_error(void);
  * launches (2*M*N*K per GEMM; minimal operand traffic for the HBM-bound kernels).  Off by default. */
 /* sizeof() of the argument structures below as THIS library was compiled, by name ("imt_gemm_args", "imt_attn_args",
  * "imt_prof_row", "imt_attn_block", "imt_layer_desc", "imt_stack_desc", "imt_stack_io", "imt_attn_decode_args",
- * "imt_decode_io", "imt_beam_args", "imt_mass_args", "imt_score_args", "imt_sample_args"); -1 for an unknown name.  A binding checks its own layout against it
+ * "imt_decode_io", "imt_beam_args", "imt_mass_args", "imt_score_args", "imt_sample_args", "imt_conv_args"); -1 for an unknown name.  A binding checks its own layout against it
  * once at load time (imagetranslate_amd/_lib.py does): a stale binding then fails loudly instead of passing shifted fields. */
 int imt_abi_sizeof(const char* struct_name);
 
@@ -389,6 +389,49 @@ int imt_align_supported(int dtype, int d);
 int imt_align_pairs(const imt_align_args* a, void* stream);
 /* out[0] = scale * sum(x[0..n)), fixed summation order: the `.mean()` of the per-row losses (train_image_mt.py:282). */
 int imt_scaled_sum(const float* x, int n, float scale, float* out, void* stream);
+
+/* ------------------------------------------------------------------ frozen ResNet trunk: pixels -> region features
+ * ModifiedResnet up to x8.view().permute() (src/image_model.py:24-36; init_net :85-97 picks the depth): conv1 / bn1 / relu /
+ * maxpool / layer1..4 of a torchvision ResNet in inference mode.  Forward only; BatchNorm arrives folded into a per-channel
+ * scale and shift.  Activations are NHWC, so the last layer's [B, H/32, W/32, C] IS the reference's
+ * view(B, C, -1).permute(0, 2, 1).
+ *
+ * imt_conv2d: 2-D convolution as an implicit GEMM on MFMA.  x [B, H, W, Cin], w [Cout, KH, KW, Cin], y [B, Ho, Wo, Cout], all of
+ *   `dtype`, Ho = (H + 2 pad_h - KH) / stride + 1 (floored), Wo likewise; stride 1 or 2, symmetric zero padding, dilation 1,
+ *   groups 1.  GEMM view M = B Ho Wo, N = Cout, K = KH KW Cin in (kh, kw, c) order; fp32 accumulation, K ascending (imt_gemm's
+ *   rule; IMT_F32 is the exact fp32 MFMA chain).  Epilogue on the fp32 accumulator, in this order:
+ *     v = acc * scale[c] + shift[c]      (fp32 [Cout], each nullable: 1 / 0)
+ *     v += residual[b, ho, wo, c]        (T, nullable)
+ *     v = max(v, 0) when relu != 0
+ *   then one store as T.  Cin must be a multiple of 8 (a tap is whole 16-byte chunks; the stem's 3 channels are padded to 8 by
+ *   imt_image_nhwc and zero weights); M, Cout and K need not be whole tiles and H, W may be odd.  A tap in the padding contributes
+ *   zeros by predicate: no byte outside x's B H W Cin elements is read and none outside y is written, whatever surrounds them.
+ *   One launch (profiling kind conv_bf16 / conv_f32), one writer per output element, no atomics, no workspace: two calls give
+ *   the same bits.
+ *   Refused before any launch with IMT_ERR_BAD_ARG: null args, x, w or y; a bad dtype; a non-positive size; stride outside
+ *   {1, 2}; negative padding; Cin % 8 != 0; Ho or Wo <= 0; x, w, y or residual off a 16-byte boundary; B H W or B Ho Wo beyond
+ *   the kernel's 32-bit pixel index, K beyond 31 bits, or an operand whose byte size overflows its 64-bit offsets.
+ *   imt_conv2d_supported: 1 for a (dtype, Cin, KH, KW, stride) the kernel takes.
+ * imt_maxpool2d_3x3s2: NHWC max pool, kernel 3, stride 2, padding 1 (the stem's nn.MaxPool2d): y [B, (H - 1) / 2 + 1,
+ *   (W - 1) / 2 + 1, C].  Padding counts as -inf, so an all-negative window keeps its negative maximum.  C % 8 == 0 (16-byte
+ *   loads over channels).  Profiling kind maxpool_bf16 / maxpool_f32.
+ * imt_image_nhwc: decoded images uint8 [B, H, W, 3] (what PIL hands over; transforms.ToTensor + Normalize of
+ *   src/dataset.py:283-289) -> out [B, H, W, 8] of `dtype`: channels 0-2 = (v / 255 - mean[c]) / std[c], evaluated in fp64 and
+ *   rounded once to fp32 (then to bf16); channels 3-7 = 0.  host_mean / host_std: 3 HOST floats each.  Profiling kind image_*. */
+typedef struct imt_conv_args {
+  int32_t dtype;                          /* IMT_F32 / IMT_BF16: type of x, w, y and residual */
+  int32_t B, H, W, Cin, Cout, KH, KW;
+  int32_t stride, pad_h, pad_w;
+  int32_t relu;
+  const void* x; const void* w; void* y;
+  const float* scale; const float* shift; /* fp32 [Cout], nullable */
+  const void* residual;                   /* [B, Ho, Wo, Cout], nullable */
+} imt_conv_args;
+int imt_conv2d_supported(int dtype, int Cin, int KH, int KW, int stride);
+int imt_conv2d(const imt_conv_args* a, void* stream);
+int imt_maxpool2d_3x3s2(int dtype, const void* x, void* y, int B, int H, int W, int C, void* stream);
+int imt_image_nhwc(int dtype, const uint8_t* img, void* out, int B, int H, int W, const float* host_mean, const float* host_std,
+                   void* stream);
 
 /* ------------------------------------------------------------------ data-parallel gradient exchange (RCCL over xGMI)
  * Replaces torch DistributedDataParallel's NCCL all-reduce of src/train_image_mt.py:72-76 (bootstrap src/utils.py:93-97):
