@@ -129,6 +129,22 @@ def layernorm_fwd_bwd(x, gamma, beta, dy, eps):
     return y, mean.squeeze(-1), rstd.squeeze(-1), dx, (dy * xh).sum(0), dy.sum(0)
 
 
+LN_TOL = {torch.float32: 1e-5, torch.bfloat16: 1.5e-2}   # of the row's largest |y|; bf16: two roundings of 2^-7 and slack
+
+
+def layernorm_bounds(x, y_ref, rstd_ref, dtype):
+    """Element-wise bounds (y [rows, 1], mean [rows], rstd [rows]) of a LayerNorm forward over the rows ``x`` in ``dtype``:
+    y within LN_TOL of the row's largest |y_ref|; an fp32 sum of d terms is off by a few ulp of sum|x|, so the mean by that
+    over d; rstd is well conditioned.  One definition for tests/test_gpu_row_edges.py and tests/test_gpu_dense_ln_edges.py."""
+    y_ref, rstd_ref = _d(y_ref), _d(rstd_ref)
+    return LN_TOL[dtype] * y_ref.abs().max(dim=-1, keepdim=True).values, 1e-5 * _d(x).abs().mean(-1), 1e-5 * rstd_ref
+
+
+def layernorm_dx_bound(dx_ref, dtype):
+    """Element-wise bound [rows, 1] of imt_layernorm_bwd's dx: twice the forward tolerance of the row's largest |dx_ref|."""
+    return 2 * LN_TOL[dtype] * _d(dx_ref).abs().max(dim=-1, keepdim=True).values
+
+
 def layernorm_param_grad_mags(x, dy, eps):
     """(sum_rows |dy * xhat|, sum_rows |dy|): the magnitudes the column sums dgamma / dbeta are made of."""
     x, dy = _d(x), _d(dy)
