@@ -138,11 +138,13 @@ def grouped_tall_min_tiles(min_tiles):
 
 
 def gemm_grouped_tn(problems, tile_rows=0):
-    """problems: list of dicts(A=dy[K,M], B=x[K,N], out=fp32 grad [M,N], a_colsum=optional) -> one launch.
+    """problems: list of dicts(A=dy[K,M], B=x[K,N], out=fp32 grad [M,N], a_colsum=optional, alpha=optional, 1.0) -> one launch
+    (one imt_gemm per product where the list is not groupable: imt_gemm_grouped_tn).
     tile_rows (tests / tuning): 256 = the 256 x 128 instance whenever every row count allows it, 128 = never, 0 = the policy."""
     arr = (L.GemmArgs * len(problems))()
     for i, pr in enumerate(problems):
-        arr[i] = gemm(pr["A"], pr["B"], IMT_TN, out=pr["out"], accumulate=True, a_colsum=pr.get("a_colsum"), _launch=False)
+        arr[i] = gemm(pr["A"], pr["B"], IMT_TN, out=pr["out"], accumulate=True, a_colsum=pr.get("a_colsum"), alpha=pr.get("alpha", 1.0),
+                      _launch=False)
     with grouped_tall_min_tiles({128: 1 << 30, 256: 1}[tile_rows]) if tile_rows else contextlib.nullcontext():
         L.check(L.load().imt_gemm_grouped_tn(arr, len(problems), _stream()), "imt_gemm_grouped_tn")
 
