@@ -307,6 +307,7 @@ SIGNATURES = {
     "imt_stack_workspace_bytes": (c_int64, [POINTER(StackDesc), c_int, c_int, c_int]),
     "imt_stack_forward": (c_int, [POINTER(StackDesc), POINTER(StackIO), _P, c_int64, _P]),
     "imt_stack_backward": (c_int, [POINTER(StackDesc), POINTER(StackIO), _P, c_int64, c_int, c_int, _P]),
+    "imt_stack_dw_schedule": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "imt_attention_decode": (c_int, [POINTER(AttnDecodeArgs), _P]),
     "imt_decode_workspace_bytes": (c_int64, [POINTER(StackDesc), c_int]),
     "imt_decode_self_cache_bytes": (c_int64, [POINTER(StackDesc), c_int, c_int]),

@@ -160,6 +160,22 @@ def grouped_tile_order(grids, plain=False):
     return [(order[3 * w], order[3 * w + 1], order[3 * w + 2]) for w in range(total)]
 
 
+DW_HOLD, DW_FLUSH_MAIN, DW_FLUSH_SIDE = 0, 1, 2
+
+
+def stack_dw_schedule(n_layers, layer_lo, layer_hi, side_stream, pairable):
+    """Where imt_stack_backward(layer_lo, layer_hi) sends the weight-gradient launch of each layer (imt_stack_dw_schedule):
+    ``pairable[l]`` says whether layer l's products would take the 256 x 128 instance with as many again.  Returns
+    ([(layer, wait_done, action, with_held)] from layer_hi - 1 down to layer_lo, join_done).  Host only."""
+    n = layer_hi - layer_lo
+    pair = (ctypes.c_int * max(1, n_layers))(*[int(bool(x)) for x in pairable])
+    rec = (ctypes.c_int * max(1, 3 * n))()
+    join = ctypes.c_int(-1)
+    L.check(L.load().imt_stack_dw_schedule(n_layers, layer_lo, layer_hi, int(side_stream), pair, rec, ctypes.byref(join)),
+            "imt_stack_dw_schedule")
+    return [(layer_hi - 1 - i, rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]) for i in range(n)], join.value
+
+
 def gemm_bias_residual_ln(x, w, bias, resid, gamma, beta, eps=1e-12, dropout_p=0.0, dropout_seed=0, want_pre_ln=True):
     """out = LayerNorm(dropout(x w^T + bias) + resid) in one launch (imt_gemm_bias_residual_ln); returns
     (out, pre_ln or None, mean, rstd)."""

@@ -711,6 +711,18 @@ int imt_stack_forward(const imt_stack_desc* m, const imt_stack_io* io, void* ws,
  * library's side stream, concurrently with the next layer's input-gradient chain (joined before return). */
 int imt_stack_backward(const imt_stack_desc* m, const imt_stack_io* io, void* ws, int64_t ws_bytes, int layer_lo,
                        int layer_hi, void* stream);
+/* The decisions of that call about its weight-gradient launches, evaluated on the host (no GPU needed, no device call):
+ * for a stack of n_layers, the range [layer_lo, layer_hi), the side stream on or off, and pairable[l] != 0 where the products
+ * of layer l and as many again would take the 256 x 128 instance of the grouped launch (HOST array of n_layers).
+ * records[3i .. 3i+2] for layer l = layer_hi - 1 - i: {wait_done, action, with_held}.  wait_done: the layer whose side-stream
+ * launch must be over before layer l writes its scratch set (l + 4: same set), or -1.  action: the products of layer l are
+ * held for the layer below, or launched on the main or the side stream -- together with those of layer with_held (or -1).
+ * *join_done (nullable): the layer whose side-stream launch the call waits for before it returns, or -1. */
+#define IMT_DW_HOLD 0
+#define IMT_DW_FLUSH_MAIN 1
+#define IMT_DW_FLUSH_SIDE 2
+int imt_stack_dw_schedule(int n_layers, int layer_lo, int layer_hi, int side_stream, const int* pairable, int* records,
+                          int* join_done);
 
 /* ------------------------------------------------------------------ incremental decoding + beam search
  * Replaces the per-step work of BeamDecoder.forward (src/seq_gen.py:131-227).  The reference re-runs the decoder
